@@ -14,7 +14,10 @@ tiles are independent, so N GPUs run N batches (weak scaling, no data-path colle
 "single RCCL all-gather" that reassembles the displacement field is issued once per timed batch of K steps
 and is inside the timed region (--gather none leaves it out; the JSON reports its cost separately).
 
-Prints ONE JSON line on rank 0.  value = all grids of all ranks / max-over-ranks wall time.
+Prints ONE JSON line on rank 0.  value = all grids of all ranks / max-over-ranks wall time.  A plain run times the steps
+and nothing else; --full adds the roofline (kernels sampled inside the timed region), the legs outside it (gen, the 64 x 64
+frame, 1024^2 x 16, the steps without the gather), the committed parity figures and the cpu_baseline leg: their keys are
+null without it.  --dump-outputs DIR writes the maps of the last timed step (dump_outputs).
 Inputs: example-ocean parameters, seeds mt19937(1000 + global cascade index), synthetic by construction.
 """
 
@@ -92,7 +95,18 @@ def parse():
                          "an N-rank run on ONE GPU (all ranks on device 0; --gather none, or up to RCCL's refusal of two ranks on one device)")
     ap.add_argument("--cpu-baseline-child", nargs=3, metavar=("N", "CASCADES", "SECONDS"), default=None,
                     help="internal: the cpu_baseline leg, run as a child process with pinned OpenMP threads; prints one JSON object")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the kernels sampled inside the timed region and timed again behind it (roofline), the "
+                         "beyond-Infinity-Cache leg, ocean.gen, the 64 x 64 reference frame, the steps again without the gather (N > 1), every "
+                         "rank's report, the output sanity check, the committed parity figures and the cpu_baseline leg.  Without it a run sets "
+                         "up, warms up, times --steps steps and prints the line (--cpu-seconds, --no-frame, --no-check and --no-regime apply "
+                         "to --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps of the last one (rank 0's cascades) to DIR as float32 .npy: dump_outputs")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _code_only(text):
@@ -386,6 +400,34 @@ def baseline_config(N, C, world, spectrum):
     return "no BASELINE.json config has this shape"
 
 
+DUMP_BYTES = 48 << 20      # at most this much of --dump-outputs (the limit is 64 MB)
+DUMP_SEED = 20260
+
+
+def dump_outputs(path, maps, N, C):
+    """--dump-outputs: what the timed path hands a caller after its last step, the maps of this rank's C cascades as the
+    logical image [layer][y][x][4] (layer 0: dx dy dz 0, layer 1: nx ny nz 0, capi.map_layers), written as
+    path/maps.npy, float32.  All of it, shape (C, 2, N, N, 4), while that is at most DUMP_BYTES; beyond that the same
+    K points of every cascade and layer, shape (C, 2, K, 4), K = DUMP_BYTES / (32 C) flat indices y * N + x drawn without
+    replacement by numpy.random.default_rng(DUMP_SEED) and sorted: fixed for a given N and C."""
+    import torch
+
+    from datum_amd import capi
+
+    os.makedirs(path, exist_ok=True)
+    block = capi.map_block_floats(N)
+    k = min(N * N, DUMP_BYTES // (32 * C))
+    idx = None
+    if k < N * N:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(N * N, size=k, replace=False))
+        idx = torch.from_numpy(pick).to(maps.device)
+    out = np.empty((C, 2, N, N, 4) if idx is None else (C, 2, k, 4), np.float32)
+    for c in range(C):
+        layers = capi.map_layers(maps[c * block: (c + 1) * block], N)
+        out[c] = (layers if idx is None else layers.reshape(2, N * N, 4)[:, idx]).cpu().numpy()
+    np.save(os.path.join(path, "maps.npy"), out)
+
+
 def main():
     args = parse()
 
@@ -576,16 +618,19 @@ def main():
     # measurement took 4.6 % off the figure it rides on.  Below 64 steps the timed region therefore carries TWO samples of each kernel (a quarter
     # and three quarters of the way through: the first step behind the barrier starts on an idle device and is not typical), and the same kernels
     # are timed on EVERY step of a second, untimed pass right behind it (roofline.after_region), which says whether the two were representative.
+    # (--full only: a plain run times the steps alone)
+    full = args.full
     stride = int(os.environ.get("DATUM_BENCH_STRIDE", "0")) or (32 if args.steps >= 512 else (8 if args.steps >= 64 else max(1, args.steps // 2)))
     first_sample = args.steps // 4 if (args.steps < 64 and "DATUM_BENCH_STRIDE" not in os.environ) else 0
     nsamples = (args.steps - first_sample + stride - 1) // stride
-    oc.profile_begin(nsamples, stride)             # (the events exist from here on; the sampling proper is switched on at step `first_sample`)
-    oc.profile_end()
+    if full:
+        oc.profile_begin(nsamples, stride)             # (the events exist from here on; the sampling proper is switched on at step `first_sample`)
+        oc.profile_end()
     ev0, ev1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
     steps_done = [0]
 
     def timed_step():
-        if steps_done[0] == first_sample:
+        if full and steps_done[0] == first_sample:
             oc.profile_begin(nsamples, stride)     # a host-side switch: no GPU work, and the host runs several steps ahead of the device
         steps_done[0] += 1
         step()
@@ -636,11 +681,15 @@ def main():
         torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
 
-    row_ms, col_ms, nprof = oc.profile_end()
+    # the maps of the last timed step, before anything below runs further steps on the same handle
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, maps, N, C)
+
+    row_ms, col_ms, nprof = oc.profile_end() if full else (0.0, 0.0, 0)
 
     # few samples inside the timed region (short runs): the same steps once more with every launch timed, outside the timed region
     after_region = None
-    if nprof < 8 and not (multi and gathering):
+    if full and nprof < 8 and not (multi and gathering):
         na = min(args.steps, 40)
         torch.cuda.synchronize(dev)
         oc.profile_begin(na, 1)
@@ -654,7 +703,7 @@ def main():
     # SURVEY.md 8e asks for both figures: with the gather (the timed region above, `value`) and the tiles' throughput without it.
     # The same K steps once more, outside the timed region, no pack and no collective in flight; max over ranks like `value`.
     plain_elapsed = 0.0
-    if multi and gathering:
+    if full and multi and gathering:
         torch.cuda.synchronize(dev)
         dist.barrier()
         torch.cuda.synchronize(dev)
@@ -670,7 +719,7 @@ def main():
     # Infinity Cache and its kernels run above what HBM alone delivers; the same kernels over 16 cascades (1 GB) cannot.  Ten
     # steps after five, every step's two kernels timed with dispatch events, fractions on ALGORITHMIC bytes like `roofline`.
     regime = None
-    if rank == 0 and world == 1 and not args.no_regime and (N, C, args.spectrum) == (1024, 4, "fp32"):
+    if full and rank == 0 and world == 1 and not args.no_regime and (N, C, args.spectrum) == (1024, 4, "fp32"):
         RC = 16
         with capi.Ocean(N, RC, device=local_rank) as big:
             big.set_stream(stream.cuda_stream)
@@ -722,7 +771,7 @@ def main():
     # ocean.gen (reported separately, as vertices/s): the 1024 x 1024 projected-grid mesh of the example
     # (examples/ocean/ocean.cpp:59) from cascade 0's maps, outside the timed region above
     gen = None
-    if rank == 0:
+    if full and rank == 0:
         sx = sy = 1024
         verts = torch.empty(sx * sy * 12, dtype=torch.float32, device=dev)
         g0, g1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
@@ -741,7 +790,7 @@ def main():
     # the reference's own frame: WaveResolution = 64, one cascade, update_ocean + the five dispatches with a
     # 1024 x 1024 mesh (examples/ocean/ocean.cpp:59,135,179) -- launch- and latency-bound, reported beside the headline
     frame = None
-    if rank == 0 and not args.no_frame:
+    if full and rank == 0 and not args.no_frame:
         p64 = host_api.OceanParams(64, **host_api.EXAMPLE_TUNABLES)
         p64.seed_ocean(1000)
         with capi.Ocean(64, 1, device=local_rank) as o64:
@@ -779,46 +828,89 @@ def main():
     # collective time, whether its CU partition was applied or refused (and why), its RCCL and the channel settings in its environment
     per_rank = None
     if multi:
-        mine = rank_report(rank, local_rank, compute_ms, gather_ms, elapsed * 1e3, plain_elapsed * 1e3, partition_state, (farm_info["rccl_version"] if native else None))
-        box = [None] * world
-        dist.all_gather_object(box, mine)
-        per_rank = box
+        if full:
+            mine = rank_report(rank, local_rank, compute_ms, gather_ms, elapsed * 1e3, plain_elapsed * 1e3, partition_state, (farm_info["rccl_version"] if native else None))
+            box = [None] * world
+            dist.all_gather_object(box, mine)
+            per_rank = box
         t = torch.tensor([elapsed, compute_ms, gather_ms, plain_elapsed], dtype=torch.float64, device=(dev if args.rendezvous == "nccl" else "cpu"))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, compute_ms, gather_ms, plain_elapsed = (float(v) for v in t.tolist())
 
     if rank == 0:
         # sanity: the maps of the last step are finite and non-trivial
-        chk = capi.map_layers(maps[: capi.map_block_floats(N)], N)
-        if not args.no_check:
+        if full and not args.no_check:
+            chk = capi.map_layers(maps[: capi.map_block_floats(N)], N)
             assert bool(torch.isfinite(chk).all()) and float(chk[0, ..., 2].abs().max()) > 0
 
         grids = args.steps * C * world
-        row_b, col_b = oc.algorithmic_bytes()
-        # what the two kernels move by design: two packed fields instead of three and 24-byte texels (the
-        # zero .w channels of the two map layers are not stored) -- 32 + 40 B/pt in fp32, 24 + 32 with the fp16-stored spectrum --
-        # against the 40 + 56 (24 + 44) algorithmic bytes `achieved` is computed from
-        pts = float(N) * N * C
-        texel = capi.map_layout(N)[3]
-        half = args.spectrum != "fp32"
-        moved = (({"fp32": 32.0, "fp16": 24.0, "fp16h0": 20.0}[args.spectrum]) * pts, ((8.0 if half else 16.0) + texel) * pts)
-        # the dominant kernel: strictly the longer of the two (round 5; round 4's tie-break towards the column pass picked the
-        # kernel with the larger figure: ADVICE r04)
-        dom = ("colpass", col_ms, col_b, moved[1]) if col_ms > row_ms else ("rowpass", row_ms, row_b, moved[0])
-        step_ach = (row_b + col_b) / ((row_ms + col_ms) * 1e-3) / 1e9 if row_ms + col_ms > 0 else 0.0
+        roofline = None
+        if full:
+            row_b, col_b = oc.algorithmic_bytes()
+            # what the two kernels move by design: two packed fields instead of three and 24-byte texels (the
+            # zero .w channels of the two map layers are not stored) -- 32 + 40 B/pt in fp32, 24 + 32 with the fp16-stored spectrum --
+            # against the 40 + 56 (24 + 44) algorithmic bytes `achieved` is computed from
+            pts = float(N) * N * C
+            texel = capi.map_layout(N)[3]
+            half = args.spectrum != "fp32"
+            moved = (({"fp32": 32.0, "fp16": 24.0, "fp16h0": 20.0}[args.spectrum]) * pts, ((8.0 if half else 16.0) + texel) * pts)
+            # the dominant kernel: strictly the longer of the two (round 5; round 4's tie-break towards the column pass picked the
+            # kernel with the larger figure: ADVICE r04)
+            dom = ("colpass", col_ms, col_b, moved[1]) if col_ms > row_ms else ("rowpass", row_ms, row_b, moved[0])
+            step_ach = (row_b + col_b) / ((row_ms + col_ms) * 1e-3) / 1e9 if row_ms + col_ms > 0 else 0.0
 
-        kernel_name = f"ocean_{dom[0]}_kernel<{N}>"
-        traffic, traffic_source = measured_traffic(kernel_name, f"{N}x{N} x {C} cascades") if args.spectrum == "fp32" else (None, None)
-        # roofline.frac is a PHYSICAL fraction (<= 1 by construction): the bytes that cross the L2's memory side per launch -- the PMC
-        # figure for this kernel, workload and kernel source when profiles/ holds one, otherwise the bytes the kernel moves by design
-        # (the two agree within 3 % wherever both exist) -- over the launch duration measured here over 8 TB/s.  The figure on SURVEY
-        # 8d's ALGORITHMIC bytes (which the kernels do not all move) is kept beside it as frac_on_survey_bytes.
-        phys_bytes = float(traffic) if traffic is not None else dom[3]
-        ach = phys_bytes / (dom[1] * 1e-3) / 1e9 if dom[1] > 0 else 0.0
-        survey_ach = dom[2] / (dom[1] * 1e-3) / 1e9 if dom[1] > 0 else 0.0
-        # h0 8 (4 as halves) + phase 4 + work spectrum 16 (8 as halves) + maps: what one step touches
-        working_set = (({"fp32": 28.0, "fp16": 20.0, "fp16h0": 16.0}[args.spectrum]) + texel) * pts
-        residency = "infinity-cache" if working_set < 256 * 2**20 else "hbm"
+            kernel_name = f"ocean_{dom[0]}_kernel<{N}>"
+            traffic, traffic_source = measured_traffic(kernel_name, f"{N}x{N} x {C} cascades") if args.spectrum == "fp32" else (None, None)
+            # roofline.frac is a PHYSICAL fraction (<= 1 by construction): the bytes that cross the L2's memory side per launch -- the PMC
+            # figure for this kernel, workload and kernel source when profiles/ holds one, otherwise the bytes the kernel moves by design
+            # (the two agree within 3 % wherever both exist) -- over the launch duration measured here over 8 TB/s.  The figure on SURVEY
+            # 8d's ALGORITHMIC bytes (which the kernels do not all move) is kept beside it as frac_on_survey_bytes.
+            phys_bytes = float(traffic) if traffic is not None else dom[3]
+            ach = phys_bytes / (dom[1] * 1e-3) / 1e9 if dom[1] > 0 else 0.0
+            survey_ach = dom[2] / (dom[1] * 1e-3) / 1e9 if dom[1] > 0 else 0.0
+            # h0 8 (4 as halves) + phase 4 + work spectrum 16 (8 as halves) + maps: what one step touches
+            working_set = (({"fp32": 28.0, "fp16": 20.0, "fp16h0": 16.0}[args.spectrum]) + texel) * pts
+            residency = "infinity-cache" if working_set < 256 * 2**20 else "hbm"
+
+            roofline = {
+                "bound": "hbm",
+                "kernel": kernel_name,
+                "achieved": ach,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBS,
+                "traffic": traffic,
+                "traffic_source": traffic_source,
+                "frac_basis": ("rocprofv3 PMC bytes per launch (traffic)" if traffic is not None else "bytes moved by design (no committed PMC pass for these kernel sources)"),
+                "residency": residency,
+                "working_set_bytes": working_set,
+                "achieved_on_survey_bytes": survey_ach,
+                "frac_on_survey_bytes": survey_ach / HBM_PEAK_GBS,
+                "frac_hbm_regime_on_bytes_moved": (regime["frac_on_bytes_moved"] if regime else None),
+                "note": ("frac = the dominant (longer) kernel's bytes across the L2's memory side per launch (PMC FETCH_SIZE x 2 + WRITE_SIZE where "
+                         "profiles/ holds a pass of these kernel sources, else the bytes moved by design) / ms_per_launch / 8 TB/s. "
+                         "frac_on_survey_bytes is the same duration on SURVEY.md 8d's ALGORITHMIC bytes (96 B/pt fp32, 68 fp16-stored; this "
+                         "kernel's share in bytes_per_launch); it can pass 1.0 because the kernels move fewer bytes than the algorithm as the "
+                         "reference states it -- two packed transforms instead of three (16 instead of 24 B/pt between the passes) and 24-byte "
+                         "texels (the constant-zero .w channels are not stored). residency says where the working set lives: at 1024^2 x 4 "
+                         "(218 MB) inside the 256 MiB Infinity Cache, so frac is a fabric rate there; frac_hbm_regime_on_bytes_moved is the same "
+                         "two kernels over 16 cascades (1 GB), out of HBM."),
+                "hbm_bytes_by_design": {"rowpass": moved[0], "colpass": moved[1]},
+                "frac_of_peak_on_bytes_moved": {"rowpass": moved[0] / (row_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if row_ms > 0 else None,
+                                                "colpass": moved[1] / (col_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if col_ms > 0 else None,
+                                                "step": (moved[0] + moved[1]) / ((row_ms + col_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS if row_ms + col_ms > 0 else None},
+                # (a step launches either kernel once per cascade group: config.launches_per_pass_and_step; rowpass.ms / colpass.ms below are per STEP)
+                "bytes_per_launch": phys_bytes / launches_per_pass,
+                "survey_bytes_per_launch": dom[2] / launches_per_pass,
+                "ms_per_launch": dom[1] / launches_per_pass,
+                "rowpass": {"ms": row_ms, "bytes": row_b, "GBps": row_b / (row_ms * 1e-3) / 1e9 if row_ms > 0 else 0.0},
+                "colpass": {"ms": col_ms, "bytes": col_b, "GBps": col_b / (col_ms * 1e-3) / 1e9 if col_ms > 0 else 0.0},
+                "step_GBps": step_ach,
+                "step_frac": step_ach / HBM_PEAK_GBS,
+                "launches_timed": nprof,
+                "after_region": after_region,
+                "hbm_regime": regime,
+            }
 
         line = {
             "metric": "ocean grids/sec (N x N displacement step)",
@@ -861,52 +953,15 @@ def main():
                 "payload": args.payload if gathering else None,
                 "payload_bytes_per_rank": pbytes if gathering else None,
                 "parallelism": f"tile-farm x{world}",
+                "full": full,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": kernel_name,
-                "achieved": ach,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": ach / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "frac_basis": ("rocprofv3 PMC bytes per launch (traffic)" if traffic is not None else "bytes moved by design (no committed PMC pass for these kernel sources)"),
-                "residency": residency,
-                "working_set_bytes": working_set,
-                "achieved_on_survey_bytes": survey_ach,
-                "frac_on_survey_bytes": survey_ach / HBM_PEAK_GBS,
-                "frac_hbm_regime_on_bytes_moved": (regime["frac_on_bytes_moved"] if regime else None),
-                "note": ("frac = the dominant (longer) kernel's bytes across the L2's memory side per launch (PMC FETCH_SIZE x 2 + WRITE_SIZE where "
-                         "profiles/ holds a pass of these kernel sources, else the bytes moved by design) / ms_per_launch / 8 TB/s. "
-                         "frac_on_survey_bytes is the same duration on SURVEY.md 8d's ALGORITHMIC bytes (96 B/pt fp32, 68 fp16-stored; this "
-                         "kernel's share in bytes_per_launch); it can pass 1.0 because the kernels move fewer bytes than the algorithm as the "
-                         "reference states it -- two packed transforms instead of three (16 instead of 24 B/pt between the passes) and 24-byte "
-                         "texels (the constant-zero .w channels are not stored). residency says where the working set lives: at 1024^2 x 4 "
-                         "(218 MB) inside the 256 MiB Infinity Cache, so frac is a fabric rate there; frac_hbm_regime_on_bytes_moved is the same "
-                         "two kernels over 16 cascades (1 GB), out of HBM."),
-                "hbm_bytes_by_design": {"rowpass": moved[0], "colpass": moved[1]},
-                "frac_of_peak_on_bytes_moved": {"rowpass": moved[0] / (row_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if row_ms > 0 else None,
-                                                "colpass": moved[1] / (col_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if col_ms > 0 else None,
-                                                "step": (moved[0] + moved[1]) / ((row_ms + col_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS if row_ms + col_ms > 0 else None},
-                # (a step launches either kernel once per cascade group: config.launches_per_pass_and_step; rowpass.ms / colpass.ms below are per STEP)
-                "bytes_per_launch": phys_bytes / launches_per_pass,
-                "survey_bytes_per_launch": dom[2] / launches_per_pass,
-                "ms_per_launch": dom[1] / launches_per_pass,
-                "rowpass": {"ms": row_ms, "bytes": row_b, "GBps": row_b / (row_ms * 1e-3) / 1e9 if row_ms > 0 else 0.0},
-                "colpass": {"ms": col_ms, "bytes": col_b, "GBps": col_b / (col_ms * 1e-3) / 1e9 if col_ms > 0 else 0.0},
-                "step_GBps": step_ach,
-                "step_frac": step_ach / HBM_PEAK_GBS,
-                "launches_timed": nprof,
-                "after_region": after_region,
-                "hbm_regime": regime,
-            },
-            "parity": committed_parity(N),
+            "roofline": roofline,
+            "parity": committed_parity(N) if full else None,
             "compute_ms": compute_ms,
             "gather_ms": gather_ms,
             # N > 1 only.  bus_GBps: what every rank RECEIVES in one all-gather, (world - 1) payloads, over the slowest rank's collective
             # time -- the figure DESIGN.md section 7's prediction assumes to be >= 270 GB/s; per_rank: each rank's own view
-            "farm_diagnostics": (farm_diagnostics(per_rank, world, pbytes if gathering else 0, gather_ms, compute_ms, gathering, args.gather == "pipelined") if multi else None),
+            "farm_diagnostics": (farm_diagnostics(per_rank, world, pbytes if gathering else 0, gather_ms, compute_ms, gathering, args.gather == "pipelined") if (multi and full) else None),
             "gen": gen,
             "reference_frame_n64": frame,
             "value_compute_only": grids / (compute_ms * 1e-3) if (compute_ms > 0 and args.gather != "serial") else None,
@@ -917,7 +972,7 @@ def main():
                                if plain_elapsed > 0 else None),
         }
 
-        if world == 1 and args.cpu_seconds > 0:
+        if full and world == 1 and args.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(N, C, args.cpu_seconds)
         else:
             line["cpu_baseline"] = None

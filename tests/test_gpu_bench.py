@@ -23,7 +23,7 @@ def _env():
     return env
 
 
-COMMON = ["--steps", "6", "--warmup", "2", "--rendezvous", "gloo", "--cpu-seconds", "0", "--no-frame", "--no-regime", "--resolution", "512", "--cascades", "2"]
+COMMON = ["--full", "--steps", "6", "--warmup", "2", "--rendezvous", "gloo", "--cpu-seconds", "0", "--no-frame", "--no-regime", "--resolution", "512", "--cascades", "2"]
 
 
 def test_two_ranks_without_the_gather():
@@ -65,7 +65,7 @@ def test_one_rank_group_with_the_native_gather():
     # communicator, pack + all-gather on the communication stream inside the timed region), then the same steps without the gather
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29641", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, BENCH, "--force-collective", "--steps", "6", "--warmup", "2", "--cpu-seconds", "0", "--no-frame", "--no-regime",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--force-collective", "--steps", "6", "--warmup", "2", "--cpu-seconds", "0", "--no-frame", "--no-regime",
                         "--resolution", "512", "--cascades", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     # stdout is the ONE JSON line and nothing else: RCCL's version banner (C stdio, flushed at exit, i.e. behind the line) goes to stderr
@@ -94,11 +94,11 @@ def test_one_rank_group_with_the_native_gather():
 
 
 def test_the_drivers_command_line():
-    # `python3 bench.py --gpus 1 --steps 20 --warmup 5` (BENCH_r03 ... r05's cmd): one line, the contract's keys, and the roofline's measurement
-    # kept light inside the timed region -- two samples of each kernel there (a sampled step costs the loop ~8 us of its ~1000), every step of a
-    # second pass behind it (roofline.after_region) to say that the two were representative
+    # `python3 bench.py --gpus 1 --steps 20 --warmup 5` (BENCH_r03 ... r05's cmd) with --full: one line, the contract's keys, and the roofline's
+    # measurement kept light inside the timed region -- two samples of each kernel there (a sampled step costs the loop ~8 us of its ~1000), every
+    # step of a second pass behind it (roofline.after_region) to say that the two were representative
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2"], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -119,3 +119,38 @@ def test_the_drivers_command_line():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
     assert j["parity"]["displacement_rmse"]["fused_vs_reduced_table_oracle"] < 1e-5
     assert j["value"] * j["ms_per_step"] * 1e-3 == pytest.approx(4.0, rel=1e-6)      # grids per step over seconds per step
+
+
+def test_a_plain_run_times_the_steps_and_dumps_the_last_ones_maps(tmp_path, oracle):
+    # without --full: the headline only (nothing sampled in the timed region, no leg outside it), and --dump-outputs writes the maps of the
+    # last timed step -- here all of them (2 x 256^2 fits the dump's budget) -- which are the oracle's after warm-up + steps updates
+    import numpy as np
+
+    from datum_amd import farm, host_api
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    N, C, steps, warmup = 256, 2, 7, 3
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--resolution", str(N), "--cascades", str(C),
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert (j["n_gpus"], j["steps"], j["warmup"], j["unit"], j["dtype"], j["higher_is_better"]) == (1, steps, warmup, "grids/s", "f32", True)
+    assert j["value"] * j["ms_per_step"] * 1e-3 == pytest.approx(C, rel=1e-6) and j["config"]["full"] is False
+    for key in ("roofline", "parity", "gen", "reference_frame_n64", "without_gather", "cpu_baseline", "farm_diagnostics"):
+        assert j[key] is None, key
+    assert sorted(os.listdir(tmp_path)) == ["maps.npy"]
+    maps = np.load(tmp_path / "maps.npy")
+    assert maps.dtype == np.float32 and maps.shape == (C, 2, N, N, 4)
+    w = oracle.weights(N, reduced=True)
+    for c in range(C):
+        ws = farm.grid_wavescale(c, C)
+        p = host_api.OceanParams(N, **dict(host_api.EXAMPLE_TUNABLES, wavescale=ws))
+        p.seed_ocean(farm.grid_seed(c))
+        phase = np.zeros((N, N), np.float32)
+        for _ in range(warmup + steps):
+            oracle.update(phase, ws, np.float32(1.0 / 60.0))
+        want = oracle.displace(p.height, phase, ws, 1.35, w=w)
+        err = float(np.sqrt(((maps[c].astype(np.float64) - want) ** 2).mean()))
+        assert err < 1e-5, (c, err)

@@ -3,7 +3,7 @@
 # (hipExtStreamCreateWithCUMask).  profiles/r05_gather_overhead.txt found the stand-in's cost to be its bursts in the in-order memory queues of the
 # CUs it shares with the step's workgroups; here it gets CUs of its own.  20-step batches, 1024^2 x 4, stand-in mode 0 (copy), 300 GB/s, xyz32.
 STEPS=${STEPS:-20}; WARM=${WARM:-5}
-run() { python bench.py --steps $STEPS --warmup $WARM --cpu-seconds 0 --no-frame --no-regime --comm-cus 0 "$@" 2>/dev/null | python3 -c '
+run() { python bench.py --full --steps $STEPS --warmup $WARM --cpu-seconds 0 --no-frame --no-regime --comm-cus 0 "$@" 2>/dev/null | python3 -c '
 import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

@@ -1,4 +1,4 @@
-for rep in 1 2 3 4; do for s in 2 4 8 100; do DATUM_BENCH_STRIDE=$s python bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-frame 2>/dev/null | python3 -c "
+for rep in 1 2 3 4; do for s in 2 4 8 100; do DATUM_BENCH_STRIDE=$s python bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --no-frame 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,7 +10,7 @@ for name, lib in libs:
     env = dict(os.environ)
     if lib:
         env["DATUM_OCEAN_HIP_LIB"] = os.path.abspath(lib)
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "1000", "--warmup", "100", "--cpu-seconds", "0"] + sys.argv[1:], env=env, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "1000", "--warmup", "100", "--cpu-seconds", "0"] + sys.argv[1:], env=env, capture_output=True, text=True, timeout=300)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:
         print(name, "FAILED", out.stderr[-300:]); continue

@@ -2236,6 +2236,11 @@ int datum_ocean_debug_rowpass(datum_ocean_t ctx, int cascade, float *c, float *d
   if (cascade < 0 || cascade >= ctx->cascades)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_debug_rowpass: cascade out of range");
 
+  // (as datum_ocean_displace: without a state the row pass would read h0 and phase the caller never wrote -- in FP16_H0 a spurious
+  // "NaN or an infinity" from size_spectrum_scale)
+  if (!ctx->uploaded[cascade])
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_debug_rowpass: the cascade has no state (datum_ocean_upload_state)");
+
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   int rc = ensure_scratch(ctx);

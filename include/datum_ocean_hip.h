@@ -121,14 +121,15 @@ int datum_ocean_set_cascade(datum_ocean_t ctx, int cascade, float wavescale, flo
  * (ocean.cpp:749) or NULL for all-zero (seed_ocean, ocean.cpp:144).  Host pointers. */
 /* Extension (BASELINE.json configs[4]): how the work spectrum between the two passes is stored.  FP32 (default): 16 B
  * per point.  FP16: 8 B per point, arithmetic stays fp32; the values are scaled by a power of two sized from max |h0|
- * so that no row sum can overflow a half.  Displacement error then ~5e-4 relative to the largest displacement
- * (tests state 2e-3).  Takes effect at the next datum_ocean_displace.
+ * so that no row sum can overflow a half.  Displacement RMSE then 5e-5 .. 1.1e-4 of the largest displacement with the
+ * example's parameters (tests state 4e-4; each stored half is the rounding of the fp32 row-pass value, and the column pass that
+ * reads them is at fp32 precision: tests/test_gpu_pointwise.py).  Takes effect at the next datum_ocean_displace.
  * FP16_H0 (round 6; SURVEY.md 8d's own byte count for that config -- "spectrum + intermediates stored fp16": h0 4 B/pt): FP16, and the
  * row pass reads h0 as two halves per point as well, from a copy the module keeps beside the fp32 h0 (4 more bytes per point of
  * device memory; rebuilt on the device whenever h0 changes: upload, rebuild from the seed, resume): h0 times the power of two that
  * brings its largest component just under 2^15, rounded to nearest even.  What the caller uploads and fetches stays fp32; the phase
- * state never passes through a half and stays bit-exact.  Same stated tolerance (2e-3 of the largest displacement; measured with
- * the example's parameters: tests/test_gpu_parity.py). */
+ * state never passes through a half and stays bit-exact.  Same stated tolerance (4e-4 of the largest displacement; measured with
+ * the example's parameters: tests/test_gpu_parity.py, tests/test_gpu_pointwise.py). */
 #define DATUM_OCEAN_SPECTRUM_FP32 0
 #define DATUM_OCEAN_SPECTRUM_FP16 1
 #define DATUM_OCEAN_SPECTRUM_FP16_H0 2
@@ -360,7 +361,9 @@ int datum_ocean_debug_sim(datum_ocean_t ctx, int cascade, float *h, float *hx, f
  * (twice the Hermitian part; the halving is folded into the column pass),
  *   c = rows of ocean.fftx applied to  C = h_S + i hx_S
  *   d = rows of ocean.fftx applied to  D = hy_S + 2 sin(2 pi x / N) h_S
- * where h, hx, hy are ocean.sim's outputs (datum_ocean_debug_sim). */
+ * where h, hx, hy are ocean.sim's outputs (datum_ocean_debug_sim).  The call re-runs the row pass of this one cascade from its current
+ * state (no pending update is applied) into work-spectrum slot 0; with the fp16 formats the values are the stored halves times 2^-e
+ * (exact in fp32).  A cascade without a state (datum_ocean_upload_state) is refused with DATUM_OCEAN_ESTATE, as by datum_ocean_displace. */
 int datum_ocean_debug_rowpass(datum_ocean_t ctx, int cascade, float *c, float *d);
 
 /* hipEvent timing of the two kernels of datum_ocean_displace on the handle's stream.

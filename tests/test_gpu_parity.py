@@ -22,6 +22,10 @@ pytestmark = pytest.mark.gpu
 
 DT = np.float32(1.0 / 60.0)
 
+# fp16 work spectrum (DATUM_OCEAN_SPECTRUM_FP16[_H0]): displacement RMSE over the largest |displacement|; measured 5.3e-5 .. 1.32e-4
+# (the worst: test_random_parameters), 3x that (the stated tolerance was 2e-3 up to round 6)
+FP16_RMSE = 4e-4
+
 
 @pytest.fixture(scope="module")
 def capi():
@@ -175,6 +179,8 @@ def packed_fields(fields):
 @pytest.mark.parametrize("N", [64, 128, 256, 512, 1024, 2048])
 def test_rowpass_stage(capi, oracle, N):
     # state after the row pass: ocean.fftx applied to the two packed fields built from ocean.sim's three
+    # (the 4096^2 row pass -- the sequential 16-points-per-thread form -- is compared element by element with a float64 row pass, in all
+    # three spectrum formats, by tests/test_gpu_pointwise.py)
     p = oracle.EXAMPLE
     h0 = make_state(oracle, N, 1002)
     phase = np.zeros((N, N), np.float32)
@@ -851,7 +857,8 @@ def test_fp16_spectrum_against_oracle(capi, oracle, report, N, fmt):
     # BASELINE.json configs[4]: work spectrum stored as IEEE halves (8 B/pt between the passes), arithmetic fp32.
     # Tolerance re-stated for fp16: each stored value carries a relative error <= 2^-11 (round to nearest; the scale is
     # sized so that nothing overflows), and a displacement is a sum of N of them with random signs, so the error is
-    # ~ 2^-11 of the rms displacement: RMSE < 2e-3 of the largest |displacement|, unit normals within 1e-2.
+    # ~ 2^-11 of the rms displacement: RMSE < FP16_RMSE of the largest |displacement|, unit normals within 3.5e-3.
+    # (The stored halves themselves and the column pass that reads them are pinned pointwise by tests/test_gpu_pointwise.py.)
     # The phase state does not pass through the spectrum: still bit-exact.
     p = oracle.EXAMPLE
     h0 = make_state(oracle, N, 1000)
@@ -876,15 +883,16 @@ def test_fp16_spectrum_against_oracle(capi, oracle, report, N, fmt):
     scale = float(np.abs(ref[0][..., :3]).max())
     assert rmse(exact[0][..., :3], ref[0][..., :3]) < 1e-5
     e = rmse(got[0][..., :3], ref[0][..., :3])
-    report(f"fp16-stored spectrum ({fmt}) N={N}: disp rmse vs oracle {e:.3e} (= {e / scale:.2e} of largest |disp|; bar 2e-3)")
-    assert 1e-7 * scale < e < 2e-3 * scale        # really went through halves, and within the stated tolerance
-    assert np.abs(got[1][..., :3] - ref[1][..., :3]).max() < 1e-2
+    report(f"fp16-stored spectrum ({fmt}) N={N}: disp rmse vs oracle {e:.3e} (= {e / scale:.2e} of largest |disp|; bar {FP16_RMSE:g}); "
+           f"normal max abs err {float(np.abs(got[1][..., :3] - ref[1][..., :3]).max()):.3e}")
+    assert 1e-7 * scale < e < FP16_RMSE * scale        # really went through halves, and within the stated tolerance
+    assert np.abs(got[1][..., :3] - ref[1][..., :3]).max() < 3.5e-3                # measured 1.15e-3 (1024^2 fp16h0; was 1e-2)
     assert np.all(got[..., 3] == 0)
 
 
 def test_fp16_spectrum_4096(capi, oracle, report):
-    # the stress size of configs[4], against the oracle: same stated tolerance as at 256^2 / 1024^2 (RMSE < 2e-3 of the
-    # largest |displacement|, unit normals within 2e-2 at this size: a normal is a ratio of sums of 4096 rounded values);
+    # the stress size of configs[4], against the oracle: same stated tolerance as at 256^2 / 1024^2 (RMSE < FP16_RMSE of the
+    # largest |displacement|, unit normals within 1.6e-2 at this size: a normal is a ratio of sums of 4096 rounded values);
     # the fp32 path on the same state within 1e-5; phase bit-exact; no overflow / NaN; w components zero
     N = 4096
     p = oracle.EXAMPLE
@@ -913,12 +921,12 @@ def test_fp16_spectrum_4096(capi, oracle, report):
     e16h = rmse(goth[0][..., :3], ref[0][..., :3])
     n16 = float(np.abs(got[1][..., :3] - ref[1][..., :3]).max())
     n16h = float(np.abs(goth[1][..., :3] - ref[1][..., :3]).max())
-    report(f"fp16-stored spectrum N=4096: disp rmse vs oracle fp16 {e16:.3e} (= {e16 / scale:.2e} of largest |disp| {scale:.3e}; bar 2e-3), "
+    report(f"fp16-stored spectrum N=4096: disp rmse vs oracle fp16 {e16:.3e} (= {e16 / scale:.2e} of largest |disp| {scale:.3e}; bar {FP16_RMSE:g}), "
            f"fp16 with h0 as halves {e16h:.3e} (= {e16h / scale:.2e}), fp32 {e32:.3e}; normal max abs err fp16 {n16:.3e}, with h0 as halves {n16h:.3e}")
     assert e32 < 1e-5
-    assert 1e-7 * scale < e16 < 2e-3 * scale
-    assert 1e-7 * scale < e16h < 2e-3 * scale
-    assert n16 < 2e-2 and n16h < 2e-2
+    assert 1e-7 * scale < e16 < FP16_RMSE * scale
+    assert 1e-7 * scale < e16h < FP16_RMSE * scale
+    assert n16 < 1.6e-2 and n16h < 1.6e-2              # measured 5.12e-3 (was 2e-2)
     assert not np.array_equal(got, goth)               # the second format really read other bits
     assert np.all(got[..., 3] == 0) and np.all(goth[..., 3] == 0)
 
@@ -1051,14 +1059,14 @@ def test_flat_ocean(capi, N):
 
 @pytest.mark.parametrize("half", [False, True, "fp16h0"])
 @pytest.mark.parametrize("case", range(6))
-def test_random_parameters(capi, oracle, case, half):
+def test_random_parameters(capi, oracle, report, case, half):
     # three cascades with random wave scales (1 .. 2000), wave amplitudes over four decades, choppiness (0 .. 2), and random
     # runs of 1 .. 12 updates between displacements (more than 8 pending goes through the phase-only kernel first), some dt
     # negative or large (the general fmod path): phase bit-exact, maps within 2e-6 of the largest |value| of the oracle's (the
     # 1e-5 absolute bar belongs to the example parameters; amplitudes here span decades).
     # half: the same through the fp16-stored spectrum (set_spectrum_format), whose power-of-two scale has to follow max |h0|
-    # of each cascade: displacement RMSE < 2e-3 of the largest |displacement| (the stated fp16 tolerance), unit normals
-    # within 2e-2, and the phase -- which never passes through the spectrum -- still bit-exact.
+    # of each cascade: displacement RMSE < FP16_RMSE of the largest |displacement| (the stated fp16 tolerance), unit normals
+    # within 7e-3, and the phase -- which never passes through the spectrum -- still bit-exact.
     rng = np.random.default_rng(100 + case)
     N = [128, 256, 64, 512, 128, 256][case]
     C = 3
@@ -1088,9 +1096,12 @@ def test_random_parameters(capi, oracle, case, half):
                 big = max(float(np.abs(ref[0]).max()), 1e-30)
                 if half:
                     e = rmse(got[0][..., :3], ref[0][..., :3])
-                    assert 1e-8 * big < e < 2e-3 * big, (c, e / big)      # really through halves, and within the stated tolerance
-                    assert np.abs(got[0][..., :3] - ref[0][..., :3]).max() < 2e-2 * big
-                    assert np.abs(got[1][..., :3] - ref[1][..., :3]).max() < 2e-2
+                    report(f"fp16-stored spectrum ({half}) random parameters case {case} N={N} round {rnd} cascade {c}: disp rmse {e / big:.2e} of largest |disp| "
+                           f"(bar FP16_RMSE {FP16_RMSE:g}), disp max abs {float(np.abs(got[0][..., :3] - ref[0][..., :3]).max()) / big:.2e} of it, "
+                           f"normal max abs {float(np.abs(got[1][..., :3] - ref[1][..., :3]).max()):.2e}")
+                    assert 1e-8 * big < e < FP16_RMSE * big, (c, e / big)      # really through halves, and within the stated tolerance
+                    assert np.abs(got[0][..., :3] - ref[0][..., :3]).max() < 2e-3 * big    # measured 6.4e-4 (was 2e-2)
+                    assert np.abs(got[1][..., :3] - ref[1][..., :3]).max() < 7e-3          # measured 2.30e-3 (was 2e-2)
                 else:
                     tol = 2e-6 * big
                     assert np.abs(got[0][..., :3] - ref[0][..., :3]).max() < 10 * tol
@@ -1148,9 +1159,10 @@ def test_fp16_spectrum_2048(capi, oracle, report):
     scale = float(np.abs(ref[0][..., :3]).max())
     for what, g in (("", got), (" with h0 as halves", goth)):
         e = rmse(g[0][..., :3], ref[0][..., :3])
-        report(f"fp16-stored spectrum{what} N=2048: disp rmse vs oracle {e:.3e} (= {e / scale:.2e} of largest |disp|; bar 2e-3)")
-        assert 1e-7 * scale < e < 2e-3 * scale
-        assert np.abs(g[1][..., :3] - ref[1][..., :3]).max() < 2e-2
+        report(f"fp16-stored spectrum{what} N=2048: disp rmse vs oracle {e:.3e} (= {e / scale:.2e} of largest |disp|; bar {FP16_RMSE:g}); "
+               f"normal max abs err {float(np.abs(g[1][..., :3] - ref[1][..., :3]).max()):.3e}")
+        assert 1e-7 * scale < e < FP16_RMSE * scale
+        assert np.abs(g[1][..., :3] - ref[1][..., :3]).max() < 7.5e-3              # measured 2.35e-3 (was 2e-2)
         assert np.all(g[..., 3] == 0)
 
 
@@ -1442,7 +1454,7 @@ def test_map_store_policies_do_not_change_the_result(capi, oracle, torch, N, C, 
 
 
 @pytest.mark.parametrize("N,C,half", [(256, 5, False), (1024, 12, False), (1024, 6, True), (2048, 3, False)])
-def test_cascade_groups_do_not_change_the_result(capi, oracle, N, C, half):
+def test_cascade_groups_do_not_change_the_result(capi, oracle, report, N, C, half):
     # datum_ocean_displace launches the two passes per GROUP of cascades (row(g), column(g), row(g + 1), ...: the exchange spectrum of a
     # group stays in the Infinity Cache; replaces the one dispatch per shader of ocean.cpp:769-789).  Whatever the group -- the module's own
     # choice, one cascade per launch, ragged last groups, every cascade at once (the form up to ABI 6) -- phase and maps are the same
@@ -1501,7 +1513,9 @@ def test_cascade_groups_do_not_change_the_result(capi, oracle, N, C, half):
     if N <= 1024:
         ref = oracle.displace(states[c % len(states)], ph, oracle.CASCADE_WAVESCALES[c % 4], p["choppiness"] + 0.05 * c, w=oracle.weights(N, reduced=True))
         err = rmse(maps0[c][..., :3], ref[..., :3])
-        assert err < (2e-3 * float(np.abs(ref[..., :3]).max()) if half else 1e-5), err
+        if half:
+            report(f"fp16-stored spectrum, {C} cascades of {N}^2 in groups: rmse of both layers {err / float(np.abs(ref[..., :3]).max()):.2e} of the largest |value|")
+        assert err < (FP16_RMSE * float(np.abs(ref[..., :3]).max()) if half else 1e-5), err
 
     with capi.Ocean(64, 1) as oc:
         with pytest.raises(capi.OceanError) as e:

@@ -21,6 +21,24 @@
 
 using namespace ocean;
 
+// One kernel of the step as the module launches it: entry point, workgroup, dynamic LDS and work items per cascade (workgroups of row pairs
+// for the row pass, tiles for the column pass)
+struct PassKernel
+{
+  void const *kernel = nullptr;
+  int threads = 0;
+  size_t lds = 0;
+  int items = 0;
+  bool walks = false;                 // persistent workgroups, at most one per compute unit, walk their share of the items (col_walks)
+};
+
+// every kernel a step can launch at the handle's resolution (step_kernels), filled and configured once by datum_ocean_create
+struct StepKernels
+{
+  PassKernel row[3][2];               // [DATUM_OCEAN_SPECTRUM_*][a phase outside [0, 2 pi)]
+  PassKernel col[2][2];               // [fp16 work spectrum][maps streamed]; the written-through kernel twice where there is no streamed form
+};
+
 struct datum_ocean_ctx
 {
   int device = 0;
@@ -28,6 +46,7 @@ struct datum_ocean_ctx
   int cascades = 0;
 
   int cus = 0;                        // compute units of the device
+  StepKernels kernels;
 
   hipStream_t stream = nullptr;       // the one in use
   hipStream_t ownstream = nullptr;
@@ -39,7 +58,7 @@ struct datum_ocean_ctx
   bool half = false;                  // DATUM_OCEAN_SPECTRUM_FP16 or _FP16_H0
   bool h0half = false;                // DATUM_OCEAN_SPECTRUM_FP16_H0: the row pass reads h0 as halves ...
   unsigned int *h0h = nullptr;        // ... from this copy, [cascades][P] x two halves, rebuilt with the scale when h0 changes (size_spectrum_scale)
-  int cascadegroup = 0;               // cascades per launch of the two passes, 0 = sized to the Infinity Cache (cascade_group)
+  int cascadegroup = 0;               // cascades per launch of the two passes, 0 = sized to the Infinity Cache (plan_step)
   int mappolicy = DATUM_OCEAN_MAPS_AUTO;   // datum_ocean_set_map_store_policy
 
   // validation mode (datum_ocean_set_literal_transform): the reference's own radix-2 transforms with its literal twiddle table
@@ -76,6 +95,7 @@ struct datum_ocean_ctx
   int profmax = 0;
   int profsteps = 0;
   int profstride = 1;
+  int profgroups = 0;                 // launches per pass when the profile began: the layout of events
   long profcalls = 0;
   std::vector<hipEvent_t> events;     // 4 per sampled step
 
@@ -131,6 +151,19 @@ namespace
     return a;
   }
 
+  // The maps streamed past the Infinity Cache instead of written through (ocean_kernels.hip: MAP_STORE_AUX_STREAM; 1024^2 and 2048^2 have both
+  // forms) where the handle's working set -- h0 8 + phase 4 + work spectrum 16 (8: fp16) + maps 24 bytes per point and cascade -- is beyond
+  // this.  The working set up to which writing the maps through wins: 1024^2 x 4 (218 MB) 82.4 k grids/s written through against 78.9 k
+  // streamed, x 5 (272 MB) 72.4-74.0 against 72.1-72.5 k, x 6 (327 MB) 68.8 against 76.1 k; 2048^2 x 1 and the fp16 spectrum's x 4 / x 6
+  // (185 / 277 MB) written through by 0-3 % (profiles/r06_store_policies.txt).  4096^2 always streams (one cascade is 0.9 GB); grids below
+  // 1024^2 never do (sixteen cascades of 512^2 still fit).
+  constexpr double MAPS_RESIDENT_BYTES = 300.0e6;
+
+  bool maps_stream(int N, int cascades, bool half)
+  {
+    return N >= 4096 || (N >= 1024 && (double)cascades * N * N * (half ? 44.0 : 52.0) > MAPS_RESIDENT_BYTES);
+  }
+
   // Cascades per launch of the two passes (replaces the one dispatch per shader of ocean.cpp:769-789).  A handle whose working set is resident
   // in the Infinity Cache takes every cascade in one launch per pass.  Beyond it the maps are streamed (ocean_kernels.hip: MAP_STORE_AUX) and
   // what can stay in the cache from the row pass to the column pass -- and for h0 and the phase from step to step -- is h0 8 + phase 4 + work
@@ -141,137 +174,115 @@ namespace
   // against 78.3 k as 2 x 4; 2048^2 x 4 as 2 x 2 18.2 k against 16.0 k in one launch and 17.2 k as 4 x 1.
   constexpr double CASCADE_GROUP_BYTES = 240.0e6;
 
-  // The maps streamed past the Infinity Cache instead of written through (ocean_kernels.hip: MAP_STORE_AUX_STREAM; 1024^2 and 2048^2 have both forms):
-  // where the handle's own working set is beyond the cache, and -- round 6, profiles/r06_farm_standin.txt -- while a farm of several ranks is
-  // initialised: the collective's gathered buffer competes for the same cache, and the step loses less under it with the maps out of the way.
-  bool handle_streams_maps(datum_ocean_ctx const *ctx);
-
-  int cascade_group(datum_ocean_ctx const *ctx)
+  // The kernels of a displace call and how many launches of them: the one place where the spectrum format, a phase outside [0, 2 pi), the map
+  // store policy, the farm and the requested group are combined.  displace, debug_rowpass, the profile and the two getters all read this.
+  struct StepPlan
   {
+    PassKernel const *row = nullptr;
+    PassKernel const *col = nullptr;
+    int group = 0;                    // cascades per launch of either pass
+    int groups = 0;                   // launches per pass
+    bool streamed = false;            // the maps streamed past the Infinity Cache
+  };
+
+  StepPlan plan_step(datum_ocean_ctx const *ctx)
+  {
+    int const N = ctx->N, C = ctx->cascades;
+    bool const beyond = maps_stream(N, C, ctx->half);
+
+    StepPlan p;
+
+    // streamed where the handle's own working set is beyond the cache, and -- round 6, profiles/r06_farm_standin.txt -- while a farm of several
+    // ranks is initialised: the collective's gathered buffer competes for the same cache, and the step loses less under it with the maps out
+    // of the way.  4096^2 has the streamed form only, the grids below 1024^2 the written-through one only.
+    if (N >= 4096 || N < 1024)
+      p.streamed = N >= 4096;
+    else if (ctx->mappolicy != DATUM_OCEAN_MAPS_AUTO)
+      p.streamed = ctx->mappolicy == DATUM_OCEAN_MAPS_STREAMED;
+    else
+      p.streamed = beyond || (ctx->farm && ctx->farm->world > 1);
+
+    // in groups only where the maps are streamed BECAUSE the working set is beyond the cache
     int g = ctx->cascadegroup;
 
     if (g > 0)
-      return g > ctx->cascades ? ctx->cascades : g;
-
-    if (!handle_streams_maps(ctx) || !maps_stream(ctx->N, ctx->cascades, ctx->half))
-      return ctx->cascades;
-
-    g = (int)(CASCADE_GROUP_BYTES / ((double)plane(ctx) * ((ctx->h0half ? 8.0 : 12.0) + (ctx->half ? 8.0 : 16.0))));
-    g = g < 1 ? 1 : (g > ctx->cascades ? ctx->cascades : g);
-
-    int const groups = (ctx->cascades + g - 1) / g;
-
-    return (ctx->cascades + groups - 1) / groups;
-  }
-
-  template<int N, bool H16>
-  hipError_t configure_one(char const **what)
-  {
-    *what = "hipFuncSetAttribute(ocean_rowpass_kernel, MaxDynamicSharedMemorySize)";
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<void const*>(&ocean_rowpass_kernel<N, H16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RowCfg<N, H16>::LDS);
-    if (e != hipSuccess)
-      return e;
-
-    if constexpr (H16)
+      g = std::min(g, C);
+    else if (!p.streamed || !beyond)
+      g = C;
+    else
     {
-      *what = "hipFuncSetAttribute(ocean_rowpass_kernel, the instantiations with h0 as halves, MaxDynamicSharedMemorySize)";
-      e = hipFuncSetAttribute(reinterpret_cast<void const*>(&ocean_rowpass_kernel<N, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RowCfg<N, true>::LDS);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<void const*>(&ocean_rowpass_kernel<N, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RowCfg<N, true>::LDS);
-      if (e != hipSuccess)
-        return e;
+      g = (int)(CASCADE_GROUP_BYTES / ((double)plane(ctx) * ((ctx->h0half ? 8.0 : 12.0) + (ctx->half ? 8.0 : 16.0))));
+      g = std::max(1, std::min(g, C));
+
+      int const groups = (C + g - 1) / g;
+
+      g = (C + groups - 1) / groups;
     }
 
-    *what = "hipFuncSetAttribute(ocean_rowpass_kernel, the instantiation for phases outside [0, 2 pi), MaxDynamicSharedMemorySize)";
-    e = hipFuncSetAttribute(reinterpret_cast<void const*>(&ocean_rowpass_kernel<N, H16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RowCfg<N, H16>::LDS);
-    if (e != hipSuccess)
-      return e;
+    p.group = g;
+    p.groups = (C + g - 1) / g;
 
-    *what = "hipFuncSetAttribute(ocean_colpass_kernel, MaxDynamicSharedMemorySize)";
-    e = hipFuncSetAttribute(colpass_entry<N, H16>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ColCfg<N>::LDS);
-    if (e != hipSuccess)
-      return e;
-
-    if constexpr (col_has_stream_variant<N>())
-      e = hipFuncSetAttribute(colpass_entry<N, H16, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ColCfg<N>::LDS);
-
-    return e;
-  }
-
-  template<int N>
-  hipError_t configure(datum_ocean_ctx *ctx, char const **what)
-  {
-    (void)ctx;
-
-    hipError_t e = configure_one<N, false>(what);
-
-    if (e == hipSuccess)
-      e = configure_one<N, true>(what);
-
-    return e;
-  }
-
-  // ev != nullptr: the dispatch itself carries a start and a stop event (hipExtLaunchKernel), so a sampled kernel is
-  // timed from its first to its last workgroup without event packets between the kernels -- an hipEventRecord between
-  // the two passes held the second one back until the first had drained (+4 us per kernel at 1024^2 x 4).
-  hipError_t launch(void const *kernel, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t stream, hipEvent_t *ev)
-  {
-    if (ev)
-      return hipExtLaunchKernel(kernel, grid, block, args, lds, stream, ev[0], ev[1], 0);
-
-    return hipLaunchKernel(kernel, grid, block, args, lds, stream);
-  }
-
-  template<int N, bool H16, bool H0H = false>
-  hipError_t launch_rowpass_as(datum_ocean_ctx *ctx, StepArgs &a, hipEvent_t *ev)
-  {
-    typedef RowCfg<N, H16> C;
-
-    // a phase outside [0, 2 pi) in some cascade (uploaded so, or left there by a negative dt): the instantiation whose sin / cos
+    // a phase outside [0, 2 pi) in some cascade (uploaded so, or left there by a negative dt): for the whole call the row pass whose sin / cos
     // take any argument
     bool wild = false;
 
-    for(int c = 0; c < ctx->cascades; ++c)
+    for(int c = 0; c < C; ++c)
       wild = wild || ctx->wildphase[c];
 
-    void *args[] = { &a };
-    void const *kernel = wild ? reinterpret_cast<void const*>(&ocean_rowpass_kernel<N, H16, true, H0H>) : reinterpret_cast<void const*>(&ocean_rowpass_kernel<N, H16, false, H0H>);
+    int const format = ctx->h0half ? DATUM_OCEAN_SPECTRUM_FP16_H0 : (ctx->half ? DATUM_OCEAN_SPECTRUM_FP16 : DATUM_OCEAN_SPECTRUM_FP32);
 
-    // work items = groups of row pairs x the cascades of this launch: one workgroup each
-    int const items = C::GROUPS * a.cascades;
+    p.row = &ctx->kernels.row[format][wild];
+    p.col = &ctx->kernels.col[ctx->half][p.streamed];
 
-    return launch(kernel, dim3(items), dim3(C::THREADS), args, C::LDS, ctx->stream, ev);
+    return p;
   }
 
+  // every kernel a step can launch at resolution N: the one place that names their instantiations (datum_ocean_create configures each)
   template<int N>
-  hipError_t launch_rowpass(datum_ocean_ctx *ctx, StepArgs &a, hipEvent_t *ev)
+  StepKernels step_kernels()
   {
-    if (ctx->h0half)
-      return launch_rowpass_as<N, true, true>(ctx, a, ev);
+    typedef RowCfg<N, false> R;
+    typedef RowCfg<N, true> RH;
+    typedef ColCfg<N> C;
 
-    return ctx->half ? launch_rowpass_as<N, true>(ctx, a, ev) : launch_rowpass_as<N, false>(ctx, a, ev);
-  }
+    auto k = [](auto *kernel) { return reinterpret_cast<void const*>(kernel); };
 
-  template<int N>
-  hipError_t launch_colpass(datum_ocean_ctx *ctx, StepArgs &a, hipEvent_t *ev)
-  {
-    void *args[] = { &a };
-    void const *kernel = ctx->half ? colpass_entry<N, true>() : colpass_entry<N, false>();
+    StepKernels t;
 
-    // the maps streamed instead of written through where the HANDLE's working set is beyond the Infinity Cache (whatever this launch's share of it)
+    t.row[DATUM_OCEAN_SPECTRUM_FP32][0] = { k(&ocean_rowpass_kernel<N, false>), R::THREADS, R::LDS, R::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP32][1] = { k(&ocean_rowpass_kernel<N, false, true>), R::THREADS, R::LDS, R::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16][0] = { k(&ocean_rowpass_kernel<N, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16][1] = { k(&ocean_rowpass_kernel<N, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][0] = { k(&ocean_rowpass_kernel<N, true, false, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][1] = { k(&ocean_rowpass_kernel<N, true, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+
+    t.col[0][0] = t.col[0][1] = { colpass_entry<N, false>(), C::THREADS, C::LDS, C::TILES, col_walks<N, false>() };
+    t.col[1][0] = t.col[1][1] = { colpass_entry<N, true>(), C::THREADS, C::LDS, C::TILES, col_walks<N, true>() };
+
     if constexpr (col_has_stream_variant<N>())
     {
-      if (handle_streams_maps(ctx))
-        kernel = ctx->half ? colpass_entry<N, true, true>() : colpass_entry<N, false, true>();
+      t.col[0][1].kernel = colpass_entry<N, false, true>();
+      t.col[1][1].kernel = colpass_entry<N, true, true>();
     }
 
-    // work items = tiles x cascades; the large grids' workgroups are persistent, one per compute unit (the LDS of a
-    // 1024-thread tile fills a CU), and walk their share of the items
-    int const items = ColCfg<N>::TILES * a.cascades;
-    bool const walks = ctx->half ? col_walks<N, true>() : col_walks<N, false>();
-    int const groups = walks ? std::min(items, ctx->cus) : items;
+    return t;
+  }
 
-    return launch(kernel, dim3(groups), dim3(ColCfg<N>::THREADS), args, ColCfg<N>::LDS, ctx->stream, ev);
+  // One launch of a pass over the cascades [a.first, a.first + a.cascades): the kernel's work items per cascade times the cascades, one
+  // workgroup each -- or, where its workgroups walk (the LDS of a 1024-thread tile fills a CU), one persistent workgroup per compute unit.
+  // ev != nullptr: the dispatch itself carries a start and a stop event (hipExtLaunchKernel), so a sampled kernel is
+  // timed from its first to its last workgroup without event packets between the kernels -- an hipEventRecord between
+  // the two passes held the second one back until the first had drained (+4 us per kernel at 1024^2 x 4).
+  hipError_t launch(datum_ocean_ctx const *ctx, PassKernel const &k, StepArgs &a, hipEvent_t *ev)
+  {
+    void *args[] = { &a };
+    int const items = k.items * a.cascades;
+    dim3 const grid(k.walks ? std::min(items, ctx->cus) : items);
+
+    if (ev)
+      return hipExtLaunchKernel(k.kernel, grid, dim3(k.threads), args, k.lds, ctx->stream, ev[0], ev[1], 0);
+
+    return hipLaunchKernel(k.kernel, grid, dim3(k.threads), args, k.lds, ctx->stream);
   }
 
   #define DISPATCH_N(n, expr) \
@@ -644,17 +655,16 @@ int datum_ocean_create(datum_ocean_t *out, int device, int resolution, int casca
     ctx->casc[c].rowscale = 1.0f;
   }
 
-  {
-    hipError_t ce = hipSuccess;
-    char const *what = "";
-    DISPATCH_N(resolution, ce = configure<NN>(ctx, &what));
-    if (ce != hipSuccess)
-    {
-      int rc = fail(nullptr, (int)ce, what);
-      datum_ocean_destroy(ctx);
-      return rc;
-    }
-  }
+  // the LDS limit of every kernel in the table: a kernel the module launches is one it configured
+  DISPATCH_N(resolution, ctx->kernels = step_kernels<NN>());
+
+  for(auto const &format : ctx->kernels.row)
+    for(PassKernel const &k : format)
+      CREATECHECK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
+
+  for(auto const &half : ctx->kernels.col)
+    for(PassKernel const &k : half)
+      CREATECHECK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
 
   CREATECHECK(hipStreamSynchronize(ctx->stream));
 
@@ -810,6 +820,9 @@ int datum_ocean_set_spectrum_format(datum_ocean_t ctx, int format)
 
   if (format != DATUM_OCEAN_SPECTRUM_FP32 && format != DATUM_OCEAN_SPECTRUM_FP16 && format != DATUM_OCEAN_SPECTRUM_FP16_H0)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_spectrum_format: unknown format");
+
+  if (ctx->profiling)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_spectrum_format: a profile is open (the format can change the cascade groups its samples are per)");
 
   if (format != DATUM_OCEAN_SPECTRUM_FP32 && ctx->literal)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_spectrum_format: the handle is in the literal mode (the reference's fp32 arithmetic); switch it off first");
@@ -1114,32 +1127,31 @@ int datum_ocean_displace(datum_ocean_t ctx)
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
+  StepPlan const plan = plan_step(ctx);
+
+  bool const sampling = ctx->profiling && ctx->profsteps < ctx->profmax;
+  bool const prof = sampling && ctx->profcalls % ctx->profstride == 0;
+
+  // (refused before anything is consumed: the queued updates stay for the next call)
+  if (prof && plan.groups != ctx->profgroups)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_displace: the cascade groups changed while profiling (its samples are per group)");
+
   StepArgs a = make_args(ctx, (int)ctx->pending.size(), ctx->pending.data());
   ctx->pending.clear();
 
-  bool const prof = ctx->profiling && ctx->profsteps < ctx->profmax && (ctx->profcalls++ % ctx->profstride) == 0;
+  if (sampling)
+    ctx->profcalls += 1;
 
-  // the two passes group by group (cascade_group): row(g), column(g), row(g + 1), ...
-  int const group = cascade_group(ctx);
-  int const groups = (ctx->cascades + group - 1) / group;
-
-  if (prof && ctx->events.size() < (size_t)4 * ctx->profmax * groups)
-    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_displace: the cascade group changed while profiling");
-
-  for(int g = 0; g < groups; ++g)
+  // the two passes group by group: row(g), column(g), row(g + 1), ...
+  for(int g = 0; g < plan.groups; ++g)
   {
-    a.first = g * group;
-    a.cascades = std::min(group, ctx->cascades - a.first);
+    a.first = g * plan.group;
+    a.cascades = std::min(plan.group, ctx->cascades - a.first);
 
-    hipEvent_t *ev = prof ? &ctx->events[4 * ((size_t)ctx->profsteps * groups + g)] : nullptr;   // row start, row stop, column start, column stop
+    hipEvent_t *ev = prof ? &ctx->events[4 * ((size_t)ctx->profsteps * plan.groups + g)] : nullptr;   // row start, row stop, column start, column stop
 
-    hipError_t le = hipSuccess;
-
-    DISPATCH_N(ctx->N, le = launch_rowpass<NN>(ctx, a, ev));
-    HIPCHECK(ctx, le);
-
-    DISPATCH_N(ctx->N, le = launch_colpass<NN>(ctx, a, ev ? ev + 2 : nullptr));
-    HIPCHECK(ctx, le);
+    HIPCHECK(ctx, launch(ctx, *plan.row, a, ev));
+    HIPCHECK(ctx, launch(ctx, *plan.col, a, ev ? ev + 2 : nullptr));
   }
 
   if (prof)
@@ -1815,29 +1827,12 @@ int datum_ocean_cascade_group(datum_ocean_t ctx, int *cascades_per_launch, int *
   if (!ctx)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_cascade_group: null handle");
 
-  int const group = cascade_group(ctx);
+  StepPlan const plan = plan_step(ctx);
 
-  if (cascades_per_launch) *cascades_per_launch = group;
-  if (launches_per_pass) *launches_per_pass = (ctx->cascades + group - 1) / group;
+  if (cascades_per_launch) *cascades_per_launch = plan.group;
+  if (launches_per_pass) *launches_per_pass = plan.groups;
 
   return DATUM_OCEAN_OK;
-}
-
-namespace
-{
-  bool handle_streams_maps(datum_ocean_ctx const *ctx)
-  {
-    if (ctx->N >= 4096)
-      return true;
-
-    if (ctx->N < 1024)
-      return false;
-
-    if (ctx->mappolicy != DATUM_OCEAN_MAPS_AUTO)
-      return ctx->mappolicy == DATUM_OCEAN_MAPS_STREAMED;
-
-    return maps_stream(ctx->N, ctx->cascades, ctx->half) || (ctx->farm && ctx->farm->world > 1);
-  }
 }
 
 int datum_ocean_set_map_store_policy(datum_ocean_t ctx, int policy)
@@ -1862,7 +1857,7 @@ int datum_ocean_map_store_policy(datum_ocean_t ctx, int *policy, int *streamed)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_map_store_policy: null handle");
 
   if (policy) *policy = ctx->mappolicy;
-  if (streamed) *streamed = handle_streams_maps(ctx) ? 1 : 0;
+  if (streamed) *streamed = plan_step(ctx).streamed ? 1 : 0;
 
   return DATUM_OCEAN_OK;
 }
@@ -2261,9 +2256,7 @@ int datum_ocean_debug_rowpass(datum_ocean_t ctx, int cascade, float *c, float *d
     a.first = cascade;
     a.cascades = 1;
 
-    hipError_t le = hipSuccess;
-    DISPATCH_N(ctx->N, le = launch_rowpass<NN>(ctx, a, nullptr));
-    HIPCHECK(ctx, le);
+    HIPCHECK(ctx, launch(ctx, *plan_step(ctx).row, a, nullptr));
   }
 
   if (ctx->half)
@@ -2288,7 +2281,7 @@ int datum_ocean_profile_begin(datum_ocean_t ctx, int max_steps, int stride)
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  int const groups = (ctx->cascades + cascade_group(ctx) - 1) / cascade_group(ctx);
+  int const groups = plan_step(ctx).groups;
 
   while (ctx->events.size() < (size_t)4 * max_steps * groups)
   {
@@ -2301,6 +2294,7 @@ int datum_ocean_profile_begin(datum_ocean_t ctx, int max_steps, int stride)
   ctx->profmax = max_steps;
   ctx->profsteps = 0;
   ctx->profstride = stride;
+  ctx->profgroups = groups;
   ctx->profcalls = 0;
 
   return DATUM_OCEAN_OK;
@@ -2317,9 +2311,7 @@ int datum_ocean_profile_end(datum_ocean_t ctx, double *rowpass_ms, double *colpa
   double row = 0, col = 0;
 
   // a sampled step = one launch of either pass per cascade group: the sums over a step's launches
-  int const groups = (ctx->cascades + cascade_group(ctx) - 1) / cascade_group(ctx);
-
-  for(int i = 0; i < ctx->profsteps * groups; ++i)
+  for(int i = 0; i < ctx->profsteps * ctx->profgroups; ++i)
   {
     float ms;
     HIPCHECK(ctx, hipEventElapsedTime(&ms, ctx->events[4*i+0], ctx->events[4*i+1]));

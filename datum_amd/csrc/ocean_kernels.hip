@@ -68,7 +68,7 @@ namespace ocean
     float const *omega;  // [cascade][(N/2+1)^2] dispersion(k) by (|m - N/2|, |n - N/2|)
     int ndt;
     int cascades;        // cascades THIS launch works on ...
-    int first;           // ... starting with this one (the two passes are launched per group of cascades: ocean_capi, cascade_group)
+    int first;           // ... starting with this one (the two passes are launched per group of cascades: ocean_capi, plan_step)
     float dt[MAX_PENDING];
     CascadeConst casc[DATUM_OCEAN_MAX_CASCADES];
 #ifdef OCEAN_STAMPS
@@ -1144,16 +1144,6 @@ namespace ocean
   // 16 or 8 + maps 24 bytes per point and cascade) is beyond the Infinity Cache; the policy is part of the instruction, hence a template
   // flag.  4096^2 always streams (one cascade is 0.9 GB); grids below 1024^2 never do (sixteen cascades of 512^2 still fit).
   template<int N> constexpr bool col_has_stream_variant() { return N == 1024 || N == 2048; }
-
-  // the working set up to which writing the maps through wins: 1024^2 x 4 (218 MB) 82.4 k grids/s written through against 78.9 k streamed, x 5
-  // (272 MB) 72.4-74.0 against 72.1-72.5 k, x 6 (327 MB) 68.8 against 76.1 k; 2048^2 x 1 and the fp16 spectrum's x 4 / x 6 (185 / 277 MB)
-  // written through by 0-3 % (profiles/r06_store_policies.txt)
-  constexpr double MAPS_RESIDENT_BYTES = 300.0e6;
-
-  inline bool maps_stream(int N, int cascades, bool half)
-  {
-    return N >= 4096 || (N >= 1024 && (double)cascades * N * N * (half ? 44.0 : 52.0) > MAPS_RESIDENT_BYTES);
-  }
 
   template<int N, bool H16, bool STREAM>
   __device__ __forceinline__ void colpass_body(StepArgs const &a)

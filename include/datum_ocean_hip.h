@@ -133,7 +133,7 @@ int datum_ocean_set_cascade(datum_ocean_t ctx, int cascade, float wavescale, flo
 #define DATUM_OCEAN_SPECTRUM_FP32 0
 #define DATUM_OCEAN_SPECTRUM_FP16 1
 #define DATUM_OCEAN_SPECTRUM_FP16_H0 2
-int datum_ocean_set_spectrum_format(datum_ocean_t ctx, int format);
+int datum_ocean_set_spectrum_format(datum_ocean_t ctx, int format);   /* DATUM_OCEAN_ESTATE while a profile is open (the format can change the cascade groups its samples are per) or the literal mode is on */
 
 /* VALIDATION MODE (round 5): displace through the reference's own algorithm instead of the fused kernels -- ocean.sim, log2 N
  * radix-2 Stockham stages along rows and along columns with the LITERAL twiddle table of ocean.cpp:686-700 (cos / sin of unreduced
@@ -145,11 +145,11 @@ int datum_ocean_set_spectrum_format(datum_ocean_t ctx, int format);
 int datum_ocean_set_literal_transform(datum_ocean_t ctx, int on);   /* DATUM_OCEAN_ESTATE while a profile is open or the spectrum format is FP16 (and those two refuse while the mode is on) */
 
 /* Cascades per launch of the two kernels (ABI 7).  The reference records one dispatch per shader for its one grid (ocean.cpp:769-789).
- * A handle whose working set (52 bytes per point and cascade, 44 with the fp16 spectrum) is resident in the 256 MiB Infinity Cache takes
- * every cascade in one launch per kernel.  Beyond that the maps are streamed past the cache and row pass and column pass are launched
+ * A handle whose working set (52 bytes per point and cascade, 44 with the fp16 spectrum) is at most 300 MB, resident in the Infinity Cache,
+ * takes every cascade in one launch per kernel.  Beyond that the maps are streamed past the cache and row pass and column pass are launched
  * group by group -- row(g), column(g), row(g + 1), ... on the handle's stream -- so that what a group's row pass leaves for its column pass
  * (and h0 and the phase from step to step) stays in the cache: 0 (default) = the module's choice, the largest group whose 28 (20) bytes
- * per point fit -- 8 cascades of 1024^2, 2 of 2048^2, 1 of 4096^2 -- in groups of equal size; n > 0: n cascades per launch (n >= cascades:
+ * per point fit 240 MB -- 8 cascades of 1024^2, 2 of 2048^2, 1 of 4096^2 -- in groups of equal size; n > 0: n cascades per launch (n >= cascades:
  * one launch per kernel).  Results do not depend on the group.  The getter reports the group in use and the launches per kernel and
  * displace call. */
 int datum_ocean_set_cascade_group(datum_ocean_t ctx, int cascades_per_launch);

@@ -174,15 +174,40 @@ def test_module_keeps_off_the_null_stream():
     # point names a stream.  The one exception is the twiddle upload inside datum_ocean_create, before any stream of the handle has work.
     import re
 
+    def call_args(text, start):
+        # the top-level arguments of the call whose "(" is at text[start - 1]: commas inside (), [], {} and template <> do not split
+        args, depth, cur, i = [], 0, "", start
+        while True:
+            ch = text[i]
+            if ch in "([{" or (ch == "<" and re.match(r"\w", text[i - 1]) and text[i + 1] != "<"):
+                depth += 1
+            elif ch in ")]}>" and not (ch == ">" and text[i - 1] == "-"):
+                if depth == 0:
+                    return args + [cur.strip()]
+                depth -= 1
+            elif ch == "," and depth == 0:
+                args.append(cur.strip())
+                cur = ""
+                i += 1
+                continue
+            cur += ch
+            i += 1
+
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     hits = []
+    launches = {"hipLaunchKernelGGL": 0, "hipLaunchKernel": 0, "hipExtLaunchKernel": 0}
     for name in ("ocean_capi.hip", "ocean_farm.hip", "ocean_gen.hip", "ocean_literal.hip", "ocean_kernels.hip"):
         text = open(os.path.join(root, "datum_amd", "csrc", name)).read()
         for m in re.finditer(r"\b(hipMemcpy|hipMemset|hipMemcpyDtoH|hipMemcpyHtoD|hipMemcpyDtoD|hipDeviceSynchronize)\s*\(", text):
             line = text.count("\n", 0, m.start()) + 1
             hits.append((name, line, m.group(1)))
-        # kernels are launched with an explicit stream argument (hipLaunchKernelGGL's fifth) or through launch(), never on stream 0
-        for m in re.finditer(r"hipLaunchKernelGGL\(([^;]*?)\);", text, re.S):
-            args = m.group(1)
-            assert re.search(r",\s*0,\s*(ctx->stream|stream|f->stream)\s*,", args) or "ctx->stream" in args or "stream" in args, (name, args[:80])
+        # every kernel launch names a stream of the handle or of the farm: hipLaunchKernelGGL's fifth argument, hipLaunchKernel's and
+        # hipExtLaunchKernel's sixth -- never 0 or nullptr
+        code = re.sub(r"//[^\n]*", "", text)
+        for m in re.finditer(r"\b(hipLaunchKernelGGL|hipLaunchKernel|hipExtLaunchKernel)\s*\(", code):
+            args = call_args(code, m.end())
+            stream = args[4 if m.group(1) == "hipLaunchKernelGGL" else 5]
+            assert stream in ("ctx->stream", "f->stream", "stream"), (name, code.count("\n", 0, m.start()) + 1, stream)
+            launches[m.group(1)] += 1
+    assert all(launches.values()), launches
     assert [h[2] for h in hits] == ["hipMemcpy"] and hits[0][0] == "ocean_capi.hip", hits

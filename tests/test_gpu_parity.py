@@ -1475,6 +1475,11 @@ def test_cascade_groups_do_not_change_the_result(capi, oracle, report, N, C, hal
             with pytest.raises(capi.OceanError) as e:
                 oc.set_cascade_group(1)                       # the samples of an open profile are per group
             assert e.value.code == capi.ESTATE
+            nbytes = oc.algorithmic_bytes()
+            with pytest.raises(capi.OceanError) as e:
+                oc.set_spectrum_format(not half)              # ... and the format can change the groups (1024^2 x 6: 2 in fp32, 1 in fp16)
+            assert e.value.code == capi.ESTATE
+            assert oc.algorithmic_bytes() == nbytes and oc.cascade_group() == (g, launches)   # (the format as it was)
             for _ in range(2):
                 oc.update(DT)
                 oc.displace()

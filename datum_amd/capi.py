@@ -113,18 +113,29 @@ SYMBOLS = {
     "datum_ocean_farm_stream_flags": (I, [P, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]),
     "datum_ocean_set_cascade_group": (I, [P, I]),
     "datum_ocean_cascade_group": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I)]),
+    "datum_ocean_set_foam": (I, [P, I]),
+    "datum_ocean_set_foam_params": (I, [P, I, F, F, F]),
+    "datum_ocean_reset_foam": (I, [P, I]),
+    "datum_ocean_bind_foam": (I, [P, P, ctypes.c_size_t]),
+    "datum_ocean_foam_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
+    "datum_ocean_read_foam": (I, [P, I, P]),
+    "datum_ocean_upload_height": (I, [P, I, P]),
 }
 
 
 # DATUM_OCEAN_ABI_VERSION of include/datum_ocean_hip.h as SYMBOLS above was written against it.  A constant, not a read of the header: an
 # installed or copied package has no include/ beside it (tests/test_golden_and_abi.py asserts that the two agree in the source tree).
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # datum_ocean_set_spectrum_format's values (include/datum_ocean_hip.h)
 SPECTRUM_FORMATS = {"fp32": 0, "fp16": 1, "fp16h0": 2}
 
 # datum_ocean_set_map_store_policy's values
 MAP_STORE_POLICIES = {"auto": 0, "written through": 1, "streamed": 2}
+
+# datum_ocean_set_foam's modes (ABI 9)
+FOAM_OFF, FOAM_JACOBIAN, FOAM_ACCUMULATE = 0, 1, 2
+FOAM_MODES = {"off": FOAM_OFF, "jacobian": FOAM_JACOBIAN, "accumulate": FOAM_ACCUMULATE}
 
 
 def header_abi_version():
@@ -246,6 +257,12 @@ class Ocean:
             phase = np.ascontiguousarray(phase, np.float32)
             assert phase.size == self.N * self.N
         self._check(self.lib.datum_ocean_upload_state(self.h, cascade, _ptr(h0), _ptr(phase) if phase is not None else None))
+
+    def upload_height(self, cascade, h0):
+        """replace the cascade's h0 and keep its phase and foam accumulator (datum_ocean_upload_height)"""
+        h0 = np.ascontiguousarray(h0, np.float32)
+        assert h0.size == 2 * self.N * self.N
+        self._check(self.lib.datum_ocean_upload_height(self.h, cascade, _ptr(h0)))
 
     def upload_seed(self, cascade, seed):
         seed = np.ascontiguousarray(seed, np.float32)
@@ -452,6 +469,35 @@ class Ocean:
     def export_maps(self, cascade, device_ptr, nbytes):
         """the cascade's maps as the reference's [layer][y][x][4] RGBA32F image, into DEVICE memory (datum_ocean_export_maps)"""
         self._check(self.lib.datum_ocean_export_maps(self.h, cascade, ctypes.c_void_p(device_ptr), nbytes))
+
+    # -- foam (datum_ocean_set_foam ...): the Jacobian of the horizontal displacement, one fp32 plane per cascade --------------
+
+    def set_foam(self, mode):
+        """"off" (default), "jacobian" (the plane holds J) or "accumulate" (persistent coverage in [0, 1]); or a FOAM_* value"""
+        self._check(self.lib.datum_ocean_set_foam(self.h, FOAM_MODES[mode] if isinstance(mode, str) else int(mode)))
+
+    def set_foam_params(self, cascade, threshold=0.5, gain=2.0, decay=1.0):
+        """the accumulation's parameters of one cascade (defaults: the module's)"""
+        self._check(self.lib.datum_ocean_set_foam_params(self.h, cascade, threshold, gain, decay))
+
+    def reset_foam(self, cascade):
+        self._check(self.lib.datum_ocean_reset_foam(self.h, cascade))
+
+    def bind_foam(self, device_ptr, nbytes):
+        """caller-owned device memory (cascades * N * N * 4 bytes) becomes the foam plane; None / 0 restores the handle's own"""
+        self._check(self.lib.datum_ocean_bind_foam(self.h, P(device_ptr) if device_ptr else None, nbytes))
+
+    def foam_device(self):
+        """(device pointer, bytes) of the foam plane in use"""
+        p = P()
+        n = ctypes.c_size_t()
+        self._check(self.lib.datum_ocean_foam_device(self.h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def read_foam(self, cascade):
+        out = np.empty((self.N, self.N), np.float32)
+        self._check(self.lib.datum_ocean_read_foam(self.h, cascade, _ptr(out)))
+        return out
 
     def algorithmic_bytes(self):
         row, col = D(), D()

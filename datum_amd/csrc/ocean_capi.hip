@@ -18,6 +18,7 @@
 #include "ocean_gen.hip"
 #include "ocean_literal.hip"
 #include "ocean_farm.hip"
+#include "ocean_foam.hip"
 
 using namespace ocean;
 
@@ -80,6 +81,15 @@ struct datum_ocean_ctx
   bool uploaded[DATUM_OCEAN_MAX_CASCADES] = {};
 
   std::vector<float> pending;         // queued update_ocean dt's
+
+  // foam (datum_ocean_set_foam): one fp32 plane per cascade, computed by displace after the column pass
+  int foammode = DATUM_OCEAN_FOAM_OFF;
+  float *foam = nullptr;              // the plane in use: boundfoam, else ownfoam
+  float *ownfoam = nullptr;           // allocated while foam is on
+  float *boundfoam = nullptr;         // datum_ocean_bind_foam
+  FoamKernels foamkernels = {};
+  float foamthreshold[DATUM_OCEAN_MAX_CASCADES], foamgain[DATUM_OCEAN_MAX_CASCADES], foamdecay[DATUM_OCEAN_MAX_CASCADES];
+  double foamdt = 0.0;                // sum of the update dt's since the last displace (pending can be flushed at any time)
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -495,6 +505,60 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
+  size_t foam_bytes(datum_ocean_ctx const *ctx) { return (size_t)ctx->cascades * plane(ctx) * sizeof(float); }
+
+  // zero one cascade's foam plane (-1: all of them), on the handle's stream
+  int zero_foam(datum_ocean_ctx *ctx, int cascade)
+  {
+    size_t const P = plane(ctx);
+
+    if (cascade < 0)
+      HIPCHECK(ctx, hipMemsetAsync(ctx->foam, 0, foam_bytes(ctx), ctx->stream));
+    else
+      HIPCHECK(ctx, hipMemsetAsync(ctx->foam + cascade * P, 0, P * sizeof(float), ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the foam plane for the cascades [first, first + count), read from the maps the column pass (or the literal dispatches) just wrote;
+  // written through or streamed as the plan stores the maps
+  int launch_foam(datum_ocean_ctx *ctx, FoamArgs &fa, int first, int count, bool streamed)
+  {
+    fa.first = first;
+
+    void *args[] = { &fa };
+    int tiles = 0;
+
+    DISPATCH_N(ctx->N, tiles = foam_tiles<NN>());
+
+    bool const accum = ctx->foammode == DATUM_OCEAN_FOAM_ACCUMULATE;
+
+    HIPCHECK(ctx, hipLaunchKernel(ctx->foamkernels.k[accum][streamed], dim3(tiles, count), dim3(FOAM_THREADS), args, 0, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the arguments of a displace call's foam launches; consumes the dt accumulated since the last displace
+  FoamArgs foam_args(datum_ocean_ctx *ctx)
+  {
+    FoamArgs fa = {};
+    fa.maps = ctx->maps;
+    fa.foam = ctx->foam;
+
+    double const dt = ctx->foamdt;
+
+    for(int c = 0; c < ctx->cascades; ++c)
+    {
+      FoamCascade &f = fa.casc[c];
+      f.inv2h = (float)((double)ctx->N / (2.0 * (double)ctx->casc[c].wavescale));
+      f.threshold = ctx->foamthreshold[c];
+      f.gain = ctx->foamgain[c];
+      f.fade = (float)std::min(1.0, std::exp(-(double)ctx->foamdecay[c] * dt));
+    }
+
+    return fa;
+  }
+
   // an ncclResult_t never leaves the module
   int fail_comm(datum_ocean_ctx *ctx, ocean::RcclApi *api, ncclComm_t comm, ncclResult_t r, char const *what)
   {
@@ -655,6 +719,15 @@ int datum_ocean_create(datum_ocean_t *out, int device, int resolution, int casca
     ctx->casc[c].rowscale = 1.0f;
   }
 
+  for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
+  {
+    ctx->foamthreshold[c] = 0.5f;
+    ctx->foamgain[c] = 2.0f;
+    ctx->foamdecay[c] = 1.0f;
+  }
+
+  DISPATCH_N(resolution, ctx->foamkernels = foam_kernels<NN>());
+
   // the LDS limit of every kernel in the table: a kernel the module launches is one it configured
   DISPATCH_N(resolution, ctx->kernels = step_kernels<NN>());
 
@@ -711,6 +784,7 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->litfields);
   (void)hipFree(ctx->litweights);
   (void)hipFree(ctx->scratch);
+  (void)hipFree(ctx->ownfoam);
 
   if (ctx->ownstream)
     (void)hipStreamDestroy(ctx->ownstream);
@@ -882,11 +956,43 @@ int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, fl
   else
     HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * P, 0, P * sizeof(float), ctx->stream));
 
+  // a new state starts without foam
+  if (ctx->foammode == DATUM_OCEAN_FOAM_ACCUMULATE)
+  {
+    rc = zero_foam(ctx, cascade);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+  }
+
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));   // the host buffers are the caller's again
 
   ctx->wildphase[cascade] = wild != 0;
 
   ctx->uploaded[cascade] = true;
+  ctx->scaledirty[cascade] = true;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_upload_height(datum_ocean_t ctx, int cascade, float const *h0)
+{
+  if (!ctx || !h0)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_upload_height: null argument");
+
+  if (cascade < 0 || cascade >= ctx->cascades)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_upload_height: cascade out of range");
+
+  if (!ctx->uploaded[cascade])
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_upload_height: the cascade holds no state (datum_ocean_upload_state)");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // the same state with new wave parameters: the phase (and the updates queued for it) and the foam accumulator stay
+  size_t const P = plane(ctx);
+
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->h0 + cascade * P, h0, P * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));   // the host buffer is the caller's again
+
   ctx->scaledirty[cascade] = true;
 
   return DATUM_OCEAN_OK;
@@ -1051,6 +1157,14 @@ int datum_ocean_resume_state(datum_ocean_t ctx, int cascade, void const *device_
   HIPCHECK(ctx, hipMemcpyAsync(ctx->h0 + cascade * P, device_src, P * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(ctx->phase + cascade * P, static_cast<char const*>(device_src) + P * sizeof(float2), P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
 
+  // another state: its foam starts from zero
+  if (ctx->foammode == DATUM_OCEAN_FOAM_ACCUMULATE)
+  {
+    rc = zero_foam(ctx, cascade);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+  }
+
   ctx->wildphase[cascade] = (flags & 1) != 0;
   ctx->uploaded[cascade] = true;
   ctx->scaledirty[cascade] = true;
@@ -1064,6 +1178,7 @@ int datum_ocean_update(datum_ocean_t ctx, float dt)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_update: null handle");
 
   ctx->pending.push_back(dt);
+  ctx->foamdt += (double)dt;
 
   if (ctx->pending.size() > 4 * MAX_PENDING)
   {
@@ -1120,6 +1235,17 @@ int datum_ocean_displace(datum_ocean_t ctx)
       HIPCHECK(ctx, launch_literal(a, ctx->stream));
     }
 
+    if (ctx->foammode != DATUM_OCEAN_FOAM_OFF)
+    {
+      FoamArgs fa = foam_args(ctx);
+
+      rc = launch_foam(ctx, fa, 0, ctx->cascades, plan_step(ctx).streamed);
+      if (rc != DATUM_OCEAN_OK)
+        return rc;
+    }
+
+    ctx->foamdt = 0.0;
+
     return DATUM_OCEAN_OK;
   }
 
@@ -1139,6 +1265,14 @@ int datum_ocean_displace(datum_ocean_t ctx)
   StepArgs a = make_args(ctx, (int)ctx->pending.size(), ctx->pending.data());
   ctx->pending.clear();
 
+  bool const foam = ctx->foammode != DATUM_OCEAN_FOAM_OFF;
+  FoamArgs fa;
+
+  if (foam)
+    fa = foam_args(ctx);
+
+  ctx->foamdt = 0.0;
+
   if (sampling)
     ctx->profcalls += 1;
 
@@ -1152,6 +1286,14 @@ int datum_ocean_displace(datum_ocean_t ctx)
 
     HIPCHECK(ctx, launch(ctx, *plan.row, a, ev));
     HIPCHECK(ctx, launch(ctx, *plan.col, a, ev ? ev + 2 : nullptr));
+
+    // the group's foam while its maps are still in the cache (not sampled: the profile times the two passes)
+    if (foam)
+    {
+      rc = launch_foam(ctx, fa, a.first, a.cascades, plan.streamed);
+      if (rc != DATUM_OCEAN_OK)
+        return rc;
+    }
   }
 
   if (prof)
@@ -1669,6 +1811,144 @@ int datum_ocean_read_maps(datum_ocean_t ctx, int cascade, float *maps)
   return DATUM_OCEAN_OK;
 }
 
+/* -- foam ------------------------------------------------------------------------------------------------------------------ */
+
+int datum_ocean_set_foam(datum_ocean_t ctx, int mode)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam: null handle");
+
+  if (mode != DATUM_OCEAN_FOAM_OFF && mode != DATUM_OCEAN_FOAM_JACOBIAN && mode != DATUM_OCEAN_FOAM_ACCUMULATE)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam: unknown mode");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  if (mode == DATUM_OCEAN_FOAM_OFF)
+  {
+    if (ctx->ownfoam)
+    {
+      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+      HIPCHECK(ctx, hipFree(ctx->ownfoam));
+      ctx->ownfoam = nullptr;
+    }
+
+    ctx->foam = nullptr;
+    ctx->foammode = mode;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  if (!ctx->ownfoam)
+    HIPCHECK(ctx, hipMalloc(&ctx->ownfoam, foam_bytes(ctx)));
+
+  ctx->foam = ctx->boundfoam ? ctx->boundfoam : ctx->ownfoam;
+  ctx->foammode = mode;
+
+  int rc = zero_foam(ctx, -1);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_set_foam_params(datum_ocean_t ctx, int cascade, float threshold, float gain, float decay)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam_params: null handle");
+
+  if (cascade < 0 || cascade >= ctx->cascades)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam_params: cascade out of range");
+
+  if (!std::isfinite(threshold) || !std::isfinite(gain) || !std::isfinite(decay))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam_params: threshold, gain and decay must be finite");
+
+  if (gain < 0 || decay < 0)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam_params: gain and decay must not be negative");
+
+  ctx->foamthreshold[cascade] = threshold;
+  ctx->foamgain[cascade] = gain;
+  ctx->foamdecay[cascade] = decay;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_reset_foam(datum_ocean_t ctx, int cascade)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_reset_foam: null handle");
+
+  if (cascade < 0 || cascade >= ctx->cascades)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_reset_foam: cascade out of range");
+
+  if (ctx->foammode == DATUM_OCEAN_FOAM_OFF)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_reset_foam: foam is off (datum_ocean_set_foam)");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return zero_foam(ctx, cascade);
+}
+
+int datum_ocean_bind_foam(datum_ocean_t ctx, void *device_ptr, size_t bytes)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_bind_foam: null handle");
+
+  if (device_ptr && bytes < foam_bytes(ctx))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bind_foam: buffer smaller than cascades * N * N * 4 bytes");
+
+  if (device_ptr && ((uintptr_t)device_ptr & 15))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bind_foam: buffer must be 16-byte aligned");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  ctx->boundfoam = (float*)device_ptr;
+
+  if (ctx->foammode != DATUM_OCEAN_FOAM_OFF)
+    ctx->foam = ctx->boundfoam ? ctx->boundfoam : ctx->ownfoam;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
+{
+  if (!ctx || !device_ptr)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_foam_device: null argument");
+
+  if (ctx->foammode == DATUM_OCEAN_FOAM_OFF)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_foam_device: foam is off (datum_ocean_set_foam)");
+
+  *device_ptr = ctx->foam;
+
+  if (bytes)
+    *bytes = foam_bytes(ctx);
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_foam(datum_ocean_t ctx, int cascade, float *foam)
+{
+  if (!ctx || !foam)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_foam: null argument");
+
+  if (cascade < 0 || cascade >= ctx->cascades)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_foam: cascade out of range");
+
+  if (ctx->foammode == DATUM_OCEAN_FOAM_OFF)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_read_foam: foam is off (datum_ocean_set_foam)");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  size_t const P = plane(ctx);
+
+  HIPCHECK(ctx, hipMemcpyAsync(foam, ctx->foam + cascade * P, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
 }   // extern "C"
 
 // a cascade's maps as the reference's 2-layer RGBA32F image (datum_ocean_export_maps); one thread per texel.  LAYOUT (up to 1024^2): in the
@@ -1999,6 +2279,13 @@ int datum_ocean_release_memory(datum_ocean_t ctx, void *device_ptr)
 
       if (reinterpret_cast<char const*>(ctx->maps) >= lo && reinterpret_cast<char const*>(ctx->maps) < hi)
         ctx->maps = ctx->ownmaps;
+
+      // the same for a foam plane bound there (datum_ocean_bind_foam): back to the handle's own plane (none while foam is off)
+      if (reinterpret_cast<char const*>(ctx->boundfoam) >= lo && reinterpret_cast<char const*>(ctx->boundfoam) < hi)
+      {
+        ctx->boundfoam = nullptr;
+        ctx->foam = (ctx->foammode != DATUM_OCEAN_FOAM_OFF) ? ctx->ownfoam : nullptr;
+      }
 
       hipError_t e = hipDestroyExternalMemory(ctx->importedmemory[i].memory);
 

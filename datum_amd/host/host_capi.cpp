@@ -289,6 +289,36 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_foam(void *c, int mode)
+  {
+    try
+    {
+      set_ocean_foam(static_cast<HostContext*>(c)->context, mode);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_set_ocean_foam_params(void *c, float threshold, float gain, float decay)
+  {
+    try
+    {
+      set_ocean_foam_params(static_cast<HostContext*>(c)->context, threshold, gain, decay);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_read_ocean_foam(void *c, float *foam)
+  {
+    try
+    {
+      read_ocean_foam(static_cast<HostContext*>(c)->context, foam);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

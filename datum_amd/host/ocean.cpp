@@ -330,11 +330,9 @@ namespace
     }
     else if (context.boundheight != params.heightid)
     {
-      // lerp_ocean_waves changed h0 only: keep the device phase, which is ahead of params.phase
-      vector<float> phase(params.phase.size());
-
-      check(context.hip, datum_ocean_read_state(context.hip, 0, phase.data()), "datum_ocean_read_state");
-      check(context.hip, datum_ocean_upload_state(context.hip, 0, params.height.data(), phase.data()), "datum_ocean_upload_state");
+      // lerp_ocean_waves changed h0 only: the same state, so the device phase (which is ahead of params.phase) and the foam
+      // accumulator are kept
+      check(context.hip, datum_ocean_upload_height(context.hip, 0, params.height.data()), "datum_ocean_upload_height");
 
       context.boundheight = params.heightid;
     }
@@ -846,6 +844,36 @@ void fetch_ocean_state(OceanContext &context, OceanParams &params)
 
   if (params.deviceheight)
     check(context.hip, datum_ocean_read_height(context.hip, 0, params.height.data()), "datum_ocean_read_height");
+}
+
+
+///////////////////////// foam //////////////////////////////////////////////
+void set_ocean_foam(OceanContext &context, int mode)
+{
+  assert(context.ready);
+
+  check(context.hip, datum_ocean_set_foam(context.hip, mode), "datum_ocean_set_foam");
+}
+
+void set_ocean_foam_params(OceanContext &context, float threshold, float gain, float decay)
+{
+  assert(context.ready);
+
+  check(context.hip, datum_ocean_set_foam_params(context.hip, 0, threshold, gain, decay), "datum_ocean_set_foam_params");
+}
+
+void read_ocean_foam(OceanContext &context, float *foam)
+{
+  assert(context.ready);
+
+  check(context.hip, datum_ocean_read_foam(context.hip, 0, foam), "datum_ocean_read_foam");
+}
+
+void ocean_foam_device(OceanContext &context, void **device_ptr, size_t *bytes)
+{
+  assert(context.ready);
+
+  check(context.hip, datum_ocean_foam_device(context.hip, device_ptr, bytes), "datum_ocean_foam_device");
 }
 
 

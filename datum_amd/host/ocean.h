@@ -331,6 +331,15 @@ std::size_t release_parked_states(OceanContext &context, OceanParams const *keep
 // copy the device-resident phase (and, with deviceheight, h0) back into params (applies any queued update first)
 void fetch_ocean_state(OceanContext &context, OceanParams &params);
 
+// foam (include/datum_ocean_hip.h, ABI 9): DATUM_OCEAN_FOAM_OFF / _JACOBIAN / _ACCUMULATE on the context's handle (after
+// prepare_ocean_context).  The plane is computed by every displace; a context that binds another state (upload or resume of a parked
+// one) starts that state's accumulation from zero, as the C ABI does.  The same state with new wave parameters (lerp_ocean_waves, with
+// or without OceanParams::deviceheight) keeps it
+void set_ocean_foam(OceanContext &context, int mode);
+void set_ocean_foam_params(OceanContext &context, float threshold, float gain, float decay);
+void read_ocean_foam(OceanContext &context, float *foam /* [N][N] */);
+void ocean_foam_device(OceanContext &context, void **device_ptr, std::size_t *bytes);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

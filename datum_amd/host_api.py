@@ -94,6 +94,9 @@ def load():
             "datum_host_fetch_ocean_state": (I, [P, P]),
             "datum_host_read_ocean_displacement": (I, [P, P]),
             "datum_host_read_ocean_vertices": (I, [P, P, P]),
+            "datum_host_set_ocean_foam": (I, [P, I]),
+            "datum_host_set_ocean_foam_params": (I, [P, F, F, F]),
+            "datum_host_read_ocean_foam": (I, [P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -285,6 +288,18 @@ class OceanContext:
     def read_displacement(self):
         out = np.empty((2, self.N, self.N, 4), np.float32)
         self._check(self.lib.datum_host_read_ocean_displacement(self.c, out.ctypes.data_as(P)))
+        return out
+
+    def set_foam(self, mode):
+        """set_ocean_foam: "off", "jacobian", "accumulate" or a capi.FOAM_* value"""
+        self._check(self.lib.datum_host_set_ocean_foam(self.c, capi.FOAM_MODES[mode] if isinstance(mode, str) else int(mode)))
+
+    def set_foam_params(self, threshold=0.5, gain=2.0, decay=1.0):
+        self._check(self.lib.datum_host_set_ocean_foam_params(self.c, threshold, gain, decay))
+
+    def read_foam(self):
+        out = np.empty((self.N, self.N), np.float32)
+        self._check(self.lib.datum_host_read_ocean_foam(self.c, out.ctypes.data_as(P)))
         return out
 
     def read_vertices(self, mesh):

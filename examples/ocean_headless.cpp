@@ -47,6 +47,8 @@ int main(int argc, char **argv)
 
     Ocean const *oceanmesh = resources.create<Ocean>(64, 64);               // :59 (1024 x 1024 in the example)
 
+    set_ocean_foam(oceancontext, DATUM_OCEAN_FOAM_JACOBIAN);                // extension: the Jacobian foam plane, computed by every render
+
     camera.lookat(Vec3(0, 0, 8), Vec3(1, 0, 8), Vec3(0, 0, 1));             // :63
 
     for(int frame = 0; frame < frames; ++frame)
@@ -59,6 +61,9 @@ int main(int argc, char **argv)
 
     std::vector<float> maps((size_t)2 * resolution * resolution * 4);
     read_ocean_displacement(oceancontext, maps.data());
+
+    std::vector<float> jacobian((size_t)resolution * resolution);
+    read_ocean_foam(oceancontext, jacobian.data());
 
     std::vector<Mesh::Vertex> vertices(64 * 64);
     read_ocean_vertices(oceancontext, oceanmesh, vertices.data());
@@ -76,6 +81,16 @@ int main(int argc, char **argv)
     printf("phase[10][20] %.9g phase[%d][%d] %.9g\n", ocean.phase[(size_t)10 * N + 20], N - 1, N - 1, ocean.phase[(size_t)N * N - 1]);
     printf("dz_rms %.9g\n", sqrt(sumsq / ((double)N * N)));
     printf("map[0][5][7] %.9g %.9g %.9g map[1][5][7] %.9g %.9g %.9g\n", texel(0, 5, 7, 0), texel(0, 5, 7, 1), texel(0, 5, 7, 2), texel(1, 5, 7, 0), texel(1, 5, 7, 1), texel(1, 5, 7, 2));
+
+    size_t folded = 0;
+    double jsum = 0;
+    for(float j : jacobian)
+    {
+      folded += (j < 0.0f) ? 1 : 0;
+      jsum += j;
+    }
+
+    printf("foam folded_fraction %.9g mean_J %.9g\n", (double)folded / ((double)N * N), jsum / ((double)N * N));
 
     Mesh::Vertex const &v = vertices[40 * 64 + 33];
     printf("vertex[40][33] pos %.9g %.9g %.9g uv %.9g %.9g n %.9g %.9g %.9g t %.9g %.9g %.9g %.9g\n", v.position.x, v.position.y, v.position.z, v.texcoord.x, v.texcoord.y,

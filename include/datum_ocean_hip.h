@@ -42,8 +42,10 @@ extern "C" {
  *   6  round 5: datum_ocean_farm_partition, datum_ocean_own_stream
  *   7  round 6: datum_ocean_set_cascade_group / datum_ocean_cascade_group (DATUM_OCEAN_SPECTRUM_FP16_H0, a further value of an existing
  *      argument, came later in the round without a bump)
- *   8  round 6: datum_ocean_set_map_store_policy / datum_ocean_map_store_policy */
-#define DATUM_OCEAN_ABI_VERSION 8
+ *   8  round 6: datum_ocean_set_map_store_policy / datum_ocean_map_store_policy
+ *   9  the Jacobian foam plane: datum_ocean_set_foam, datum_ocean_set_foam_params, datum_ocean_reset_foam, datum_ocean_bind_foam,
+ *      datum_ocean_foam_device, datum_ocean_read_foam, datum_ocean_upload_height */
+#define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
 
 enum
@@ -172,6 +174,12 @@ int datum_ocean_map_store_policy(datum_ocean_t ctx, int *policy, int *streamed);
 int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, float const *phase);
 int datum_ocean_read_state(datum_ocean_t ctx, int cascade, float *phase);
 
+/* Replace the h0 of a cascade's state and keep everything else (ABI 9): the phase as advanced so far, the updates queued for it, and
+ * the foam accumulator (datum_ocean_set_foam).  The same state with new wave parameters -- what lerp_ocean_waves does to
+ * OceanParams::height on the host (ocean.cpp:194-211) -- where datum_ocean_upload_state would start a new one.  N*N*2 floats, host
+ * pointer.  DATUM_OCEAN_ESTATE for a cascade that holds no state. */
+int datum_ocean_upload_height(datum_ocean_t ctx, int cascade, float const *h0);
+
 /* Park a cascade's state (h0 and the phase as advanced so far: 12 * N * N bytes, h0 first) in caller-owned DEVICE memory,
  * and bring a parked state back -- device to device on the handle's stream, no host round trip.  For a host object that
  * renders more states than the handle has cascades (the reference keeps every OceanParams' phase on the host and uploads
@@ -220,6 +228,50 @@ int datum_ocean_gen(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, 
 #define DATUM_OCEAN_PAYLOAD_XYZ16 2
 int datum_ocean_payload_bytes(datum_ocean_t ctx, int format, size_t *bytes);
 int datum_ocean_pack_displacement(datum_ocean_t ctx, int format, void *payload_device, size_t bytes);
+
+/* -- foam (ABI 9; nothing in the reference: SURVEY.md F3) ---------------------------------------------------------------------
+ * Where the choppy surface pinches or folds over.  The mesh places each vertex at p - D(p), where D = (dx, dy) from map layer 0 with
+ * choppiness already applied (ocean_gen.hip; reference gen.comp:122-124).  For that mapping, per texel:
+ *
+ *     J = (1 − a)(1 − d) − b·c
+ *     a = ∂x dx,  b = ∂y dx,  c = ∂x dy,  d = ∂y dy
+ *
+ * each derivative a periodic central difference in world units, (f[i+1] − f[i−1]) / (2·h), h = wavescale / N the texel pitch (the map
+ * covers wavescale metres: texcoord = position·scale, scale = 1/wavescale); x is the column index and y the row index, as in
+ * datum_ocean_read_maps.  J < 0: the rendered mesh folds at that texel; J = 1: the surface is undisturbed.
+ *
+ * Modes, per handle (datum_ocean_set_foam):
+ *   OFF (default)  nothing is computed or allocated; every other call behaves as without foam
+ *   JACOBIAN       the plane holds J; no state
+ *   ACCUMULATE     the plane holds a persistent coverage value in [0, 1]:
+ *                    foam = max(clamp((threshold − J)·gain, 0, 1), foam_prev · fade),   fade = (float)exp(−(double)decay · (double)dt)
+ *                  dt = the sum, in double, of the datum_ocean_update dt values queued since the previous displace (its own accumulator: it
+ *                  does not depend on when queued steps are flushed); fade is computed on the host and held at 1 when that sum is negative.
+ *                  Per cascade (datum_ocean_set_foam_params): threshold 0.5, gain 2, decay 1 s^-1 by default
+ * STORAGE: one fp32 plane per cascade, row-major [cascade][y][x], 4 * N * N bytes -- a plain R32F image a renderer samples with the same
+ * texture coordinate (and repeat addressing) as the displacement map, or imports (datum_ocean_bind_foam).  It lies beside the maps; their
+ * 24-byte layout does not change, nor do the maps' values (bit for bit: the foam kernel reads them after the column pass).
+ * Computed by datum_ocean_displace in every configuration (spectrum formats, literal mode, map-store policies, cascade groups, bound maps,
+ * a running farm): one launch after each cascade group's column pass (after the literal dispatches in the literal mode).
+ * NOT included in: the farm payloads, datum_ocean_gen, datum_ocean_export_maps, the profile's events, datum_ocean_algorithmic_bytes.
+ *   set_foam         mode: allocates (own plane) and zero-fills the plane in use; OFF frees the own plane.  Drains the stream
+ *   set_foam_params  EINVAL if a value is not finite or gain / decay is negative; takes effect at the next displace
+ *   reset_foam       zeroes the cascade's plane (ESTATE while foam is OFF).  datum_ocean_upload_state and datum_ocean_resume_state do the
+ *                    same to the cascade's accumulator in ACCUMULATE mode (a new state); datum_ocean_rebuild_height and
+ *                    datum_ocean_upload_height do not (the same state with new wave parameters: lerp_ocean_waves, every frame)
+ *   bind_foam        caller-owned DEVICE memory of at least cascades * N * N * 4 bytes, 16-byte aligned, becomes the plane (its contents are
+ *                    the accumulator from then on: reset_foam to start from zero); NULL restores the handle's own.  Allowed in any mode
+ *   foam_device      the plane in use and its bytes; ESTATE while foam is OFF
+ *   read_foam        blocking read of the cascade's N * N floats (host pointer); ESTATE while foam is OFF */
+#define DATUM_OCEAN_FOAM_OFF 0
+#define DATUM_OCEAN_FOAM_JACOBIAN 1
+#define DATUM_OCEAN_FOAM_ACCUMULATE 2
+int datum_ocean_set_foam(datum_ocean_t ctx, int mode);
+int datum_ocean_set_foam_params(datum_ocean_t ctx, int cascade, float threshold, float gain, float decay);
+int datum_ocean_reset_foam(datum_ocean_t ctx, int cascade);
+int datum_ocean_bind_foam(datum_ocean_t ctx, void *device_ptr, size_t bytes);
+int datum_ocean_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes);
+int datum_ocean_read_foam(datum_ocean_t ctx, int cascade, float *foam);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

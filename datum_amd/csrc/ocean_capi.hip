@@ -40,6 +40,31 @@ struct StepKernels
   PassKernel col[2][2];               // [fp16 work spectrum][maps streamed]; the written-through kernel twice where there is no streamed form
 };
 
+// a device plane the caller can replace with memory of its own (datum_ocean_bind_maps, datum_ocean_bind_foam)
+template<typename T>
+struct BindablePlane
+{
+  T *own = nullptr;
+  T *bound = nullptr;
+  T *get() const { return bound ? bound : own; }   // the plane in use
+};
+
+// the host's record of one cascade (what the kernels read of it is CascadeConst)
+struct CascadeState
+{
+  bool uploaded = false;              // holds a state (upload_state, resume_state, rebuild_height)
+  bool wild = false;                  // its phase lies outside [0, 2 pi)
+  bool scaledirty = false;            // fp16 only: h0 changed since specscale was sized
+  bool omegadirty = true;             // the wave scale changed since its dispersion table was built
+  float omegamax = 0.0f;              // largest dispersion (table corner)
+  float foamthreshold = 0.5f, foamgain = 2.0f, foamdecay = 1.0f;   // datum_ocean_set_foam_params
+
+  // the transitions of include/datum_ocean_hip.h (foam): a new state (upload_state, resume_state; new_state_foam zeroes its accumulator),
+  // and the same state with a new h0 (upload_height, rebuild_height), which keeps the phase, the updates queued for it and the accumulator
+  void new_state(bool wildphase) { uploaded = true; wild = wildphase; scaledirty = true; }
+  void new_height() { scaledirty = true; }
+};
+
 struct datum_ocean_ctx
 {
   int device = 0;
@@ -66,29 +91,21 @@ struct datum_ocean_ctx
   bool literal = false;
   float2 *litfields = nullptr;        // [3][N*N]: h, hx, hy of the cascade being displaced (the reference's Spectrum buffer, ocean.cpp:61-68)
   float *litweights = nullptr;        // [N][2 log2 N] (ocean.cpp:686-700)
-  bool scaledirty[DATUM_OCEAN_MAX_CASCADES] = {};   // fp16 only: h0 changed since specscale was sized
   unsigned int *absmax = nullptr;     // device word for ocean_absmax_kernel
-  float4 *maps = nullptr;             // the one in use
-  float4 *ownmaps = nullptr;
+  BindablePlane<float4> maps;
   cf *tw = nullptr;
   float *omega = nullptr;             // [cascade][(N/2+1)^2] dispersion quadrant, rebuilt when a wavescale changes
-  unsigned int omegadirty = ~0u;      // cascades whose wave scale changed since their table was built
-  float omegamax[DATUM_OCEAN_MAX_CASCADES] = {};   // largest dispersion of each cascade (table corner)
-  bool wildphase[DATUM_OCEAN_MAX_CASCADES] = {};   // an uploaded phase lies outside [0, 2 pi)
   cf *scratch = nullptr;              // 3 row-major planes for the debug read-backs (lazy)
 
   CascadeConst casc[DATUM_OCEAN_MAX_CASCADES];
-  bool uploaded[DATUM_OCEAN_MAX_CASCADES] = {};
+  CascadeState cstate[DATUM_OCEAN_MAX_CASCADES];
 
   std::vector<float> pending;         // queued update_ocean dt's
 
   // foam (datum_ocean_set_foam): one fp32 plane per cascade, computed by displace after the column pass
   int foammode = DATUM_OCEAN_FOAM_OFF;
-  float *foam = nullptr;              // the plane in use: boundfoam, else ownfoam
-  float *ownfoam = nullptr;           // allocated while foam is on
-  float *boundfoam = nullptr;         // datum_ocean_bind_foam
+  BindablePlane<float> foam;          // the own plane exists while foam is on; off, nothing reads the plane (a binding is kept)
   FoamKernels foamkernels = {};
-  float foamthreshold[DATUM_OCEAN_MAX_CASCADES], foamgain[DATUM_OCEAN_MAX_CASCADES], foamdecay[DATUM_OCEAN_MAX_CASCADES];
   double foamdt = 0.0;                // sum of the update dt's since the last displace (pending can be flushed at any time)
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
@@ -148,7 +165,7 @@ namespace
     a.h0h = ctx->h0half ? ctx->h0h : nullptr;
     a.phase = ctx->phase;
     a.spec = ctx->spec;
-    a.maps = ctx->maps;
+    a.maps = ctx->maps.get();
     a.tw = ctx->tw;
     a.omega = ctx->omega;
     a.ndt = ndt;
@@ -237,7 +254,7 @@ namespace
     bool wild = false;
 
     for(int c = 0; c < C; ++c)
-      wild = wild || ctx->wildphase[c];
+      wild = wild || ctx->cstate[c].wild;
 
     int const format = ctx->h0half ? DATUM_OCEAN_SPECTRUM_FP16_H0 : (ctx->half ? DATUM_OCEAN_SPECTRUM_FP16 : DATUM_OCEAN_SPECTRUM_FP32);
 
@@ -309,7 +326,9 @@ namespace
   // (re)build the dispersion quadrant tables of the cascades whose wave scale changed
   int ensure_omega(datum_ocean_ctx *ctx)
   {
-    unsigned int const dirty = ctx->omegadirty & ((ctx->cascades >= 32) ? ~0u : ((1u << ctx->cascades) - 1));
+    unsigned int dirty = 0;
+    for(int c = 0; c < ctx->cascades; ++c)
+      dirty |= (unsigned int)ctx->cstate[c].omegadirty << c;
 
     if (!dirty)
       return DATUM_OCEAN_OK;
@@ -323,13 +342,14 @@ namespace
       // dispersion grows with |k|: its maximum is the table corner |m - N/2| = |n - N/2| = N/2 (same fp32 formula)
       float kc = (6.2831855f * (0.5f * (float)ctx->N)) / ws.v[c];
       float k2 = kc * kc + kc * kc;
-      ctx->omegamax[c] = sqrtf((9.81f * sqrtf(k2)) * (1.0f + k2 / 136900.0f));
+      ctx->cstate[c].omegamax = sqrtf((9.81f * sqrtf(k2)) * (1.0f + k2 / 136900.0f));
     }
 
     hipLaunchKernelGGL(ocean_omega_kernel, dim3(512), dim3(256), 0, ctx->stream, ctx->omega, ctx->N, ctx->cascades, ws, dirty);
     HIPCHECK(ctx, hipGetLastError());
 
-    ctx->omegadirty = 0;
+    for(CascadeState &s : ctx->cstate)
+      s.omegadirty = false;
 
     return DATUM_OCEAN_OK;
   }
@@ -340,12 +360,12 @@ namespace
   {
     for(int c = 0; c < ctx->cascades; ++c)
     {
-      if (ctx->wildphase[c])
+      if (ctx->cstate[c].wild)
         return false;
 
       for(float dt : ctx->pending)
       {
-        if (!(dt >= 0.0f) || !(ctx->omegamax[c] * dt < 6.0f))
+        if (!(dt >= 0.0f) || !(ctx->cstate[c].omegamax * dt < 6.0f))
           return false;
       }
     }
@@ -376,7 +396,7 @@ namespace
         if (!(ctx->pending[i] >= 0.0f))
         {
           for(int c = 0; c < ctx->cascades; ++c)
-            ctx->wildphase[c] = true;
+            ctx->cstate[c].wild = true;
         }
       }
 
@@ -403,7 +423,7 @@ namespace
 
     for(int c = 0; c < ctx->cascades; ++c)
     {
-      if (!ctx->scaledirty[c])
+      if (!ctx->cstate[c].scaledirty)
         continue;
 
       unsigned int bits = 0;
@@ -449,7 +469,7 @@ namespace
         ctx->casc[c].rowscale = std::ldexp(1.0f, e - eh);
       }
 
-      ctx->scaledirty[c] = false;
+      ctx->cstate[c].scaledirty = false;
     }
 
     return DATUM_OCEAN_OK;
@@ -486,7 +506,7 @@ namespace
     if (format == DATUM_OCEAN_PAYLOAD_MAPS)
     {
       // the map block as it lies in memory (device layout), so that the producer may go on writing its own buffer
-      HIPCHECK(ctx, hipMemcpyAsync(payload_device, ctx->maps, need, hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHECK(ctx, hipMemcpyAsync(payload_device, ctx->maps.get(), need, hipMemcpyDeviceToDevice, ctx->stream));
     }
     else
     {
@@ -495,9 +515,9 @@ namespace
       PackShape const sh = pack_shape(ctx->N);
 
       if (format == DATUM_OCEAN_PAYLOAD_XYZ16)
-        hipLaunchKernelGGL(ocean_pack_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->maps, ctx->N, ctx->cascades, payload_device, sh);
+        hipLaunchKernelGGL(ocean_pack_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->maps.get(), ctx->N, ctx->cascades, payload_device, sh);
       else
-        hipLaunchKernelGGL(ocean_pack_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->maps, ctx->N, ctx->cascades, payload_device, sh);
+        hipLaunchKernelGGL(ocean_pack_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->maps.get(), ctx->N, ctx->cascades, payload_device, sh);
 
       HIPCHECK(ctx, hipGetLastError());
     }
@@ -513,9 +533,59 @@ namespace
     size_t const P = plane(ctx);
 
     if (cascade < 0)
-      HIPCHECK(ctx, hipMemsetAsync(ctx->foam, 0, foam_bytes(ctx), ctx->stream));
+      HIPCHECK(ctx, hipMemsetAsync(ctx->foam.get(), 0, foam_bytes(ctx), ctx->stream));
     else
-      HIPCHECK(ctx, hipMemsetAsync(ctx->foam + cascade * P, 0, P * sizeof(float), ctx->stream));
+      HIPCHECK(ctx, hipMemsetAsync(ctx->foam.get() + cascade * P, 0, P * sizeof(float), ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // a new state in the cascade (CascadeState::new_state) starts without foam: its accumulator is zeroed, on the handle's stream
+  int new_state_foam(datum_ocean_ctx *ctx, int cascade)
+  {
+    return (ctx->foammode == DATUM_OCEAN_FOAM_ACCUMULATE) ? zero_foam(ctx, cascade) : DATUM_OCEAN_OK;
+  }
+
+  // datum_ocean_bind_maps, datum_ocean_bind_foam: the size and alignment checks, then the drain (nullptr: the handle's own plane again)
+  template<typename T>
+  int bind_plane(datum_ocean_ctx *ctx, BindablePlane<T> &target, void *device_ptr, size_t bytes, size_t need, char const *too_small, char const *unaligned)
+  {
+    if (device_ptr && bytes < need)
+      return fail(ctx, DATUM_OCEAN_EINVAL, too_small);
+
+    if (device_ptr && ((uintptr_t)device_ptr & 15))
+      return fail(ctx, DATUM_OCEAN_EINVAL, unaligned);
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+    target.bound = static_cast<T*>(device_ptr);
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the literal mode's step for the cascades [first, first + count): the reference's five dispatches, cascade by cascade (ocean.cpp:769-789),
+  // after the general kernel advanced the phase
+  int launch_literals(datum_ocean_ctx *ctx, int first, int count)
+  {
+    size_t const P = plane(ctx);
+
+    for(int c = first; c < first + count; ++c)
+    {
+      LiteralArgs a;
+      a.h0 = ctx->h0 + c * P;
+      a.phase = ctx->phase + c * P;
+      a.h = ctx->litfields;
+      a.hx = ctx->litfields + P;
+      a.hy = ctx->litfields + 2 * P;
+      a.weights = ctx->litweights;
+      a.maps = reinterpret_cast<char*>(ctx->maps.get()) + (size_t)c * map_cascade_bytes(ctx->N);
+      a.N = ctx->N;
+      a.scale = ctx->casc[c].scale;
+      a.choppiness = ctx->casc[c].choppiness;
+
+      HIPCHECK(ctx, launch_literal(a, ctx->stream));
+    }
 
     return DATUM_OCEAN_OK;
   }
@@ -542,8 +612,8 @@ namespace
   FoamArgs foam_args(datum_ocean_ctx *ctx)
   {
     FoamArgs fa = {};
-    fa.maps = ctx->maps;
-    fa.foam = ctx->foam;
+    fa.maps = ctx->maps.get();
+    fa.foam = ctx->foam.get();
 
     double const dt = ctx->foamdt;
 
@@ -551,9 +621,9 @@ namespace
     {
       FoamCascade &f = fa.casc[c];
       f.inv2h = (float)((double)ctx->N / (2.0 * (double)ctx->casc[c].wavescale));
-      f.threshold = ctx->foamthreshold[c];
-      f.gain = ctx->foamgain[c];
-      f.fade = (float)std::min(1.0, std::exp(-(double)ctx->foamdecay[c] * dt));
+      f.threshold = ctx->cstate[c].foamthreshold;
+      f.gain = ctx->cstate[c].foamgain;
+      f.fade = (float)std::min(1.0, std::exp(-(double)ctx->cstate[c].foamdecay * dt));
     }
 
     return fa;
@@ -682,14 +752,13 @@ int datum_ocean_create(datum_ocean_t *out, int device, int resolution, int casca
   CREATECHECK(hipMalloc(&ctx->phase, cascades * P * sizeof(float)));
   CREATECHECK(hipMalloc(&ctx->spec, cascades * P * sizeof(cd)));
   CREATECHECK(hipMalloc(&ctx->absmax, sizeof(unsigned int)));
-  CREATECHECK(hipMalloc(&ctx->ownmaps, cascades * map_cascade_bytes(resolution)));
+  CREATECHECK(hipMalloc(&ctx->maps.own, cascades * map_cascade_bytes(resolution)));
   CREATECHECK(hipMalloc(&ctx->tw, resolution * sizeof(cf)));
   CREATECHECK(hipMalloc(&ctx->omega, (size_t)cascades * (resolution / 2 + 1) * (resolution / 2 + 1) * sizeof(float)));
-  ctx->maps = ctx->ownmaps;
 
   CREATECHECK(hipMemsetAsync(ctx->h0, 0, cascades * P * sizeof(float2), ctx->stream));
   CREATECHECK(hipMemsetAsync(ctx->phase, 0, cascades * P * sizeof(float), ctx->stream));
-  CREATECHECK(hipMemsetAsync(ctx->ownmaps, 0, cascades * map_cascade_bytes(resolution), ctx->stream));
+  CREATECHECK(hipMemsetAsync(ctx->maps.own, 0, cascades * map_cascade_bytes(resolution), ctx->stream));
 
   // exp(+2 pi i k / N), rounded once from double (the reference's table -- ocean.cpp:686-700 -- is per
   // lane and stage and evaluated at unreduced fp32 angles; see datum_ocean_reference_weights)
@@ -717,13 +786,6 @@ int datum_ocean_create(datum_ocean_t *out, int device, int resolution, int casca
     ctx->casc[c].specscale = 1.0f;
     ctx->casc[c].specinv = 1.0f;
     ctx->casc[c].rowscale = 1.0f;
-  }
-
-  for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
-  {
-    ctx->foamthreshold[c] = 0.5f;
-    ctx->foamgain[c] = 2.0f;
-    ctx->foamdecay[c] = 1.0f;
   }
 
   DISPATCH_N(resolution, ctx->foamkernels = foam_kernels<NN>());
@@ -778,13 +840,13 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->spec);
   (void)hipFree(ctx->absmax);
   (void)hipFree(ctx->h0h);
-  (void)hipFree(ctx->ownmaps);
+  (void)hipFree(ctx->maps.own);
   (void)hipFree(ctx->tw);
   (void)hipFree(ctx->omega);
   (void)hipFree(ctx->litfields);
   (void)hipFree(ctx->litweights);
   (void)hipFree(ctx->scratch);
-  (void)hipFree(ctx->ownfoam);
+  (void)hipFree(ctx->foam.own);
 
   if (ctx->ownstream)
     (void)hipStreamDestroy(ctx->ownstream);
@@ -812,20 +874,8 @@ int datum_ocean_bind_maps(datum_ocean_t ctx, void *device_ptr, size_t bytes)
   if (!ctx)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_bind_maps: null handle");
 
-  size_t need = ctx->cascades * map_cascade_bytes(ctx->N);
-
-  if (device_ptr && bytes < need)
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bind_maps: buffer smaller than cascades * N * N * texel_bytes (datum_ocean_map_layout)");
-
-  if (device_ptr && ((uintptr_t)device_ptr & 15))
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bind_maps: buffer must be 16-byte aligned");
-
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  ctx->maps = device_ptr ? (float4*)device_ptr : ctx->ownmaps;
-
-  return DATUM_OCEAN_OK;
+  return bind_plane(ctx, ctx->maps, device_ptr, bytes, ctx->cascades * map_cascade_bytes(ctx->N),
+                    "datum_ocean_bind_maps: buffer smaller than cascades * N * N * texel_bytes (datum_ocean_map_layout)", "datum_ocean_bind_maps: buffer must be 16-byte aligned");
 }
 
 int datum_ocean_maps_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
@@ -833,7 +883,7 @@ int datum_ocean_maps_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
   if (!ctx || !device_ptr)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_maps_device: null argument");
 
-  *device_ptr = ctx->maps;
+  *device_ptr = ctx->maps.get();
 
   if (bytes)
     *bytes = ctx->cascades * map_cascade_bytes(ctx->N);
@@ -877,7 +927,7 @@ int datum_ocean_set_cascade(datum_ocean_t ctx, int cascade, float wavescale, flo
   CascadeConst &cc = ctx->casc[cascade];
 
   if (cc.wavescale != wavescale)
-    ctx->omegadirty |= 1u << cascade;
+    ctx->cstate[cascade].omegadirty = true;
 
   cc.wavescale = wavescale;
   cc.scale = 1 / wavescale;                      // ocean.cpp:743
@@ -912,7 +962,7 @@ int datum_ocean_set_spectrum_format(datum_ocean_t ctx, int format)
 
   for(int c = 0; c < ctx->cascades; ++c)
   {
-    ctx->scaledirty[c] = ctx->half;
+    ctx->cstate[c].scaledirty = ctx->half;
 
     if (!ctx->half)
       ctx->casc[c].specscale = ctx->casc[c].specinv = ctx->casc[c].rowscale = 1.0f;
@@ -956,20 +1006,13 @@ int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, fl
   else
     HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * P, 0, P * sizeof(float), ctx->stream));
 
-  // a new state starts without foam
-  if (ctx->foammode == DATUM_OCEAN_FOAM_ACCUMULATE)
-  {
-    rc = zero_foam(ctx, cascade);
-    if (rc != DATUM_OCEAN_OK)
-      return rc;
-  }
+  rc = new_state_foam(ctx, cascade);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));   // the host buffers are the caller's again
 
-  ctx->wildphase[cascade] = wild != 0;
-
-  ctx->uploaded[cascade] = true;
-  ctx->scaledirty[cascade] = true;
+  ctx->cstate[cascade].new_state(wild != 0);
 
   return DATUM_OCEAN_OK;
 }
@@ -982,18 +1025,17 @@ int datum_ocean_upload_height(datum_ocean_t ctx, int cascade, float const *h0)
   if (cascade < 0 || cascade >= ctx->cascades)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_upload_height: cascade out of range");
 
-  if (!ctx->uploaded[cascade])
+  if (!ctx->cstate[cascade].uploaded)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_upload_height: the cascade holds no state (datum_ocean_upload_state)");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // the same state with new wave parameters: the phase (and the updates queued for it) and the foam accumulator stay
   size_t const P = plane(ctx);
 
   HIPCHECK(ctx, hipMemcpyAsync(ctx->h0 + cascade * P, h0, P * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));   // the host buffer is the caller's again
 
-  ctx->scaledirty[cascade] = true;
+  ctx->cstate[cascade].new_height();
 
   return DATUM_OCEAN_OK;
 }
@@ -1046,14 +1088,14 @@ int datum_ocean_rebuild_height(datum_ocean_t ctx, int cascade, float wavescale, 
   size_t const P = plane(ctx);
 
   hipLaunchKernelGGL(ocean_height_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->seed + cascade * P, ctx->h0 + cascade * P, ctx->N, wavescale, waveamplitude, windspeed, windx, windy);
-  ctx->scaledirty[cascade] = true;
+  ctx->cstate[cascade].new_height();
   HIPCHECK(ctx, hipGetLastError());
 
-  if (!ctx->uploaded[cascade])
+  // a cascade without a state gets one with phase zero -- its foam accumulator is not reset (include/datum_ocean_hip.h)
+  if (!ctx->cstate[cascade].uploaded)
   {
     HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * P, 0, P * sizeof(float), ctx->stream));
-    ctx->wildphase[cascade] = false;
-    ctx->uploaded[cascade] = true;
+    ctx->cstate[cascade].new_state(false);
   }
 
   return DATUM_OCEAN_OK;
@@ -1115,7 +1157,7 @@ int datum_ocean_park_state(datum_ocean_t ctx, int cascade, void *device_dst, siz
   if (bytes != datum_ocean_state_bytes(ctx->N))
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_park_state: buffer must be datum_ocean_state_bytes()");
 
-  if (!ctx->uploaded[cascade])
+  if (!ctx->cstate[cascade].uploaded)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_park_state: the cascade holds no state");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
@@ -1129,7 +1171,7 @@ int datum_ocean_park_state(datum_ocean_t ctx, int cascade, void *device_dst, siz
   HIPCHECK(ctx, hipMemcpyAsync(device_dst, ctx->h0 + cascade * P, P * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(static_cast<char*>(device_dst) + P * sizeof(float2), ctx->phase + cascade * P, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
 
-  *flags = ctx->wildphase[cascade] ? 1 : 0;
+  *flags = ctx->cstate[cascade].wild ? 1 : 0;
 
   return DATUM_OCEAN_OK;
 }
@@ -1157,17 +1199,11 @@ int datum_ocean_resume_state(datum_ocean_t ctx, int cascade, void const *device_
   HIPCHECK(ctx, hipMemcpyAsync(ctx->h0 + cascade * P, device_src, P * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(ctx->phase + cascade * P, static_cast<char const*>(device_src) + P * sizeof(float2), P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
 
-  // another state: its foam starts from zero
-  if (ctx->foammode == DATUM_OCEAN_FOAM_ACCUMULATE)
-  {
-    rc = zero_foam(ctx, cascade);
-    if (rc != DATUM_OCEAN_OK)
-      return rc;
-  }
+  rc = new_state_foam(ctx, cascade);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
-  ctx->wildphase[cascade] = (flags & 1) != 0;
-  ctx->uploaded[cascade] = true;
-  ctx->scaledirty[cascade] = true;
+  ctx->cstate[cascade].new_state((flags & 1) != 0);
 
   return DATUM_OCEAN_OK;
 }
@@ -1195,7 +1231,7 @@ int datum_ocean_displace(datum_ocean_t ctx)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_displace: null handle");
 
   for(int c = 0; c < ctx->cascades; ++c)
-    if (!ctx->uploaded[c])
+    if (!ctx->cstate[c].uploaded)
       return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_displace: a cascade has no state (datum_ocean_upload_state)");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
@@ -1213,47 +1249,18 @@ int datum_ocean_displace(datum_ocean_t ctx)
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  if (ctx->literal)
-  {
-    // the reference's five dispatches, cascade by cascade (ocean.cpp:769-789); the phase was advanced by the general kernel above
-    size_t const P = plane(ctx);
-
-    for(int c = 0; c < ctx->cascades; ++c)
-    {
-      LiteralArgs a;
-      a.h0 = ctx->h0 + c * P;
-      a.phase = ctx->phase + c * P;
-      a.h = ctx->litfields;
-      a.hx = ctx->litfields + P;
-      a.hy = ctx->litfields + 2 * P;
-      a.weights = ctx->litweights;
-      a.maps = reinterpret_cast<char*>(ctx->maps) + (size_t)c * map_cascade_bytes(ctx->N);
-      a.N = ctx->N;
-      a.scale = ctx->casc[c].scale;
-      a.choppiness = ctx->casc[c].choppiness;
-
-      HIPCHECK(ctx, launch_literal(a, ctx->stream));
-    }
-
-    if (ctx->foammode != DATUM_OCEAN_FOAM_OFF)
-    {
-      FoamArgs fa = foam_args(ctx);
-
-      rc = launch_foam(ctx, fa, 0, ctx->cascades, plan_step(ctx).streamed);
-      if (rc != DATUM_OCEAN_OK)
-        return rc;
-    }
-
-    ctx->foamdt = 0.0;
-
-    return DATUM_OCEAN_OK;
-  }
-
   rc = size_spectrum_scale(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  StepPlan const plan = plan_step(ctx);
+  StepPlan plan = plan_step(ctx);
+
+  // the literal mode -- an fp32 spectrum, no update queued, no profile open -- as one group of every cascade
+  if (ctx->literal)
+  {
+    plan.group = ctx->cascades;
+    plan.groups = 1;
+  }
 
   bool const sampling = ctx->profiling && ctx->profsteps < ctx->profmax;
   bool const prof = sampling && ctx->profcalls % ctx->profstride == 0;
@@ -1276,16 +1283,25 @@ int datum_ocean_displace(datum_ocean_t ctx)
   if (sampling)
     ctx->profcalls += 1;
 
-  // the two passes group by group: row(g), column(g), row(g + 1), ...
+  // group by group: row(g), column(g) -- or the literal dispatches -- and foam(g), then row(g + 1), ...
   for(int g = 0; g < plan.groups; ++g)
   {
     a.first = g * plan.group;
     a.cascades = std::min(plan.group, ctx->cascades - a.first);
 
-    hipEvent_t *ev = prof ? &ctx->events[4 * ((size_t)ctx->profsteps * plan.groups + g)] : nullptr;   // row start, row stop, column start, column stop
+    if (ctx->literal)
+    {
+      rc = launch_literals(ctx, a.first, a.cascades);
+      if (rc != DATUM_OCEAN_OK)
+        return rc;
+    }
+    else
+    {
+      hipEvent_t *ev = prof ? &ctx->events[4 * ((size_t)ctx->profsteps * plan.groups + g)] : nullptr;   // row start, row stop, column start, column stop
 
-    HIPCHECK(ctx, launch(ctx, *plan.row, a, ev));
-    HIPCHECK(ctx, launch(ctx, *plan.col, a, ev ? ev + 2 : nullptr));
+      HIPCHECK(ctx, launch(ctx, *plan.row, a, ev));
+      HIPCHECK(ctx, launch(ctx, *plan.col, a, ev ? ev + 2 : nullptr));
+    }
 
     // the group's foam while its maps are still in the cache (not sampled: the profile times the two passes)
     if (foam)
@@ -1320,7 +1336,7 @@ int datum_ocean_gen(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, 
 
   GenArgs g;
   g.set = *set;
-  g.map = reinterpret_cast<float4 const*>(reinterpret_cast<char const*>(ctx->maps) + (size_t)cascade * map_cascade_bytes(ctx->N));
+  g.map = reinterpret_cast<float4 const*>(reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N));
   g.vertices = (float*)vertices_device;
   gen_shape(g, ctx->N, sizex, sizey);
 
@@ -1790,7 +1806,7 @@ int datum_ocean_read_maps(datum_ocean_t ctx, int cascade, float *maps)
   std::vector<float> raw;
   try { raw.resize(bytes / sizeof(float)); } catch (...) { return fail(ctx, DATUM_OCEAN_ENOMEM, "datum_ocean_read_maps: out of host memory"); }
 
-  HIPCHECK(ctx, hipMemcpyAsync(raw.data(), reinterpret_cast<char const*>(ctx->maps) + (size_t)cascade * bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(raw.data(), reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   int const N = ctx->N;
@@ -1825,23 +1841,21 @@ int datum_ocean_set_foam(datum_ocean_t ctx, int mode)
 
   if (mode == DATUM_OCEAN_FOAM_OFF)
   {
-    if (ctx->ownfoam)
+    if (ctx->foam.own)
     {
       HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCHECK(ctx, hipFree(ctx->ownfoam));
-      ctx->ownfoam = nullptr;
+      HIPCHECK(ctx, hipFree(ctx->foam.own));
+      ctx->foam.own = nullptr;
     }
 
-    ctx->foam = nullptr;
     ctx->foammode = mode;
 
     return DATUM_OCEAN_OK;
   }
 
-  if (!ctx->ownfoam)
-    HIPCHECK(ctx, hipMalloc(&ctx->ownfoam, foam_bytes(ctx)));
+  if (!ctx->foam.own)
+    HIPCHECK(ctx, hipMalloc(&ctx->foam.own, foam_bytes(ctx)));
 
-  ctx->foam = ctx->boundfoam ? ctx->boundfoam : ctx->ownfoam;
   ctx->foammode = mode;
 
   int rc = zero_foam(ctx, -1);
@@ -1867,9 +1881,9 @@ int datum_ocean_set_foam_params(datum_ocean_t ctx, int cascade, float threshold,
   if (gain < 0 || decay < 0)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_foam_params: gain and decay must not be negative");
 
-  ctx->foamthreshold[cascade] = threshold;
-  ctx->foamgain[cascade] = gain;
-  ctx->foamdecay[cascade] = decay;
+  ctx->cstate[cascade].foamthreshold = threshold;
+  ctx->cstate[cascade].foamgain = gain;
+  ctx->cstate[cascade].foamdecay = decay;
 
   return DATUM_OCEAN_OK;
 }
@@ -1895,21 +1909,8 @@ int datum_ocean_bind_foam(datum_ocean_t ctx, void *device_ptr, size_t bytes)
   if (!ctx)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_bind_foam: null handle");
 
-  if (device_ptr && bytes < foam_bytes(ctx))
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bind_foam: buffer smaller than cascades * N * N * 4 bytes");
-
-  if (device_ptr && ((uintptr_t)device_ptr & 15))
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bind_foam: buffer must be 16-byte aligned");
-
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  ctx->boundfoam = (float*)device_ptr;
-
-  if (ctx->foammode != DATUM_OCEAN_FOAM_OFF)
-    ctx->foam = ctx->boundfoam ? ctx->boundfoam : ctx->ownfoam;
-
-  return DATUM_OCEAN_OK;
+  return bind_plane(ctx, ctx->foam, device_ptr, bytes, foam_bytes(ctx),
+                    "datum_ocean_bind_foam: buffer smaller than cascades * N * N * 4 bytes", "datum_ocean_bind_foam: buffer must be 16-byte aligned");
 }
 
 int datum_ocean_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
@@ -1920,7 +1921,7 @@ int datum_ocean_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
   if (ctx->foammode == DATUM_OCEAN_FOAM_OFF)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_foam_device: foam is off (datum_ocean_set_foam)");
 
-  *device_ptr = ctx->foam;
+  *device_ptr = ctx->foam.get();
 
   if (bytes)
     *bytes = foam_bytes(ctx);
@@ -1943,7 +1944,7 @@ int datum_ocean_read_foam(datum_ocean_t ctx, int cascade, float *foam)
 
   size_t const P = plane(ctx);
 
-  HIPCHECK(ctx, hipMemcpyAsync(foam, ctx->foam + cascade * P, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(foam, ctx->foam.get() + cascade * P, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;
@@ -2013,7 +2014,7 @@ int datum_ocean_export_maps(datum_ocean_t ctx, int cascade, void *device_dst, si
   size_t const P = plane(ctx);
   int const blocks = (int)((P + 255) / 256 < 4096 ? (P + 255) / 256 : 4096);
 
-  char const *block = reinterpret_cast<char const*>(ctx->maps) + (size_t)cascade * map_cascade_bytes(ctx->N);
+  char const *block = reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N);
 
   if (ctx->N <= 1024)
     hipLaunchKernelGGL(ocean_export_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, block, ctx->N, static_cast<float4*>(device_dst), pack_shape(ctx->N));
@@ -2274,18 +2275,16 @@ int datum_ocean_release_memory(datum_ocean_t ctx, void *device_ptr)
       HIPCHECK(ctx, hipSetDevice(ctx->device));
       HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));    // nothing enqueued may still write it
 
-      // (a VkBuffer commonly sits at an offset inside its VkDeviceMemory: the maps may be bound anywhere inside the block)
+      // a plane bound inside the block is the handle's own again (a VkBuffer commonly sits at an offset inside its VkDeviceMemory: the
+      // maps or the foam plane may be bound anywhere inside it)
       char const *lo = static_cast<char const*>(device_ptr), *hi = lo + ctx->importedmemory[i].bytes;
+      auto inside = [lo, hi](void const *p) { return static_cast<char const*>(p) >= lo && static_cast<char const*>(p) < hi; };
 
-      if (reinterpret_cast<char const*>(ctx->maps) >= lo && reinterpret_cast<char const*>(ctx->maps) < hi)
-        ctx->maps = ctx->ownmaps;
+      if (inside(ctx->maps.bound))
+        ctx->maps.bound = nullptr;
 
-      // the same for a foam plane bound there (datum_ocean_bind_foam): back to the handle's own plane (none while foam is off)
-      if (reinterpret_cast<char const*>(ctx->boundfoam) >= lo && reinterpret_cast<char const*>(ctx->boundfoam) < hi)
-      {
-        ctx->boundfoam = nullptr;
-        ctx->foam = (ctx->foammode != DATUM_OCEAN_FOAM_OFF) ? ctx->ownfoam : nullptr;
-      }
+      if (inside(ctx->foam.bound))
+        ctx->foam.bound = nullptr;
 
       hipError_t e = hipDestroyExternalMemory(ctx->importedmemory[i].memory);
 
@@ -2496,7 +2495,7 @@ int datum_ocean_debug_sim(datum_ocean_t ctx, int cascade, float *h, float *hx, f
 
   StepArgs a = make_args(ctx, 0, nullptr);
 
-  if (ctx->wildphase[cascade])
+  if (ctx->cstate[cascade].wild)
     hipLaunchKernelGGL(ocean_sim_kernel<true>, dim3(1024), dim3(256), 0, ctx->stream, a, ctx->N, cascade, ctx->scratch, ctx->scratch + P, ctx->scratch + 2 * P);
   else
     hipLaunchKernelGGL(ocean_sim_kernel<false>, dim3(1024), dim3(256), 0, ctx->stream, a, ctx->N, cascade, ctx->scratch, ctx->scratch + P, ctx->scratch + 2 * P);
@@ -2520,7 +2519,7 @@ int datum_ocean_debug_rowpass(datum_ocean_t ctx, int cascade, float *c, float *d
 
   // (as datum_ocean_displace: without a state the row pass would read h0 and phase the caller never wrote -- in FP16_H0 a spurious
   // "NaN or an infinity" from size_spectrum_scale)
-  if (!ctx->uploaded[cascade])
+  if (!ctx->cstate[cascade].uploaded)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_debug_rowpass: the cascade has no state (datum_ocean_upload_state)");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));

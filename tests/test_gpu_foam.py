@@ -246,6 +246,60 @@ def test_bound_plane(capi, oracle):
         assert np.array_equal(outs[0][c], outs[1][c])
 
 
+def test_plane_bound_while_off(capi, oracle):
+    # bind_foam is allowed in any mode: a plane bound while foam is off becomes the plane in use (zero-filled) when foam is switched on,
+    # stays bound through off and on again, and bind_foam(None, 0) returns to the handle's own plane
+    import torch
+
+    N, C = 64, 2
+    nbytes = C * N * N * 4
+    zero = np.zeros((C, N, N), np.float32)
+    oc, ws = _setup(capi, oracle, N, C, chops=[2.5, 3.0])
+    with oc:
+        oc.set_foam("off")
+        buf = torch.full((C * N * N,), 7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        oc.bind_foam(buf.data_ptr(), nbytes)
+        with pytest.raises(capi.OceanError) as e:
+            oc.foam_device()
+        assert e.value.code == capi.ESTATE
+        oc.update(DT)
+        oc.displace()                                # foam off: the bound plane is not touched
+        oc.sync()
+        assert np.array_equal(buf.cpu().numpy(), np.full(C * N * N, 7.0, np.float32))
+
+        oc.set_foam("accumulate")
+        assert oc.foam_device() == (buf.data_ptr(), nbytes)
+        assert np.array_equal(buf.cpu().numpy().reshape(C, N, N), zero)
+        for c in range(C):
+            oc.set_foam_params(c, 1.5, 1.0, 1.0)    # coverage 1.5 - J wherever J < 1.5: nonzero over much of the sea
+        for _ in range(2):
+            oc.update(DT)
+            oc.displace()
+        oc.sync()
+        got = buf.cpu().numpy().reshape(C, N, N)
+        assert np.any(got > 0)
+        for c in range(C):
+            assert np.array_equal(got[c], oc.read_foam(c))
+
+        oc.set_foam("off")
+        oc.set_foam("jacobian")
+        assert oc.foam_device() == (buf.data_ptr(), nbytes)
+        assert np.array_equal(buf.cpu().numpy().reshape(C, N, N), zero)
+        oc.displace()
+        oc.sync()
+        jac = buf.cpu().numpy().reshape(C, N, N)
+        assert not np.array_equal(jac, zero)
+
+        oc.bind_foam(None, 0)
+        own, n = oc.foam_device()
+        assert own != buf.data_ptr() and n == nbytes
+        oc.displace()                                # the same maps again: the same J, now in the handle's own plane
+        for c in range(C):
+            assert np.array_equal(oc.read_foam(c), jac[c])
+        assert np.array_equal(buf.cpu().numpy().reshape(C, N, N), jac)
+
+
 def test_accumulation(capi, oracle, report):
     N, C = 256, 2
     params = [(0.5, 2.0, 1.0), (0.9, 4.0, 0.5)]

@@ -120,6 +120,8 @@ SYMBOLS = {
     "datum_ocean_foam_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
     "datum_ocean_read_foam": (I, [P, I, P]),
     "datum_ocean_upload_height": (I, [P, I, P]),
+    "datum_ocean_sample_surface": (I, [P, I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_surface": (I, [P, I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -136,6 +138,10 @@ MAP_STORE_POLICIES = {"auto": 0, "written through": 1, "streamed": 2}
 # datum_ocean_set_foam's modes (ABI 9)
 FOAM_OFF, FOAM_JACOBIAN, FOAM_ACCUMULATE = 0, 1, 2
 FOAM_MODES = {"off": FOAM_OFF, "jacobian": FOAM_JACOBIAN, "accumulate": FOAM_ACCUMULATE}
+
+# surface queries (datum_ocean_sample_surface, added at ABI 9): floats per record and the largest iteration count
+SURFACE_SAMPLE_FLOATS = 8
+SURFACE_MAX_ITERATIONS = 16
 
 
 def header_abi_version():
@@ -178,7 +184,11 @@ def load():
         if have != want:
             raise OSError(f"{LIBPATH} reports ABI version {have}, this binding is written against version {want} of include/datum_ocean_hip.h: rebuild the HIP module (`make`)")
         for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                # entry points added within a version (include/datum_ocean_hip.h) are detected by symbol: a library without one is stale
+                raise OSError(f"{LIBPATH} does not export {name}, which this binding of ABI version {want} declares: rebuild the HIP module (`make`)") from None
             fn.restype = res
             fn.argtypes = args
         _lib = lib
@@ -497,6 +507,21 @@ class Ocean:
     def read_foam(self, cascade):
         out = np.empty((self.N, self.N), np.float32)
         self._check(self.lib.datum_ocean_read_foam(self.h, cascade, _ptr(out)))
+        return out
+
+    # -- surface queries (datum_ocean_sample_surface): the water surface above world points ---------------------------------------
+
+    def sample_surface(self, cascade, oceanset, points_ptr, count, samples_ptr, iterations=4):
+        """Enqueue the query of `count` float2 world points (device pointer, 8-byte aligned) into `count` records of 8 floats (device
+        pointer, 16-byte aligned): surface point (x, y, height), residual, unit normal, foam.  `oceanset` as for gen()."""
+        self._check(self.lib.datum_ocean_sample_surface(self.h, cascade, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
+                                                        count, P(samples_ptr) if samples_ptr else None))
+
+    def read_surface(self, cascade, oceanset, points, iterations=4):
+        """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_surface(self.h, cascade, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
         return out
 
     def algorithmic_bytes(self):

@@ -19,6 +19,7 @@
 #include "ocean_literal.hip"
 #include "ocean_farm.hip"
 #include "ocean_foam.hip"
+#include "ocean_surface.hip"
 
 using namespace ocean;
 
@@ -107,6 +108,11 @@ struct datum_ocean_ctx
   BindablePlane<float> foam;          // the own plane exists while foam is on; off, nothing reads the plane (a binding is kept)
   FoamKernels foamkernels = {};
   double foamdt = 0.0;                // sum of the update dt's since the last displace (pending can be flushed at any time)
+
+  // datum_ocean_read_surface's device staging of points and records, grown on demand
+  float2 *surfacepoints = nullptr;
+  float4 *surfacesamples = nullptr;
+  size_t surfacecapacity = 0;         // points both hold
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -847,6 +853,8 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->litweights);
   (void)hipFree(ctx->scratch);
   (void)hipFree(ctx->foam.own);
+  (void)hipFree(ctx->surfacepoints);
+  (void)hipFree(ctx->surfacesamples);
 
   if (ctx->ownstream)
     (void)hipStreamDestroy(ctx->ownstream);
@@ -1945,6 +1953,105 @@ int datum_ocean_read_foam(datum_ocean_t ctx, int cascade, float *foam)
   size_t const P = plane(ctx);
 
   HIPCHECK(ctx, hipMemcpyAsync(foam, ctx->foam.get() + cascade * P, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
+/* -- surface queries ------------------------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // the argument checks both entry points share; `name` goes into the error text
+  int check_surface_args(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void const *samples, char const *name)
+  {
+    std::string const what = name;
+
+    if (!ctx || !set)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle or set").c_str());
+
+    if (count > 0 && (!points || !samples))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or samples").c_str());
+
+    if (cascade < 0 || cascade >= ctx->cascades)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
+
+    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
+
+    if (((uintptr_t)points & 7) || ((uintptr_t)samples & 15))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and samples 16-byte aligned").c_str());
+
+    if (count > (size_t)INT32_MAX)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": count above INT32_MAX").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  SurfaceArgs surface_args(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void *samples)
+  {
+    SurfaceArgs s;
+    s.set = *set;
+    s.map = reinterpret_cast<float4 const*>(reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N));
+    s.foam = (ctx->foammode != DATUM_OCEAN_FOAM_OFF) ? ctx->foam.get() + (size_t)cascade * plane(ctx) : nullptr;
+    s.points = static_cast<float2 const*>(points);
+    s.samples = static_cast<float4*>(samples);
+    s.N = ctx->N;
+    s.count = (int)count;
+    s.iterations = iterations;
+    return s;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_sample_surface(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points_device, size_t count, void *samples_device)
+{
+  int rc = check_surface_args(ctx, cascade, set, iterations, points_device, count, samples_device, "datum_ocean_sample_surface");
+  if (rc != DATUM_OCEAN_OK || count == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  SurfaceArgs s = surface_args(ctx, cascade, set, iterations, points_device, count, samples_device);
+
+  HIPCHECK(ctx, launch_surface(s, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, int iterations, float const *points, size_t count, float *samples)
+{
+  int rc = check_surface_args(ctx, cascade, set, iterations, points, count, samples, "datum_ocean_read_surface");
+  if (rc != DATUM_OCEAN_OK || count == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  if (count > ctx->surfacecapacity)
+  {
+    // the old staging may still be read by an earlier launch of this stream
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHECK(ctx, hipFree(ctx->surfacepoints));
+    HIPCHECK(ctx, hipFree(ctx->surfacesamples));
+    ctx->surfacepoints = nullptr;
+    ctx->surfacesamples = nullptr;
+    ctx->surfacecapacity = 0;
+
+    HIPCHECK(ctx, hipMalloc(&ctx->surfacepoints, count * sizeof(float2)));
+    HIPCHECK(ctx, hipMalloc(&ctx->surfacesamples, count * 2 * sizeof(float4)));
+    ctx->surfacecapacity = count;
+  }
+
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->surfacepoints, points, count * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+
+  SurfaceArgs s = surface_args(ctx, cascade, set, iterations, ctx->surfacepoints, count, ctx->surfacesamples);
+
+  HIPCHECK(ctx, launch_surface(s, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(samples, ctx->surfacesamples, count * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;

@@ -319,6 +319,16 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_query_ocean_surface(void *c, void *p, float const *xy, size_t count, float *samples, int iterations)
+  {
+    try
+    {
+      query_ocean_surface(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanSurfaceSample*>(samples), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

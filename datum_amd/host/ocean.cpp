@@ -877,6 +877,20 @@ void ocean_foam_device(OceanContext &context, void **device_ptr, size_t *bytes)
 }
 
 
+///////////////////////// query_ocean_surface ///////////////////////////////
+void query_ocean_surface(OceanContext &context, OceanParams const &params, Vec2 const *positions, size_t count, OceanSurfaceSample *samples, int iterations)
+{
+  static_assert(sizeof(Vec2) == 8, "the C ABI reads the positions as float2");
+
+  if (!context.ready)
+    throw runtime_error("query_ocean_surface: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  check(context.hip, datum_ocean_read_surface(context.hip, 0, &set, iterations, reinterpret_cast<float const*>(positions), count, reinterpret_cast<float*>(samples)), "datum_ocean_read_surface");
+}
+
+
 ///////////////////////// read_ocean_displacement ///////////////////////////
 void read_ocean_displacement(OceanContext &context, float *maps)
 {

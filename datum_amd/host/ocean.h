@@ -340,6 +340,22 @@ void set_ocean_foam_params(OceanContext &context, float threshold, float gain, f
 void read_ocean_foam(OceanContext &context, float *foam /* [N][N] */);
 void ocean_foam_device(OceanContext &context, void **device_ptr, std::size_t *bytes);
 
+// surface queries (include/datum_ocean_hip.h: datum_ocean_read_surface, the definition there): the water surface above world points, for
+// buoyancy and the like.  The maps are the ones the context last displaced (as read_ocean_displacement's); swell, plane and scale come from
+// `params` (through make_oceanset -- the camera's fields are not read).  Blocking; after render_ocean_surface or displace_ocean_surface.
+// Throws before prepare_ocean_context
+struct OceanSurfaceSample
+{
+  lml::Vec3 position;                     // the surface point found; .z is the water height above the query point
+  float residual;                         // |position.xy - query|: large where the surface folds over (no height field there)
+  lml::Vec3 normal;                       // unit normal (the mesh's, without distance smoothing)
+  float foam;                             // the foam plane there, 0 while foam is off
+};
+
+static_assert(sizeof(OceanSurfaceSample) == 32, "OceanSurfaceSample must be the C ABI's record of DATUM_OCEAN_SURFACE_SAMPLE_FLOATS floats");
+
+void query_ocean_surface(OceanContext &context, OceanParams const &params, lml::Vec2 const *positions, std::size_t count, OceanSurfaceSample *samples, int iterations = 4);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

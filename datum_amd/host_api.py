@@ -97,6 +97,7 @@ def load():
             "datum_host_set_ocean_foam": (I, [P, I]),
             "datum_host_set_ocean_foam_params": (I, [P, F, F, F]),
             "datum_host_read_ocean_foam": (I, [P, P]),
+            "datum_host_query_ocean_surface": (I, [P, P, P, ctypes.c_size_t, P, I]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -300,6 +301,14 @@ class OceanContext:
     def read_foam(self):
         out = np.empty((self.N, self.N), np.float32)
         self._check(self.lib.datum_host_read_ocean_foam(self.c, out.ctypes.data_as(P)))
+        return out
+
+    def query_ocean_surface(self, params, xy, iterations=4):
+        """query_ocean_surface: the surface above the (M, 2) world points on the maps the context last displaced, swell, plane and scale from
+        `params`; returns (M, 8) float32 records (OceanSurfaceSample: position, residual, normal, foam)"""
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], capi.SURFACE_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_host_query_ocean_surface(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
         return out
 
     def read_vertices(self, mesh):

@@ -44,7 +44,9 @@ extern "C" {
  *      argument, came later in the round without a bump)
  *   8  round 6: datum_ocean_set_map_store_policy / datum_ocean_map_store_policy
  *   9  the Jacobian foam plane: datum_ocean_set_foam, datum_ocean_set_foam_params, datum_ocean_reset_foam, datum_ocean_bind_foam,
- *      datum_ocean_foam_device, datum_ocean_read_foam, datum_ocean_upload_height */
+ *      datum_ocean_foam_device, datum_ocean_read_foam, datum_ocean_upload_height.
+ *      Later added at 9 without a bump (nothing changed, entry points were only added): the surface queries datum_ocean_sample_surface and
+ *      datum_ocean_read_surface.  A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
 
@@ -272,6 +274,47 @@ int datum_ocean_reset_foam(datum_ocean_t ctx, int cascade);
 int datum_ocean_bind_foam(datum_ocean_t ctx, void *device_ptr, size_t bytes);
 int datum_ocean_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes);
 int datum_ocean_read_foam(datum_ocean_t ctx, int cascade, float *foam);
+
+/* -- surface queries (added at ABI 9; nothing in the reference: SURVEY.md F5) ---------------------------------------------------
+ * Where is the water surface above the world point (x, y)?  For buoyancy, wakes, spray, "is the camera under water".  With choppy waves
+ * the answer is not the map read at (x, y): the mesh places the vertex of base point b at P(b) − D(P(b)) horizontally (ocean_gen.hip;
+ * reference gen.comp:122-124), so the water above (x, y) comes from another texel, and a plain lookup is wrong by about choppiness·|D|.
+ *
+ * The query uses the swell fields, `scale` (= 1/wavescale) and `plane[3]` of the set; everything else (camera, projection, smoothing) is
+ * ignored.  For a base point b in the plane, with gen's own constants:
+ *
+ *     θ     = frequency · (swelldirection · b) + swellphase          frequency = 2π / swelllength
+ *     P(b)  = b + qi · A · swelldirection · cos θ                    qi = swellsteepness / (frequency · A · 4 + 1e-6),  A = swellamplitude
+ *     t     = P(b) · scale                                           texcoord; REPEAT bilinear, texel centres at (i + 0.5) / N, as gen
+ *     D, m  = layer 0 (dx, dy, dz) and layer 1 (normal) of the cascade's map at t
+ *     V(b)  = ( P.x − D.x,  P.y − D.y,  −plane.w + A · sin θ + D.z )   the vertex gen would place for base point b
+ *
+ * The query for a world point q = (qx, qy) is a fixed-point solve: start at b₀ = q, apply exactly `iterations` updates
+ * b ← b + (q − V(b).xy) (no early exit: a point's result does not depend on which other points share its wave), then evaluate once more
+ * at the final b.  Each point gets a record of DATUM_OCEAN_SURFACE_SAMPLE_FLOATS = 8 floats (32 bytes):
+ *     0-2  V(b): the surface point found; .z is the water height above q
+ *     3    residual = |V(b).xy − q|.  Large where the surface folds (J < 0 in the foam block's definition): there the surface is not a
+ *          height field and no b solves the equation; also where `iterations` was too few for a steep, choppy state
+ *     4-6  the unit normal: gen's tbn[2] at b with smoothing = 0, i.e. normalize(t0·m.x + t1·m.y + t2·m.z) with gen's Gerstner frame
+ *          t0, t1, t2; it does not depend on the camera
+ *     7    foam: the foam plane in use sampled at t with the same REPEAT bilinear fetch; 0 while foam is OFF
+ * iterations = 0 is plain sampling at q (what a naive integration does; its residual shows how wrong that is).  A non-finite query
+ * coordinate gives a record of quiet NaNs and fetches nothing.
+ *
+ *   sample_surface  enqueue and return: one kernel on the handle's stream behind the last displace; like datum_ocean_gen it applies no
+ *                   pending update and reads the map as it lies (own buffer or datum_ocean_bind_maps).  points_device: `count` float2
+ *                   (x, y), 8-byte aligned; samples_device: count * 32 bytes, 16-byte aligned.  DEVICE pointers
+ *   read_surface    the same from HOST arrays, blocking: copies through device staging buffers the handle owns (grown on demand, freed by
+ *                   datum_ocean_destroy), all on the handle's stream
+ * DATUM_OCEAN_EINVAL for a null handle or set, null arrays with count > 0, a cascade out of range, iterations outside
+ * [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS], misaligned arrays and count > INT32_MAX.  count == 0 enqueues nothing.  A query writes only
+ * the samples: the maps and the foam plane are not touched. */
+#define DATUM_OCEAN_SURFACE_SAMPLE_FLOATS 8
+#define DATUM_OCEAN_SURFACE_MAX_ITERATIONS 16
+int datum_ocean_sample_surface(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, int iterations,
+                               void const *points_device, size_t count, void *samples_device);
+int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, int iterations,
+                             float const *points, size_t count, float *samples);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

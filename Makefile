@@ -5,7 +5,7 @@ HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -fno-f
 
 LIB = datum_amd/lib/libdatum_ocean_hip.so
 SRC = datum_amd/csrc/ocean_capi.hip
-DEPS = datum_amd/csrc/ocean_kernels.hip datum_amd/csrc/ocean_literal.hip datum_amd/csrc/ocean_gen.hip datum_amd/csrc/ocean_farm.hip datum_amd/csrc/ocean_foam.hip datum_amd/csrc/ocean_surface.hip datum_amd/csrc/ocean_fft_core.h include/datum_ocean_hip.h
+DEPS = datum_amd/csrc/ocean_kernels.hip datum_amd/csrc/ocean_literal.hip datum_amd/csrc/ocean_gen.hip datum_amd/csrc/ocean_farm.hip datum_amd/csrc/ocean_foam.hip datum_amd/csrc/ocean_surface.hip datum_amd/csrc/ocean_fft_core.h datum_amd/csrc/ocean_layout.h include/datum_ocean_hip.h
 
 HOSTLIB = datum_amd/lib/libdatum_ocean_host.so
 HOSTSRC = datum_amd/host/ocean.cpp datum_amd/host/host_capi.cpp
@@ -45,12 +45,15 @@ $(FARMEXAMPLE): examples/ocean_farm.cpp $(HOSTLIB)
 $(EXAMPLE): examples/ocean_headless.cpp $(HOSTLIB)
 	$(CXX) -O2 -std=c++14 -Wall -o $@ examples/ocean_headless.cpp -Ldatum_amd/lib -ldatum_ocean_host -ldatum_ocean_hip -Wl,-rpath,'$$ORIGIN/../datum_amd/lib'
 
-# CPU emulation of the thread-parallel line FFT (tests only)
+# CPU emulation of the thread-parallel line FFT, and the memory layouts walked point by point (tests only)
 EMUL = tests/cpu/libfft_core_emul.so
 emul: $(EMUL)
 
-$(EMUL): tests/cpu/fft_core_emul.cpp datum_amd/csrc/ocean_fft_core.h
-	$(CXX) -O2 -std=c++14 -fPIC -shared -o $@ tests/cpu/fft_core_emul.cpp
+# (the layout walk is compiled in where the tests directory holds it: the library still builds for a tests directory without it)
+EMULSRC = tests/cpu/fft_core_emul.cpp $(wildcard tests/cpu/layout_emul.cpp)
+
+$(EMUL): $(EMULSRC) datum_amd/csrc/ocean_fft_core.h datum_amd/csrc/ocean_layout.h
+	$(CXX) -O2 -std=c++17 -fPIC -shared -o $@ $(EMULSRC)
 
 # stand-in for the Vulkan side of the external-memory handshake (GPU tests only)
 EXTMEM = tests/gpu/libextmem_helper.so

@@ -14,6 +14,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "ocean_layout.h"
 #include "ocean_kernels.hip"
 #include "ocean_gen.hip"
 #include "ocean_literal.hip"
@@ -164,6 +165,12 @@ namespace
 
   size_t plane(datum_ocean_ctx const *ctx) { return (size_t)ctx->N * ctx->N; }
 
+  // one cascade's block of the maps (ocean_layout.h: map_compact_a / map_compact_b are offsets into it)
+  char *map_block(datum_ocean_ctx const *ctx, int cascade)
+  {
+    return reinterpret_cast<char*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N);
+  }
+
   StepArgs make_args(datum_ocean_ctx *ctx, int ndt, float const *dt)
   {
     StepArgs a;
@@ -194,7 +201,7 @@ namespace
 
   bool maps_stream(int N, int cascades, bool half)
   {
-    return N >= 4096 || (N >= 1024 && (double)cascades * N * N * (half ? 44.0 : 52.0) > MAPS_RESIDENT_BYTES);
+    return N >= 4096 || (N >= 1024 && (double)cascades * N * N * ((half ? 20.0 : 28.0) + MAP_TEXEL_BYTES) > MAPS_RESIDENT_BYTES);
   }
 
   // Cascades per launch of the two passes (replaces the one dispatch per shader of ocean.cpp:769-789).  A handle whose working set is resident
@@ -489,23 +496,6 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  // the map layout's shape as shifts (ocean_pack_kernel, ocean_export_kernel: texel <- part number)
-  PackShape pack_shape(int N)
-  {
-    auto log2of = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-
-    int const B = band_cols(N), PW = map_patch_cols(N), PH = map_patch_rows(N);
-
-    PackShape sh;
-    sh.n2 = log2of(N);
-    sh.pw2 = log2of(PW);
-    sh.bp2 = log2of(B / PW);
-    sh.bandpatches2 = log2of((N / PH) * (B / PW));
-    sh.b2 = log2of(B);
-
-    return sh;
-  }
-
   // the pack of datum_ocean_pack_displacement / datum_ocean_farm_gather, on the handle's stream (arguments checked by the callers)
   int pack_into(datum_ocean_ctx *ctx, int format, void *payload_device, size_t need)
   {
@@ -585,7 +575,7 @@ namespace
       a.hx = ctx->litfields + P;
       a.hy = ctx->litfields + 2 * P;
       a.weights = ctx->litweights;
-      a.maps = reinterpret_cast<char*>(ctx->maps.get()) + (size_t)c * map_cascade_bytes(ctx->N);
+      a.maps = map_block(ctx, c);
       a.N = ctx->N;
       a.scale = ctx->casc[c].scale;
       a.choppiness = ctx->casc[c].choppiness;
@@ -907,7 +897,7 @@ int datum_ocean_map_layout(int resolution, int *group_cols, int *group_rows, int
   *group_cols = map_patch_cols(resolution);
   *group_rows = map_patch_rows(resolution);
   *band = band_cols(resolution);
-  *texel_bytes = 24;
+  *texel_bytes = MAP_TEXEL_BYTES;
 
   return DATUM_OCEAN_OK;
 }
@@ -1344,7 +1334,7 @@ int datum_ocean_gen(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, 
 
   GenArgs g;
   g.set = *set;
-  g.map = reinterpret_cast<float4 const*>(reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N));
+  g.map = reinterpret_cast<float4 const*>(map_block(ctx, cascade));
   g.vertices = (float*)vertices_device;
   gen_shape(g, ctx->N, sizex, sizey);
 
@@ -1807,14 +1797,14 @@ int datum_ocean_read_maps(datum_ocean_t ctx, int cascade, float *maps)
 
   size_t const P = plane(ctx);
 
-  // the device layout is the module's own (ocean_kernels.hip: map_compact_a / map_compact_b); hand out the reference's logical
+  // the device layout is the module's own (ocean_layout.h: map_compact_a / map_compact_b); hand out the reference's logical
   // image, [layer][y][x] RGBA32F with the .w channels zero (map.comp:79-80)
   size_t const bytes = map_cascade_bytes(ctx->N);
 
   std::vector<float> raw;
   try { raw.resize(bytes / sizeof(float)); } catch (...) { return fail(ctx, DATUM_OCEAN_ENOMEM, "datum_ocean_read_maps: out of host memory"); }
 
-  HIPCHECK(ctx, hipMemcpyAsync(raw.data(), reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(raw.data(), map_block(ctx, cascade), bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   int const N = ctx->N;
@@ -1994,7 +1984,7 @@ namespace
   {
     SurfaceArgs s;
     s.set = *set;
-    s.map = reinterpret_cast<float4 const*>(reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N));
+    s.map = reinterpret_cast<float4 const*>(map_block(ctx, cascade));
     s.foam = (ctx->foammode != DATUM_OCEAN_FOAM_OFF) ? ctx->foam.get() + (size_t)cascade * plane(ctx) : nullptr;
     s.points = static_cast<float2 const*>(points);
     s.samples = static_cast<float4*>(samples);
@@ -2074,16 +2064,11 @@ __global__ void __launch_bounds__(256) ocean_export_kernel(char const *maps, int
 
     if constexpr (LAYOUT)
     {
-      int const patch = (int)(r >> 4), j = (int)(r & 15);
+      ocean::MapPart const m = ocean::map_part(sh, r);
 
-      oa = (size_t)patch * ocean::MAP_PATCH_BYTES + j * 16;
-      ob = (size_t)patch * ocean::MAP_PATCH_BYTES + 256 + j * 8;
-
-      int const band = patch >> sh.bandpatches2, pp = patch & ((1 << sh.bandpatches2) - 1);
-      int const y = ((pp >> sh.bp2) << (4 - sh.pw2)) + (j >> sh.pw2);
-      int const x = (band << sh.b2) + ((pp & ((1 << sh.bp2) - 1)) << sh.pw2) + (j & ((1 << sh.pw2) - 1));
-
-      i = ((size_t)y << sh.n2) + x;
+      oa = m.a;
+      ob = m.b;
+      i = ((size_t)m.y << sh.n2) + m.x;
     }
     else
     {
@@ -2121,7 +2106,7 @@ int datum_ocean_export_maps(datum_ocean_t ctx, int cascade, void *device_dst, si
   size_t const P = plane(ctx);
   int const blocks = (int)((P + 255) / 256 < 4096 ? (P + 255) / 256 : 4096);
 
-  char const *block = reinterpret_cast<char const*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N);
+  char const *block = map_block(ctx, cascade);
 
   if (ctx->N <= 1024)
     hipLaunchKernelGGL(ocean_export_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, block, ctx->N, static_cast<float4*>(device_dst), pack_shape(ctx->N));

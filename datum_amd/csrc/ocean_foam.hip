@@ -17,6 +17,7 @@
 
 #pragma once
 
+#include "ocean_layout.h"
 #include "ocean_kernels.hip"
 
 namespace ocean

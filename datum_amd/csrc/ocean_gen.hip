@@ -17,7 +17,7 @@
 //   * the shading frame (gen.comp:101-120) uses v_rsq_f32 / v_exp_f32 / v_log_f32 and FMAs: errors are not amplified there;
 //   * sin / cos of the swell phase (up to 1e5..1e6 at the horizon) by the two-constant Cody-Waite step of sincos_phase;
 //   * texture(sampler2DArray) (gen.comp:113-114) is a manual bilinear REPEAT fetch from the module's own map layout
-//     (ocean_kernels.hip: map_compact_a / map_compact_b) in fp32 with float weights (lavapipe-style exact bilinear).  The texel index wraps
+//     (ocean_layout.h: map_compact_a / map_compact_b) in fp32 with float weights (lavapipe-style exact bilinear).  The texel index wraps
 //     through v_fract_f32 of coordinate / N (exact: N is a power of two), right for every float the oracle's 64-bit wrap
 //     is right for -- an int32 conversion saturates from |coordinate| = 2^31 (dist = 1e6 at wavescale < 2, N = 4096);
 //   * where a bilinear weight is exactly 0 along an axis (beyond |coordinate| = 2^23 texels, i.e. every ray above the
@@ -32,6 +32,7 @@
 
 #pragma once
 
+#include "ocean_layout.h"
 #include "ocean_kernels.hip"
 
 namespace ocean
@@ -63,7 +64,7 @@ namespace ocean
   {
     datum_ocean_set set;
     GenFrame frame;
-    float4 const *map;     // the cascade's displacement map, map_cascade_bytes(N) bytes (ocean_kernels.hip: map_compact_a / map_compact_b)
+    float4 const *map;     // the cascade's displacement map, map_cascade_bytes(N) bytes (ocean_layout.h: map_compact_a / map_compact_b)
     int N;
     int sizex;
     int sizey;
@@ -235,40 +236,6 @@ namespace ocean
 
     return { (v.x + q[0] * tt.x) + (uy * tt.z - uz * tt.y), (v.y + q[0] * tt.y) + (uz * tt.x - ux * tt.z), (v.z + q[0] * tt.z) + (ux * tt.y - uy * tt.x) };
   }
-
-  // BYTE offset of a texel column's / row's part of the map layout (ocean_kernels.hip); the two add up to the texel's
-  // displacement: part A of its patch, (dx, dy, dz, nx) -- whose part B, (ny, nz), lies at A + 256 - bcolumn(i) - brow(j).
-  //   PLAIN   N <= 1024: whole rows
-  //   BANDED  2048 and 4096: bands of band_cols(N) columns
-  enum GenLayout { GEN_PLAIN = 0, GEN_BANDED = 1 };
-
-  template<int LAYOUT> struct TexelIndex
-  {
-    int ln, lb, bmask;
-    int lpw, lph;            // log2 of the patch's columns and rows
-
-    __device__ __forceinline__ TexelIndex(int N) : ln(31 - __builtin_clz(N)), lb(31 - __builtin_clz(band_cols(N))), bmask(band_cols(N) - 1),
-                                                   lpw(31 - __builtin_clz(map_patch_cols(N))), lph(31 - __builtin_clz(map_patch_rows(N))) { }
-
-    __device__ __forceinline__ int column(int i) const
-    {
-      int const inband = ((i & bmask) >> lpw) * MAP_PATCH_BYTES + ((i & ((1 << lpw) - 1)) << 4);
-
-      if constexpr (LAYOUT == GEN_PLAIN)
-        return inband;
-      else
-        return (i >> lb) * (3 << (3 + ln + lb)) + inband;           // 24 N B bytes per band
-    }
-
-    __device__ __forceinline__ int row(int j) const
-    {
-      return (j >> lph) * (3 << (7 + lb - lpw)) + ((j & ((1 << lph) - 1)) << (4 + lpw));     // 384 B / PW bytes per patch row
-    }
-
-    // 8 * (the texel's index in its patch), column and row part
-    __device__ __forceinline__ int bcolumn(int i) const { return (i & ((1 << lpw) - 1)) << 3; }
-    __device__ __forceinline__ int brow(int j) const { return (j & ((1 << lph) - 1)) << (3 + lpw); }
-  };
 
   //|---------------------- the kernel ------------------------------------------
   // (One function, local arrays: with the three stages as functions over structs, or inside a loop over tiles, hipcc keeps
@@ -444,7 +411,7 @@ namespace ocean
         o00[ph][i] = r0 + c0; o10[ph][i] = wantx ? r0 + c1 : -256; o01[ph][i] = wanty ? r1 + c0 : -256; o11[ph][i] = (wantx && wanty) ? r1 + c1 : -256;
 
         int const bc0 = texel.bcolumn(i0), bc1 = texel.bcolumn(i1);
-        int const br0 = 256 - texel.brow(j0), br1 = 256 - texel.brow(j1);
+        int const br0 = MAP_PART_B - texel.brow(j0), br1 = MAP_PART_B - texel.brow(j1);
 
         q00[ph][i] = o00[ph][i] + br0 - bc0; q10[ph][i] = wantx ? o10[ph][i] + br0 - bc1 : -256; q01[ph][i] = wanty ? o01[ph][i] + br1 - bc0 : -256; q11[ph][i] = (wantx && wanty) ? o11[ph][i] + br1 - bc1 : -256;
 
@@ -595,11 +562,6 @@ namespace ocean
 
     OCEAN_STAMP_WHERE();
     OCEAN_STAMP(4);
-  }
-
-  inline GenLayout gen_layout(int N)
-  {
-    return (band_cols(N) != N) ? GEN_BANDED : GEN_PLAIN;
   }
 
   // everything but the set header, the map and the vertex buffer

@@ -15,9 +15,7 @@
 // 96 algorithmic bytes per point (bench.py's roofline.frac_on_survey_bytes) and the reference as
 // written moves 196.
 //
-// Work spectrum layout (private to these kernels): per cascade, 8 x 8 blocks of 16-byte values (C, D),
-// [y/8][x/8][y%8][x%8]: a row of a block is one 128-byte line; a column-pass wave reads whole blocks.  The largest grids
-// keep the columns one XCD works on at a time contiguous ([x/B][...]: blocked_at, band_cols), for the maps too (map_compact_patch).
+// The work spectrum between the two passes and the maps have layouts of the module's own (blocked_at, map_compact_a / _b): ocean_layout.h.
 // At 4096^2 the column pass's workgroups are persistent and walk their tiles; everything else is one work item per workgroup.
 //
 // Built with -ffp-contract=off: products and sums are rounded as written (the phase state is
@@ -31,6 +29,7 @@
 #include <type_traits>
 
 #include "ocean_fft_core.h"
+#include "ocean_layout.h"
 #include "../../include/datum_ocean_hip.h"
 
 namespace ocean
@@ -86,75 +85,6 @@ namespace ocean
   #define OCEAN_STAMP_WHERE() do { } while(0)
   #define OCEAN_WAIT_LOADS() do { } while(0)
 #endif
-
-  constexpr int SBR = 8, SBC = 8;
-
-  // columns per block, by the stored value's size.  The 8-byte values of the fp16-stored spectrum keep 8 columns (64-byte block rows): with 16 -- whole
-  // lines per row-pass store -- the row pass gains 6-14 us at 4096^2 and 2048^2 x 4 and the column pass, whose narrow tiles then take 16 bytes of
-  // every line they touch, loses as much or more (profiles/r06_spectrum_blocks.txt: 4096^2 with h0 as halves 5.2 -> 5.1 k grids/s)
-  __host__ __device__ __forceinline__ constexpr int spec_block_cols(bool half) { return half ? 8 : SBC; }
-
-  // Bands (large grids): the columns one XCD's column-pass workgroups work on at the same time are made contiguous in
-  // memory -- [x / B][rows][x % B] -- for the work spectrum and for the maps alike, so that what is read and written
-  // concurrently is a dense region instead of 2 KB pieces of rows 128 KB apart (4096^2).  B = band_cols(N), 0 = whole rows.
-  // measured (profiles/r02_large_grids.txt): 4096^2 B = 64 (32 CUs x 2-column tiles): column pass 240 -> 226 us, with the
-  // fp16-stored spectrum 202 -> 164 us; 2048^2 x 4 B = 128 (32 CUs x 4-column tiles): 181 -> 167 us; B = 512 at 4096^2: 270 us.
-  // With the maps in 2 x 2 patches at 4096^2 (round 3's layout): B = 64 184-195 us, B = 128 176-183 us, B = 256 192 us, B = 512 / none 220 us
-  __host__ __device__ __forceinline__ constexpr int band_cols(int N) { return (N >= 2048) ? 128 : N; }
-
-  // element index of grid point (y, x) in the blocked work spectrum: per band, blocks of SBR rows x SBC columns, row-major inside
-  __host__ __device__ __forceinline__ constexpr size_t blocked_at(int N, int y, int x, bool half = false)
-  {
-    int const B = band_cols(N);
-    int const BC = spec_block_cols(half);
-
-    return (size_t)(x / B) * N * B + ((size_t)(y / SBR) * (B / BC) + (x % B) / BC) * (SBR * BC) + (y % SBR) * BC + (x % BC);
-  }
-
-  template<int N, bool H16 = false>
-  __host__ __device__ __forceinline__ constexpr size_t blocked(int y, int x)
-  {
-    return blocked_at(N, y, x, H16);
-  }
-
-  // Displacement map layout (private to this module: in the reference the map is a VK_IMAGE_TILING_OPTIMAL 2-layer image whose
-  // only reader is ocean.gen's sampler, ocean.cpp:706, gen.comp:113-114; datum_ocean_read_maps / datum_ocean_export_maps hand out
-  // the logical [layer][y][x] RGBA32F image).
-  // 24 bytes per texel instead of 32 -- the two RGBA32F layers' .w channels are
-  // constant zero (map.comp:79-80) and nothing reads them (gen.comp:113-114 takes .xyz), yet they were a quarter of what the
-  // write-bound column pass stores.  Per cascade, bands as above; inside a band PATCHES of PW x PH = 16 texels, patch rows
-  // one after the other; a patch is 384 bytes = three 128-byte lines:
-  //     part A, 256 bytes: texel j = (y % PH) * PW + x % PW  ->  float4 (dx, dy, dz, nx)   at 16 j
-  //     part B, 128 bytes: texel j                            ->  float2 (ny, nz)           at 256 + 8 j
-  // PW = the column pass's tile width at that resolution (8 up to 256^2, 2 at 512^2, 4 at 1024^2 and 2048^2, 2 at 4096^2), so that the 16 texels of
-  // a patch are 16 neighbouring lanes of a column-pass wave: one 16-byte and one 8-byte store instruction per thread and slot
-  // write two whole lines and one whole line per patch -- no lane trades, no partial lines.  For ocean.gen a 4 x 4 patch holds
-  // the four corners of a bilinear fetch more often than a 4 x 1 group did.
-  constexpr int MAP_PATCH = 16;                   // texels per patch
-  constexpr int MAP_PATCH_BYTES = 384;
-
-  __host__ __device__ __forceinline__ constexpr int map_patch_cols(int N) { return N <= 256 ? 8 : (N == 512 ? 2 : (N <= 2048 ? 4 : 2)); }     // == ColCfg<N>::W (asserted there)
-  __host__ __device__ __forceinline__ constexpr int map_patch_rows(int N) { return MAP_PATCH / map_patch_cols(N); }
-
-  // bytes of one cascade's maps
-  __host__ __device__ __forceinline__ constexpr size_t map_cascade_bytes(int N) { return (size_t)N * N * 24; }
-
-  // byte offset of texel (x, y)'s part A inside its cascade's block; part B is map_compact_b(...)
-  __host__ __device__ __forceinline__ constexpr size_t map_compact_patch(int N, int y, int x)
-  {
-    int const B = band_cols(N);
-    int const PW = map_patch_cols(N), PH = map_patch_rows(N);
-
-    return (size_t)(x / B) * 24 * N * B + ((size_t)(y / PH) * (B / PW) + (x % B) / PW) * MAP_PATCH_BYTES;
-  }
-
-  __host__ __device__ __forceinline__ constexpr int map_compact_j(int N, int y, int x) { return (y % map_patch_rows(N)) * map_patch_cols(N) + x % map_patch_cols(N); }
-
-  __host__ __device__ __forceinline__ constexpr size_t map_compact_a(int N, int y, int x) { return map_compact_patch(N, y, x) + 16 * map_compact_j(N, y, x); }
-  __host__ __device__ __forceinline__ constexpr size_t map_compact_b(int N, int y, int x) { return map_compact_patch(N, y, x) + 256 + 8 * map_compact_j(N, y, x); }
-
-  // bytes from a texel's patch to the patch of the same column k * PH rows on
-  __host__ __device__ __forceinline__ constexpr int map_compact_patchrow_bytes(int N) { return (band_cols(N) / map_patch_cols(N)) * MAP_PATCH_BYTES; }
 
   //|---------------------- buffer addressing ----------------------------------
   // Global accesses whose addresses differ between a thread's slots only by a wave-uniform amount go through
@@ -545,6 +475,36 @@ namespace ocean
       __syncthreads();
   }
 
+  // the middle passes I = 1 ... NP - 2 of fft_lines, each between two exchanges
+  template<int N, int K, int W, int E_, bool WAVE, int I = 1>
+  __device__ __forceinline__ void fft_mid_phases(cf (&v)[K][E_], int t, cf *line, int linestride, cf const *midtab, typename LineTw<N, E_>::type const &w, bool active)
+  {
+    typedef LineFFT<N, W, E_> L;
+
+    if constexpr (I <= Plan<N, E_>::NP - 2)
+    {
+      if (active)
+      {
+        #pragma unroll
+        for(int k = 0; k < K; ++k)
+          L::template mid_load<I>(v[k], t, line + k * linestride, midtab, w);
+      }
+
+      exchange_sync<WAVE>();
+
+      if (active)
+      {
+        #pragma unroll
+        for(int k = 0; k < K; ++k)
+          L::template mid_store<I>(v[k], t, line + k * linestride);
+      }
+
+      exchange_sync<WAVE>();
+
+      fft_mid_phases<N, K, W, E_, WAVE, I + 1>(v, t, line, linestride, midtab, w, active);
+    }
+  }
+
   template<int N, int K, int W, int E_, typename Hook = NoHook>
   __device__ __forceinline__ void fft_lines(cf (&v)[K][E_], int t, cf *line, int linestride, cf const *midtab, typename LineTw<N, E_>::type const &w, bool active, Hook before_last = Hook())
   {
@@ -564,89 +524,7 @@ namespace ocean
 
     exchange_sync<WAVE>();
 
-    if (Plan<N, E_>::NP >= 3)
-    {
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_load<1>(v[k], t, line + k * linestride, midtab, w);
-      }
-
-      exchange_sync<WAVE>();
-
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_store<1>(v[k], t, line + k * linestride);
-      }
-
-      exchange_sync<WAVE>();
-    }
-
-    if (Plan<N, E_>::NP >= 4)
-    {
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_load<2>(v[k], t, line + k * linestride, midtab, w);
-      }
-
-      exchange_sync<WAVE>();
-
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_store<2>(v[k], t, line + k * linestride);
-      }
-
-      exchange_sync<WAVE>();
-    }
-
-    if (Plan<N, E_>::NP >= 5)
-    {
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_load<3>(v[k], t, line + k * linestride, midtab, w);
-      }
-
-      exchange_sync<WAVE>();
-
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_store<3>(v[k], t, line + k * linestride);
-      }
-
-      exchange_sync<WAVE>();
-    }
-
-    if (Plan<N, E_>::NP >= 6)
-    {
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_load<4>(v[k], t, line + k * linestride, midtab, w);
-      }
-
-      exchange_sync<WAVE>();
-
-      if (active)
-      {
-        #pragma unroll
-        for(int k = 0; k < K; ++k)
-          L::template mid_store<4>(v[k], t, line + k * linestride);
-      }
-
-      exchange_sync<WAVE>();
-    }
+    fft_mid_phases<N, K, W, E_, WAVE>(v, t, line, linestride, midtab, w, active);
 
     before_last();
 
@@ -789,7 +667,7 @@ namespace ocean
     for(int i = threadIdx.x; i < L::MIDTAB; i += C::THREADS)
       midtab[i] = L::midtab_entry(a.tw, i);
 
-    // work items = (cascade, group of PAIRS row pairs), cascade-major; workgroup b takes items b, b + gridDim.x, ...
+    // work items = (cascade, group of PAIRS row pairs), cascade-major; workgroup b takes item b and no other.
     // Neighbouring pairs read each other's rows as ocean.sim's mirror rows: item -> group deals contiguous bands of
     // groups to the workgroups of one XCD (b % 8)
     constexpr int G = C::GROUPS;
@@ -1116,7 +994,7 @@ namespace ocean
     static constexpr int WCAP = WRAW > 8 ? 8 : (WRAW < 1 ? 1 : WRAW);
     static constexpr int W = WCAP < WFIT ? WCAP : WFIT;                 // columns per workgroup, one per thread group
     static constexpr int THREADS = W * T;
-    static constexpr int MIN_WAVES = (N == 2048) ? 4 : 1;        // per SIMD, for __launch_bounds__: two 512-thread tiles per CU at 2048^2 (128 registers, 20 bytes of spill)
+    static constexpr int MIN_WAVES = (N == 2048) ? 4 : 1;        // per SIMD, for __launch_bounds__: two 512-thread tiles per CU at 2048^2 (126 registers, no scratch: DESIGN 5.5)
     static constexpr int CS = LineFFT<N, W, E>::LINE;                      // elements per column line
     static constexpr int TILES = N / W;
 
@@ -1492,15 +1370,6 @@ namespace ocean
   // write 12 or 8 bytes each into runs of PW x (lanes / 16) texels per row.  Round 5: 39.7 -> 18.5 us for xyz32 at 1024^2 x 4 (6.35 TB/s), 169 -> 97 us at x 16
   // (up to round 4 a thread read the four texels of a patch row -- every line fetched by two far-apart waves -- and wrote 48 bytes
   // at a 48-byte stride: tools/dbg/pack_time.py).
-  struct PackShape
-  {
-    int n2;                 // log2 N
-    int pw2;                // log2 of a patch's width
-    int bp2;                // log2 of the patches in a row of patches of one band (B / PW)
-    int bandpatches2;       // log2 of the patches per band ((N / PH) * (B / PW))
-    int b2;                 // log2 of the band's columns
-  };
-
   template<bool HALF>
   __global__ void __launch_bounds__(256) ocean_pack_kernel(float4 const *maps, int N, int cascades, void *payload, PackShape sh)
   {
@@ -1523,7 +1392,7 @@ namespace ocean
         {
           size_t const c = q >> (2 * sh.n2), r = q & (plane - 1);
 
-          v[k] = *reinterpret_cast<float4 const*>(reinterpret_cast<char const*>(maps) + c * map_cascade_bytes(N) + (r >> 4) * MAP_PATCH_BYTES + (r & 15) * 16);
+          v[k] = *reinterpret_cast<float4 const*>(map_part_a(reinterpret_cast<char const*>(maps) + c * map_cascade_bytes(N), r));
         }
       }
 
@@ -1536,13 +1405,9 @@ namespace ocean
         {
           size_t const c = q >> (2 * sh.n2), r = q & (plane - 1);
 
-          // the texel of part A number j of patch P (map_compact_patch / map_compact_j read backwards)
-          int const P = (int)(r >> 4), j = (int)(r & 15);
-          int const band = P >> sh.bandpatches2, pp = P & ((1 << sh.bandpatches2) - 1);
-          int const y = ((pp >> sh.bp2) << (4 - sh.pw2)) + (j >> sh.pw2);
-          int const x = (band << sh.b2) + ((pp & ((1 << sh.bp2) - 1)) << sh.pw2) + (j & ((1 << sh.pw2) - 1));
+          MapPart const m = map_part(sh, r);       // the texel of part A number r
 
-          size_t const at = c * plane + ((size_t)y << sh.n2) + x;
+          size_t const at = c * plane + ((size_t)m.y << sh.n2) + m.x;
 
           if constexpr (HALF)
             static_cast<half4_*>(payload)[at] = half4_{ (_Float16)v[k].x, (_Float16)v[k].y, (_Float16)v[k].z, (_Float16)0.0f };

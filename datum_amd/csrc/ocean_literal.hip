@@ -18,6 +18,7 @@
 
 #pragma once
 
+#include "ocean_layout.h"
 #include "ocean_kernels.hip"
 
 namespace ocean

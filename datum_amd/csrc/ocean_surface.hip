@@ -15,6 +15,7 @@
 
 #pragma once
 
+#include "ocean_layout.h"
 #include "ocean_gen.hip"
 
 namespace ocean
@@ -154,7 +155,7 @@ namespace ocean
     SurfaceTexel<LAYOUT> const t(texel, f, p.scale, nmask, px, py);
 
     int const bc0 = texel.bcolumn(t.i0), bc1 = texel.bcolumn(t.i1);
-    int const br0 = 256 - texel.brow(t.j0), br1 = 256 - texel.brow(t.j1);
+    int const br0 = MAP_PART_B - texel.brow(t.j0), br1 = MAP_PART_B - texel.brow(t.j1);
 
     float2 const b00 = buf_load_f32x2(rmap, t.o00 + br0 - bc0, 0);
     float2 const b10 = buf_load_f32x2(rmap, t.wantx ? t.o10 + br0 - bc1 : -256, 0);

@@ -1,4 +1,4 @@
-"""Short seeded runs of the differential fuzzers of tools/dbg/ (their long runs are in profiles/r04_fuzz.txt): random cases, random sequences of
+"""Short seeded runs of the differential fuzzers of tools/dbg/ (their long runs are in profiles/r06_fuzz_raw.txt, earlier ones in r05_fuzz_raw.txt and r04_fuzz.txt): random cases, random sequences of
 C-ABI calls against a host model of the handle's state, random sequences of calls on the C++ host shim.  Each exits non-zero on the first mismatch."""
 
 import os

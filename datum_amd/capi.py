@@ -111,6 +111,8 @@ SYMBOLS = {
     "datum_ocean_set_literal_transform": (I, [P, I]),
     "datum_ocean_export_maps": (I, [P, I, P, ctypes.c_size_t]),
     "datum_ocean_farm_stream_flags": (I, [P, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]),
+    "datum_ocean_set_phase_writeback": (I, [P, I]),
+    "datum_ocean_phase_writeback": (I, [P, ctypes.POINTER(I)]),
     "datum_ocean_set_cascade_group": (I, [P, I]),
     "datum_ocean_cascade_group": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I)]),
     "datum_ocean_set_foam": (I, [P, I]),
@@ -465,6 +467,17 @@ class Ocean:
         g, n = I(), I()
         self._check(self.lib.datum_ocean_cascade_group(self.h, ctypes.byref(g), ctypes.byref(n)))
         return g.value, n.value
+
+    def set_phase_writeback(self, every):
+        """the row pass stores the phase once per `every` steps' worth of dt's: 1 = every row pass, 0 = the module's choice; results do not
+        depend on it (datum_ocean_set_phase_writeback)"""
+        self._check(self.lib.datum_ocean_set_phase_writeback(self.h, int(every)))
+
+    def phase_writeback(self):
+        """the write-back interval in use"""
+        e = I(0)
+        self._check(self.lib.datum_ocean_phase_writeback(self.h, ctypes.byref(e)))
+        return e.value
 
     def set_map_store_policy(self, policy):
         """how the column pass stores the maps: "auto" (default), "written through", "streamed" (datum_ocean_set_map_store_policy)"""

@@ -15,6 +15,7 @@
 #include <hip/hip_ext.h>
 
 #include "ocean_layout.h"
+#include "ocean_writeback.h"
 #include "ocean_kernels.hip"
 #include "ocean_gen.hip"
 #include "ocean_literal.hip"
@@ -102,7 +103,10 @@ struct datum_ocean_ctx
   CascadeConst casc[DATUM_OCEAN_MAX_CASCADES];
   CascadeState cstate[DATUM_OCEAN_MAX_CASCADES];
 
-  std::vector<float> pending;         // queued update_ocean dt's
+  std::vector<float> pending;         // queued update_ocean dt's no kernel has seen yet
+  PhaseWriteback writeback;           // ... and those the last row pass applied without storing the phase (every cascade alike: each launch of a
+                                      // displace call takes the same list)
+  int writebackevery = 0;             // datum_ocean_set_phase_writeback; 0 = the module's choice (plan_step)
 
   // foam (datum_ocean_set_foam): one fp32 plane per cascade, computed by displace after the column pass
   int foammode = DATUM_OCEAN_FOAM_OFF;
@@ -171,7 +175,7 @@ namespace
     return reinterpret_cast<char*>(ctx->maps.get()) + (size_t)cascade * map_cascade_bytes(ctx->N);
   }
 
-  StepArgs make_args(datum_ocean_ctx *ctx, int ndt, float const *dt)
+  StepArgs make_args(datum_ocean_ctx *ctx, int ndt, float const *dt, bool storephase = true)
   {
     StepArgs a;
     a.h0 = ctx->h0;
@@ -182,6 +186,7 @@ namespace
     a.tw = ctx->tw;
     a.omega = ctx->omega;
     a.ndt = ndt;
+    a.storephase = storephase ? 1 : 0;
     a.cascades = ctx->cascades;
     a.first = 0;
 
@@ -223,7 +228,17 @@ namespace
     int group = 0;                    // cascades per launch of either pass
     int groups = 0;                   // launches per pass
     bool streamed = false;            // the maps streamed past the Infinity Cache
+    int writeback = 1;                // the row pass stores the phase once its dt list holds this many (ocean_writeback.h)
   };
+
+  // The phase written back once per this many steps' worth of dt's unless the caller sets an interval (datum_ocean_set_phase_writeback).
+  // Measured, parent build and intervals 1 / 2 / 4 / 8 alternated on one device (profiles/phase_writeback_ab.txt, phase_writeback_kernel_trace.txt):
+  // 1024^2 x 4 fp32 82.8-83.0 k grids/s without (interval 1: 82.8-83.1 k) against 84.5-84.7 / 85.0-85.5 / 85.4-85.8 k, its row pass 22.64-22.66 us
+  // against 21.75-21.78 / 21.33-21.45 / 21.17-21.25 us over 2100 launches; 1024^2 x 16 81.5 k against 83.1 / 83.8-83.9 / 83.8-84.1 k.  The
+  // longest interval wins where the row pass runs at its memory path's rate: the re-applied dt's (4.5 on average at 8) hide under it.  At
+  // 4096^2 with h0 as halves, where a workgroup's arithmetic is exposed, one trace each had 4 ahead of 8 (row pass 79.8 ->
+  // 72.4 against 74.3 us) and the step equal within the device's drift (5.8-6.1 k both, 5.3-5.9 k without): not resolved, one value for all sizes.
+  constexpr int PHASE_WRITEBACK_EVERY = MAX_PENDING;
 
   StepPlan plan_step(datum_ocean_ctx const *ctx)
   {
@@ -273,6 +288,8 @@ namespace
 
     p.row = &ctx->kernels.row[format][wild];
     p.col = &ctx->kernels.col[ctx->half][p.streamed];
+
+    p.writeback = ctx->writebackevery > 0 ? ctx->writebackevery : PHASE_WRITEBACK_EVERY;
 
     return p;
   }
@@ -386,12 +403,37 @@ namespace
     return true;
   }
 
-  // flush queued updates that do not fit into one displace call
+  // Store the phase the handle stands at: the dt's the last row pass applied without storing, through the phase-only kernel (the same
+  // roundings).  Before anything reads the stored phase, replaces it, or changes what the retained dt's mean (a cascade's dispersion table).
+  int flush_retained(datum_ocean_ctx *ctx)
+  {
+    if (ctx->writeback.retained == 0)
+      return DATUM_OCEAN_OK;
+
+    int rc = ensure_omega(ctx);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    PhaseWriteback::Launch const l = ctx->writeback.repeat();
+
+    StepArgs a = make_args(ctx, l.ndt, l.dt);
+
+    hipLaunchKernelGGL(ocean_advance_kernel, dim3(1024, ctx->cascades), dim3(256), 0, ctx->stream, a, ctx->N);
+    HIPCHECK(ctx, hipGetLastError());
+
+    ctx->writeback.clear();
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // flush queued updates that do not fit into one displace call (behind the retained ones, which come first in time)
   int flush_pending(datum_ocean_ctx *ctx, size_t keep)
   {
     if (ctx->pending.size() > keep)
     {
-      int rc = ensure_omega(ctx);
+      int rc = flush_retained(ctx);
+      if (rc == DATUM_OCEAN_OK)
+        rc = ensure_omega(ctx);
       if (rc != DATUM_OCEAN_OK)
         return rc;
     }
@@ -421,6 +463,14 @@ namespace
     }
 
     return DATUM_OCEAN_OK;
+  }
+
+  // the stored phase brought up to every update the handle has been given: retained and queued
+  int flush_phase(datum_ocean_ctx *ctx)
+  {
+    int rc = flush_retained(ctx);
+
+    return (rc == DATUM_OCEAN_OK) ? flush_pending(ctx, 0) : rc;
   }
 
   // fp16 work spectrum: the power of two that brings the largest possible row sum under the largest half.
@@ -913,11 +963,12 @@ int datum_ocean_set_cascade(datum_ocean_t ctx, int cascade, float wavescale, flo
   if (!(wavescale > 0))
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_cascade: wavescale must be positive");
 
-  // queued updates were issued under the old wavescale: apply them first
-  if (wavescale != ctx->casc[cascade].wavescale && !ctx->pending.empty())
+  // queued updates, and those a row pass applied without storing the phase, were issued under the old wavescale: apply them first, while
+  // the dispersion table is still the old one
+  if (wavescale != ctx->casc[cascade].wavescale && (!ctx->pending.empty() || ctx->writeback.retained > 0))
   {
     HIPCHECK(ctx, hipSetDevice(ctx->device));
-    int rc = flush_pending(ctx, 0);
+    int rc = flush_phase(ctx);
     if (rc != DATUM_OCEAN_OK)
       return rc;
   }
@@ -979,9 +1030,9 @@ int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, fl
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // the new state replaces the old one: updates queued against the old state are applied first so that
+  // the new state replaces the old one: updates queued against the old state (or applied to it and not stored) are applied first so that
   // the other cascades keep them
-  int rc = flush_pending(ctx, 0);
+  int rc = flush_phase(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -1089,9 +1140,14 @@ int datum_ocean_rebuild_height(datum_ocean_t ctx, int cascade, float wavescale, 
   ctx->cstate[cascade].new_height();
   HIPCHECK(ctx, hipGetLastError());
 
-  // a cascade without a state gets one with phase zero -- its foam accumulator is not reset (include/datum_ocean_hip.h)
+  // a cascade without a state gets one with phase zero -- its foam accumulator is not reset (include/datum_ocean_hip.h).  (Nothing is
+  // retained while a cascade has no state, displace refuses: the flush says so where the phase is replaced.)
   if (!ctx->cstate[cascade].uploaded)
   {
+    rc = flush_retained(ctx);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
     HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * P, 0, P * sizeof(float), ctx->stream));
     ctx->cstate[cascade].new_state(false);
   }
@@ -1127,7 +1183,7 @@ int datum_ocean_read_state(datum_ocean_t ctx, int cascade, float *phase)
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  int rc = flush_pending(ctx, 0);
+  int rc = flush_phase(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -1160,7 +1216,7 @@ int datum_ocean_park_state(datum_ocean_t ctx, int cascade, void *device_dst, siz
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  int rc = flush_pending(ctx, 0);
+  int rc = flush_phase(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -1187,8 +1243,8 @@ int datum_ocean_resume_state(datum_ocean_t ctx, int cascade, void const *device_
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // updates queued against the state that is being replaced are applied first (the other cascades keep them)
-  int rc = flush_pending(ctx, 0);
+  // updates queued against the state that is being replaced, or applied to it and not stored, are applied first (the other cascades keep them)
+  int rc = flush_phase(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -1236,12 +1292,20 @@ int datum_ocean_displace(datum_ocean_t ctx)
 
   int rc = DATUM_OCEAN_OK;
 
-  if (!ctx->pending.empty())
+  // What the row pass cannot take goes through the phase-only kernel first, which stores: everything in the literal mode (its dispatches
+  // read the stored phase) and where a queued dt or a phase is outside the fused advance's range; otherwise the oldest of more than
+  // MAX_PENDING -- the retained dt's, which the row pass would have to apply in front of the queued ones, first
+  if (ctx->literal)
+    rc = flush_phase(ctx);
+  else if (!ctx->pending.empty())
   {
     rc = ensure_omega(ctx);
 
     if (rc == DATUM_OCEAN_OK)
-      rc = flush_pending(ctx, (fusable(ctx) && !ctx->literal) ? MAX_PENDING : 0);
+      rc = fusable(ctx) ? flush_pending(ctx, MAX_PENDING) : flush_phase(ctx);
+
+    if (rc == DATUM_OCEAN_OK && !ctx->writeback.fits((int)ctx->pending.size()))
+      rc = flush_retained(ctx);
   }
 
   if (rc != DATUM_OCEAN_OK)
@@ -1267,7 +1331,10 @@ int datum_ocean_displace(datum_ocean_t ctx)
   if (prof && plan.groups != ctx->profgroups)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_displace: the cascade groups changed while profiling (its samples are per group)");
 
-  StepArgs a = make_args(ctx, (int)ctx->pending.size(), ctx->pending.data());
+  // the retained dt's once more, then the queued ones; stored, or retained for the next row pass (ocean_writeback.h)
+  PhaseWriteback::Launch const step = ctx->writeback.step(ctx->pending.data(), (int)ctx->pending.size(), plan.writeback);
+
+  StepArgs a = make_args(ctx, step.ndt, step.dt, step.store);
   ctx->pending.clear();
 
   bool const foam = ctx->foammode != DATUM_OCEAN_FOAM_OFF;
@@ -2235,6 +2302,33 @@ int datum_ocean_map_store_policy(datum_ocean_t ctx, int *policy, int *streamed)
   return DATUM_OCEAN_OK;
 }
 
+int datum_ocean_set_phase_writeback(datum_ocean_t ctx, int every)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_phase_writeback: null handle");
+
+  if (every < 0 || every > MAX_PENDING)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_phase_writeback: the interval is 1 ... 8 row passes, or 0 for the module's choice");
+
+  if (ctx->profiling)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_phase_writeback: a profile is open (its row-pass samples are with the interval it began with)");
+
+  // (dt's retained under the old interval need no flush: the next row pass takes them and stores if the new interval says so)
+  ctx->writebackevery = every;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_phase_writeback(datum_ocean_t ctx, int *every)
+{
+  if (!ctx || !every)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_phase_writeback: null argument");
+
+  *every = plan_step(ctx).writeback;
+
+  return DATUM_OCEAN_OK;
+}
+
 int datum_ocean_abi_version(void)
 {
   return DATUM_OCEAN_ABI_VERSION;
@@ -2577,7 +2671,7 @@ int datum_ocean_debug_sim(datum_ocean_t ctx, int cascade, float *h, float *hx, f
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  int rc = flush_pending(ctx, 0);
+  int rc = flush_phase(ctx);
   if (rc == DATUM_OCEAN_OK)
     rc = ensure_scratch(ctx);
   if (rc != DATUM_OCEAN_OK)
@@ -2623,14 +2717,16 @@ int datum_ocean_debug_rowpass(datum_ocean_t ctx, int cascade, float *c, float *d
   size_t const P = plane(ctx);
 
   // The work spectrum belongs to a launch, not to a cascade (slot cascade - first of the group: ocean_kernels.hip), and the last displace may
-  // have left another cascade's values in the slot: the row pass of this one cascade once more -- no update pending, so the phase is neither
-  // advanced nor stored and the values are those of the last displace -- into slot 0
+  // have left another cascade's values in the slot: the row pass of this one cascade once more -- with the dt's the last displace applied and
+  // did not store, if any, and no queued one, so the phase is not stored and the values are those of the last displace -- into slot 0
   rc = size_spectrum_scale(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
   {
-    StepArgs a = make_args(ctx, 0, nullptr);
+    PhaseWriteback::Launch const again = ctx->writeback.repeat();
+
+    StepArgs a = make_args(ctx, again.ndt, again.dt, false);
     a.first = cascade;
     a.cascades = 1;
 
@@ -2658,6 +2754,11 @@ int datum_ocean_profile_begin(datum_ocean_t ctx, int max_steps, int stride)
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_profile_begin: the handle is in the literal mode, whose dispatches are not sampled");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // (the sampled row passes start at the beginning of a write-back interval, whatever came before)
+  int rc = flush_retained(ctx);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   int const groups = plan_step(ctx).groups;
 

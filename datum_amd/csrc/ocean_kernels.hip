@@ -30,12 +30,11 @@
 
 #include "ocean_fft_core.h"
 #include "ocean_layout.h"
+#include "ocean_writeback.h"
 #include "../../include/datum_ocean_hip.h"
 
 namespace ocean
 {
-  constexpr int MAX_PENDING = 8;
-
   typedef float4 cd;    // (C.re, C.im, D.re, D.im) of one grid point: the two packed fields of the work spectrum
 
   // the same four numbers as IEEE halves, 8 bytes (BASELINE.json configs[4]: spectrum stored fp16, arithmetic fp32)
@@ -65,7 +64,8 @@ namespace ocean
     float4 *maps;        // [cascade][2*N*N]     displacementmap, 2 layers, 24-byte texels in patches (map_compact_a / map_compact_b)
     cf const *tw;        // [N]                  exp(+2 pi i k / N)
     float const *omega;  // [cascade][(N/2+1)^2] dispersion(k) by (|m - N/2|, |n - N/2|)
-    int ndt;
+    int ndt;             // dt[0 .. ndt) are applied, in order, to the phase as it is stored ...
+    int storephase;      // ... and the row pass stores the result only under this flag (launch-uniform; ocean_writeback.h).  The phase-only kernel always stores
     int cascades;        // cascades THIS launch works on ...
     int first;           // ... starting with this one (the two passes are launched per group of cascades: ocean_capi, plan_step)
     float dt[MAX_PENDING];
@@ -838,10 +838,14 @@ namespace ocean
           }
         }
 
-        #pragma unroll
-        for(int s = 0; s < E; ++s)
+        // (not on every step: a row pass that does not store is handed the same dt's again by the next one, ocean_writeback.h)
+        if (a.storephase)
         {
-          buf_store_f32_aux<PHASE_STORE_AUX>(ph[s], rphase, (y * N + t) * 4, T * s * 4);
+          #pragma unroll
+          for(int s = 0; s < E; ++s)
+          {
+            buf_store_f32_aux<PHASE_STORE_AUX>(ph[s], rphase, (y * N + t) * 4, T * s * 4);
+          }
         }
       }
 

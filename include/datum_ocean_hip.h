@@ -46,7 +46,8 @@ extern "C" {
  *   9  the Jacobian foam plane: datum_ocean_set_foam, datum_ocean_set_foam_params, datum_ocean_reset_foam, datum_ocean_bind_foam,
  *      datum_ocean_foam_device, datum_ocean_read_foam, datum_ocean_upload_height.
  *      Later added at 9 without a bump (nothing changed, entry points were only added): the surface queries datum_ocean_sample_surface and
- *      datum_ocean_read_surface.  A consumer that needs them detects them by symbol (dlsym), not by the version */
+ *      datum_ocean_read_surface; then the phase write-back interval, datum_ocean_set_phase_writeback and datum_ocean_phase_writeback.  A consumer
+ *      that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
 
@@ -173,6 +174,21 @@ int datum_ocean_cascade_group(datum_ocean_t ctx, int *cascades_per_launch, int *
 int datum_ocean_set_map_store_policy(datum_ocean_t ctx, int policy);
 int datum_ocean_map_store_policy(datum_ocean_t ctx, int *policy, int *streamed);
 
+/* How often the row pass writes the advanced phase back (added at ABI 9 without a bump: both entry points exist from the library build that
+ * has the lazy write-back on; a consumer detects them by symbol).  datum_ocean_update only queues dt and the row pass of the next
+ * datum_ocean_displace applies it to the phase it loads.  Nothing but the next row pass reads what it would store, so it stores only once
+ * its list of applied dt's has reached `every` (1 ... 8; 1 = every row pass that advances, the behaviour of earlier builds; 0 = the
+ * module's choice, the default) and is otherwise handed the same dt's again, in front of the newer ones: the same instructions on the same
+ * stored value, so every map, every foam value and every phase a caller can obtain is bit for bit what `every` = 1 gives.
+ * WHAT A CALLER MAY ASSUME: the device's phase array is private to the module, and every call that returns, copies, replaces or
+ * re-interprets the phase brings it up to date first -- datum_ocean_read_state, datum_ocean_park_state / datum_ocean_resume_state,
+ * datum_ocean_upload_state, datum_ocean_rebuild_height for a cascade without a state, datum_ocean_set_cascade with a new wavescale (under the old
+ * dispersion), datum_ocean_debug_sim, and displace in the literal mode.  The value they see is the one the every-step path would hold.
+ * DATUM_OCEAN_ESTATE while a profile is open (its samples are with the interval it began with; datum_ocean_profile_begin starts at the
+ * beginning of an interval).  The getter reports the interval in use. */
+int datum_ocean_set_phase_writeback(datum_ocean_t ctx, int every);
+int datum_ocean_phase_writeback(datum_ocean_t ctx, int *every);
+
 int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, float const *phase);
 int datum_ocean_read_state(datum_ocean_t ctx, int cascade, float *phase);
 
@@ -205,7 +221,8 @@ int datum_ocean_read_height(datum_ocean_t ctx, int cascade, float *h0);
 
 /* update_ocean's phase advance (ocean.cpp:223-233) for every cascade:
  * phase = fmod(phase + dispersion(k) * dt, 2 pi), in fp32, in call order.  It is applied on the device,
- * fused into the next datum_ocean_displace (bit-identical to applying each dt in turn). */
+ * fused into the next datum_ocean_displace (bit-identical to applying each dt in turn; when the result is stored:
+ * datum_ocean_set_phase_writeback). */
 int datum_ocean_update(datum_ocean_t ctx, float dt);
 
 /* ocean.sim -> ocean.fftx -> ocean.ffty -> ocean.map for every cascade (ocean.cpp:769-789), as two fused

@@ -395,7 +395,7 @@ namespace
 
       for(float dt : ctx->pending)
       {
-        if (!(dt >= 0.0f) || !(ctx->cstate[c].omegamax * dt < 6.0f))
+        if (!dt_fusable(dt, ctx->cstate[c].omegamax))
           return false;
       }
     }
@@ -448,7 +448,7 @@ namespace
       // fused fast path must never see
       for(int i = 0; i < n; ++i)
       {
-        if (!(ctx->pending[i] >= 0.0f))
+        if (!dt_keeps_range(ctx->pending[i]))
         {
           for(int c = 0; c < ctx->cascades; ++c)
             ctx->cstate[c].wild = true;

@@ -30,6 +30,7 @@
 
 #include "ocean_fft_core.h"
 #include "ocean_layout.h"
+#include "ocean_phase.h"
 #include "ocean_writeback.h"
 #include "../../include/datum_ocean_hip.h"
 
@@ -215,7 +216,7 @@ namespace ocean
     {
       float const p = phase[i];
 
-      bad |= !(p >= 0.0f && p < 6.2831855f);
+      bad |= !phase_in_range(p);
     }
 
     if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0)
@@ -232,47 +233,15 @@ namespace ocean
     return table[i * (N / 2 + 1) + j];
   }
 
-  // fmod(phase + w*dt, 2 pi) of ocean.cpp:231, any operands (phase-only kernel).  fmod is exact.
-  __device__ __forceinline__ float advance_phase(float phase, float wdt)
-  {
-    return fmodf(phase + wdt, 6.2831855f);
-  }
-
-  // (the fused row pass is given 0 <= phase < 2 pi and 0 <= w*dt < 2 pi -- the host checks both and otherwise runs the phase-only
-  // kernel first: then 0 <= a < 4 pi and fmod(a, 2 pi) is a or a - 2 pi, the subtraction being exact (Sterbenz), bit-identical to fmod's:
-  // the row pass's packed select)
+  // (update_ocean's advance, general and fused, and the range the fused one needs: ocean_phase.h)
 
   //|---------------------- ocean.sim -----------------------------------------
 
-  // sin and cos of the phase (sim.comp:61-62).  update_ocean keeps the phase in [0, 2 pi), so the argument
-  // reduction is a two-constant Cody-Waite step to [-pi/4, pi/4] followed by the Cephes single-precision
-  // minimax polynomials: about 1 ulp there (measured against float64 in tests), at a quarter of the
-  // instructions and registers of the all-range libm path.  Arguments far outside (|x| >> 1e4) lose accuracy
-  // gradually, as GLSL's own sin/cos do.
-  __device__ __forceinline__ void sincos_phase(float x, float *sin_out, float *cos_out)
-  {
-    float k = rintf(x * 0.636619772367581343f);                 // x * 2/pi
-
-    float r = fmaf(k, -1.57079637050628662109375f, x);          // pi/2 head
-    r = fmaf(k, 4.37113900018624283e-8f, r);                    // pi/2 tail
-
-    float z = r * r;
-
-    float sp = fmaf(fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * r, r);
-    float cp = fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f), z * z, fmaf(z, -0.5f, 1.0f));
-
-    int q = (int)k;
-
-    float s = (q & 1) ? cp : sp;
-    float c = (q & 1) ? sp : cp;
-
-    *sin_out = (q & 2) ? -s : s;
-    *cos_out = ((q + 1) & 2) ? -c : c;
-  }
+  // (sin and cos of any phase, sincos_phase and its packed form sincos_phase_pair_poly: ocean_phase.h)
 
   // The row pass's sin / cos of ONE phase: the hardware's v_sin_f32 / v_cos_f32 of phase / 2 pi (what a
   // Vulkan driver makes of the shader's sin() and cos(), sim.comp:61-62, on this GPU: |error| <= 4.8e-7 for phases in [0, 2 pi),
-  // tools/dbg/hwsin.hip) or sincos_phase above
+  // tools/dbg/hwsin.hip) or sincos_phase
   template<bool WILD> __device__ __forceinline__ void sincos_row(float x, float *sin_out, float *cos_out);
 
   // one point of data/ocean.sim.comp:52-66: h~ from h0(k), h0 at the mirror index and the phase, evaluated as
@@ -318,36 +287,7 @@ namespace ocean
   // slots are taken in pairs (s, s + 1).  With -ffp-contract=off every product and sum is rounded as the scalar form rounds
   // it (the phase state stays bit-identical to update_ocean's).  A real factor that belongs to ONE slot of a pair enters
   // the complex operations through the half-select modifiers (broadcast of one half), not through a splat.
-  typedef float f2_ __attribute__((ext_vector_type(2)));
-
-  __device__ __forceinline__ f2_ pfma2(f2_ a, f2_ b, f2_ c) { return __builtin_elementwise_fma(a, b, c); }
-
-  // sincos_phase of two arguments: the same reduction and polynomials, packed
-  __device__ __forceinline__ void sincos_phase_pair_poly(f2_ x, f2_ &sn, f2_ &cs)
-  {
-    f2_ const t = x * 0.636619772367581343f;                            // x * 2/pi
-    f2_ const k = { __builtin_rintf(t.x), __builtin_rintf(t.y) };
-
-    f2_ r = pfma2(k, f2_{ -1.57079637050628662109375f, -1.57079637050628662109375f }, x);       // pi/2 head
-    r = pfma2(k, f2_{ 4.37113900018624283e-8f, 4.37113900018624283e-8f }, r);                    // pi/2 tail
-
-    f2_ const z = r * r;
-
-    f2_ const sp = pfma2(pfma2(pfma2(f2_{ -1.9515295891e-4f, -1.9515295891e-4f }, z, f2_{ 8.3321608736e-3f, 8.3321608736e-3f }), z, f2_{ -1.6666654611e-1f, -1.6666654611e-1f }), z * r, r);
-    f2_ const cp = pfma2(pfma2(pfma2(f2_{ 2.443315711809948e-5f, 2.443315711809948e-5f }, z, f2_{ -1.388731625493765e-3f, -1.388731625493765e-3f }), z, f2_{ 4.166664568298827e-2f, 4.166664568298827e-2f }), z * z, pfma2(z, f2_{ -0.5f, -0.5f }, f2_{ 1.0f, 1.0f }));
-
-    #pragma unroll
-    for(int i = 0; i < 2; ++i)
-    {
-      int const q = (int)k[i];
-
-      float const s_ = (q & 1) ? cp[i] : sp[i];
-      float const c_ = (q & 1) ? sp[i] : cp[i];
-
-      sn[i] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, s_) ^ (((unsigned)q << 30) & 0x80000000u));
-      cs[i] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, c_) ^ (((unsigned)(q + 1) << 30) & 0x80000000u));
-    }
-  }
+  // (f2_, pfma2: ocean_phase.h)
 
   // sin / cos of the phases of two slots.  WILD (the row pass's template flag, chosen per launch by the host): a phase may lie
   // outside [0, 2 pi) -- uploaded so, or left there by a negative dt -- and v_sin_f32 / v_cos_f32 end at 256 turns: the reduction +
@@ -823,18 +763,17 @@ namespace ocean
         {
           float const dt = a.dt[k];
 
-          // two slots per instruction: w = omega dt, a = phase + w, b = a - 2 pi (the roundings of phase + w dt, see advance_phase), then the select
+          // two slots per instruction: w = omega dt, then the fused advance (ocean_phase.h)
           f2_ const dt2 = { dt, dt };
 
           #pragma unroll
           for(int s = 0; s < E; s += 2)
           {
             f2_ const w = f2_{ in.om[s], in.om[s + 1] } * dt2;
-            f2_ const sum = f2_{ ph[s], ph[s + 1] } + w;
-            f2_ const wrapped = sum - f2_{ 6.2831855f, 6.2831855f };
+            f2_ const p = fused_advance_pair(f2_{ ph[s], ph[s + 1] }, w);
 
-            ph[s] = (sum.x >= 6.2831855f) ? wrapped.x : sum.x;
-            ph[s + 1] = (sum.y >= 6.2831855f) ? wrapped.y : sum.y;
+            ph[s] = p.x;
+            ph[s + 1] = p.y;
           }
         }
 

@@ -15,7 +15,8 @@
 //   * what does not depend on the vertex is evaluated once on the host in the shader's operation order (GenFrame) --
 //     gfx950 has no scalar float unit, a uniform product costs a vector instruction in every wave;
 //   * the shading frame (gen.comp:101-120) uses v_rsq_f32 / v_exp_f32 / v_log_f32 and FMAs: errors are not amplified there;
-//   * sin / cos of the swell phase (up to 1e5..1e6 at the horizon) by the two-constant Cody-Waite step of sincos_phase;
+//   * sin / cos of the swell phase (up to 1e5..1e6 at the horizon) by sincos_phase_pair_poly (ocean_phase.h: two Cody-Waite steps with
+//     a two-constant pi/2, within 4 * 2^-24 + |x| * 2^-49.7 of float64 up to |x| = 2^21);
 //   * texture(sampler2DArray) (gen.comp:113-114) is a manual bilinear REPEAT fetch from the module's own map layout
 //     (ocean_layout.h: map_compact_a / map_compact_b) in fp32 with float weights (lavapipe-style exact bilinear).  The texel index wraps
 //     through v_fract_f32 of coordinate / N (exact: N is a power of two), right for every float the oracle's 64-bit wrap
@@ -199,34 +200,6 @@ namespace ocean
     return { a.x * inv, a.y * inv, a.z * inv };
   }
 
-  // sincos_phase (ocean_kernels.hip) of two arguments: the same reduction and polynomials, packed.  Always the software form
-  // here: the swell phase reaches 1e5..1e6 at the horizon, far outside v_sin_f32's domain
-  __device__ __forceinline__ void sincos_phase2(v2 x, v2 &sn, v2 &cs)
-  {
-    v2 t = x * 0.636619772367581343f;                            // x * 2/pi
-    v2 k = { __builtin_rintf(t.x), __builtin_rintf(t.y) };
-
-    v2 r = pfma(k, splat(-1.57079637050628662109375f), x);       // pi/2 head
-    r = pfma(k, splat(4.37113900018624283e-8f), r);              // pi/2 tail
-
-    v2 z = r * r;
-
-    v2 sp = pfma(pfma(pfma(splat(-1.9515295891e-4f), z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * r, r);
-    v2 cp = pfma(pfma(pfma(splat(2.443315711809948e-5f), z, -1.388731625493765e-3f), z, 4.166664568298827e-2f), z * z, pfma(z, splat(-0.5f), 1.0f));
-
-    #pragma unroll
-    for(int i = 0; i < 2; ++i)
-    {
-      int q = (int)k[i];
-
-      float s = (q & 1) ? cp[i] : sp[i];
-      float c = (q & 1) ? sp[i] : cp[i];
-
-      sn[i] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, s) ^ (((unsigned)q << 30) & 0x80000000u));
-      cs[i] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, c) ^ (((unsigned)(q + 1) << 30) & 0x80000000u));
-    }
-  }
-
   // rotate v by the unit quaternion q = (w, x, y, z)   (data/transform.inc:32-37), the shader's operation order
   __device__ __forceinline__ p3 rotate(float const (&q)[4], p3 v)
   {
@@ -363,7 +336,9 @@ namespace ocean
 
       v2 const theta = f.frequency * (p.swelldirection[0] * basex + p.swelldirection[1] * basey) + p.swellphase;
 
-      sincos_phase2(theta, st[ph], ct[ph]);
+      // (ocean_phase.h, no copy here: always the software form -- the swell phase reaches 1e5 .. 1e6 at the horizon, far outside
+      // v_sin_f32's domain -- and pinned against float64 up to |x| = 2^21 by tests/test_gen64.py)
+      sincos_phase_pair_poly(theta, st[ph], ct[ph]);
 
       position[ph] = { basex + f.gx * ct[ph], basey + f.gy * ct[ph], f.basez + p.swellamplitude * st[ph] };
 

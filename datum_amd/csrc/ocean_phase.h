@@ -81,17 +81,33 @@ namespace ocean
 
   //|---------------------- ocean.sim: sin and cos of any phase ----------------
 
-  // sin and cos of the phase (sim.comp:61-62).  update_ocean keeps the phase in [0, 2 pi), so the argument
-  // reduction is a two-constant Cody-Waite step to [-pi/4, pi/4] followed by the Cephes single-precision
-  // minimax polynomials: about 1 ulp there (measured against float64 in tests/test_phase_emul.py), at a quarter of the
-  // instructions and registers of the all-range libm path.  Arguments far outside (|x| >> 1e4) lose accuracy
-  // gradually, as GLSL's own sin/cos do.
+  // sin and cos of the phase (sim.comp:61-62) and of the swell phase (gen.comp:99).  update_ocean keeps the phase in [0, 2 pi), so the
+  // argument reduction is a two-constant Cody-Waite step to [-pi/4, pi/4] followed by the Cephes single-precision minimax polynomials:
+  // about 1 ulp there (measured against float64 in tests/test_phase_emul.py), at a quarter of the instructions and registers of the
+  // all-range libm path.
+  //
+  // Far outside -- the swell phase of a ray at the horizon is 1e5 .. 1e6 -- two things grow with |x| (tests/test_gen64.py measures both
+  // up to |x| = 2^21, profiles/gen_pointwise_table.txt):
+  //   * pi/2 is HEAD + TAIL only to 1.72e-15, so the reduced argument is off by 1.09e-15 = 2^-49.7 per unit of x: 2.3e-9 at 2^21,
+  //     a hundredth of the polynomials' own error.  A third constant would buy nothing below |x| = 2^26;
+  //   * the quarter-turn count rint(x * 2/pi) is taken from a ROUNDED product with a rounded constant (4e-8 relative): next to a
+  //     quadrant boundary it can be off by one, at |x| = 2^21 wherever the fraction lies within 0.15 of one half.  The reduced
+  //     argument then reaches 1.02 instead of pi/4 and the polynomials leave their interval: 3.7e-7 at 2^20 <= |x| < 2^21 (nothing
+  //     above 1.1e-7 below 2^20) before the second step below was added.  One more Cody-Waite step on the reduced argument -- its count
+  //     is -1, 0 or 1 -- brings it back to [-pi/4, pi/4]; where the first count was right the step multiplies by zero and changes no bit.
+  // With it the error stays below 4 * 2^-24 + |x| * 2^-49.7 up to |x| = 2^21 (measured 1.04e-7).  Beyond, accuracy is lost gradually, as
+  // GLSL's own sin / cos lose it.
   OP_HD void sincos_phase(float x, float *sin_out, float *cos_out)
   {
     float k = rintf(x * 0.636619772367581343f);                 // x * 2/pi
 
     float r = fmaf(k, -1.57079637050628662109375f, x);          // pi/2 head
     r = fmaf(k, 4.37113900018624283e-8f, r);                    // pi/2 tail
+
+    float const k2 = rintf(r * 0.636619772367581343f);          // -1, 0, 1: the first count was a rounded product's
+    r = fmaf(k2, -1.57079637050628662109375f, r);               // (exact: r and pi/2 within a factor of two of each other, or k2 = 0)
+    r = fmaf(k2, 4.37113900018624283e-8f, r);
+    k += k2;
 
     float z = r * r;
 
@@ -111,10 +127,17 @@ namespace ocean
   OP_HD void sincos_phase_pair_poly(f2_ x, f2_ &sn, f2_ &cs)
   {
     f2_ const t = x * 0.636619772367581343f;                            // x * 2/pi
-    f2_ const k = { __builtin_rintf(t[0]), __builtin_rintf(t[1]) };
+    f2_ k = { __builtin_rintf(t[0]), __builtin_rintf(t[1]) };
 
     f2_ r = pfma2(k, f2_{ -1.57079637050628662109375f, -1.57079637050628662109375f }, x);       // pi/2 head
     r = pfma2(k, f2_{ 4.37113900018624283e-8f, 4.37113900018624283e-8f }, r);                    // pi/2 tail
+
+    f2_ const t2 = r * 0.636619772367581343f;                           // the second step of sincos_phase
+    f2_ const k2 = { __builtin_rintf(t2[0]), __builtin_rintf(t2[1]) };
+
+    r = pfma2(k2, f2_{ -1.57079637050628662109375f, -1.57079637050628662109375f }, r);
+    r = pfma2(k2, f2_{ 4.37113900018624283e-8f, 4.37113900018624283e-8f }, r);
+    k += k2;
 
     f2_ const z = r * r;
 

@@ -28,6 +28,16 @@ CASES = {
     # sea level at z = 1.5 (plane.w = -1.5), camera 6.5 m above it
     "plane_w": dict(position=(0, 0, 8), target=(0.9396926, 0.1, 8 - 0.3420201), up=(0, 0, 1),
                     params=dict(swellsteepness=0.8, swellamplitude=0.5, swelllength=25.0, plane=(0.0, 0.0, 1.0, -1.5))),
+    # 0.3 m above the sea, looking level: costheta changes sign across the middle rows, the rays just below the horizon hit the plane
+    # at 1e5 m and beyond (swell phases of 1e5 and more), margin = 1 + sqrt(0.7 / 0.3) = 2.5
+    "grazing": dict(position=(0, 0, 0.3), target=(1, 0, 0.3), up=(0, 0, 1),
+                    params=dict(swellsteepness=0.3, swellamplitude=0.1, swelllength=12.0, swelldirection=(0.6, 0.8))),
+    # 50 m up, looking straight down with up = +x: the components of viewvec and of worlddir pass through zero inside the mesh
+    "nadir": dict(position=(0, 0, 50), target=(0, 0, 0), up=(1, 0, 0),
+                  params=dict(swellsteepness=0.3, swellamplitude=0.8, swelllength=40.0)),
+    # 2e4 m up, 30 degrees down: camerapos, dist and base at 1e4 .. 1e5, margin = 1 + 1e-2
+    "altitude": dict(position=(0, 0, 2e4), target=(0.8660254, 0, 2e4 - 0.5), up=(0, 0, 1),
+                     params=dict(swellsteepness=0.3, swellamplitude=0.8, swelllength=40.0)),
 }
 
 FOV = 60.0 * np.pi / 180.0          # examples/ocean/ocean.h:17-18

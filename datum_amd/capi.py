@@ -124,6 +124,9 @@ SYMBOLS = {
     "datum_ocean_upload_height": (I, [P, I, P]),
     "datum_ocean_sample_surface": (I, [P, I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_surface": (I, [P, I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_gen_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, P]),
+    "datum_ocean_sample_surface_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_surface_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -535,6 +538,32 @@ class Ocean:
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
         out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_surface(self.h, cascade, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
+
+    # -- several cascades at once (datum_ocean_gen_blend): the summed surface's mesh and queries -------------------------------------
+
+    @staticmethod
+    def _list(cascades):
+        c = [int(x) for x in cascades]
+        return (I * len(c))(*c), len(c)
+
+    def gen_blend(self, cascades, oceanset, sizex, sizey, vertices_device_ptr):
+        """gen() of the sum of the listed cascades, each sampled with the handle's own 1 / wavescale (oceanset.scale is ignored)"""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_gen_blend(self.h, arr, n, ctypes.byref(oceanset), sizex, sizey, P(vertices_device_ptr)))
+
+    def sample_surface_blend(self, cascades, oceanset, points_ptr, count, samples_ptr, iterations=4):
+        """sample_surface() of the sum of the listed cascades: device pointers, enqueued on the handle's stream"""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_sample_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
+                                                              count, P(samples_ptr) if samples_ptr else None))
+
+    def read_surface_blend(self, cascades, oceanset, points, iterations=4):
+        """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
+        arr, n = self._list(cascades)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
         return out
 
     def algorithmic_bytes(self):

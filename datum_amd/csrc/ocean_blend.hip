@@ -1,0 +1,404 @@
+// ocean_blend.hip -- several cascades at once on the read side (include/datum_ocean_hip.h: datum_ocean_gen_blend,
+// datum_ocean_sample_surface_blend): the mesh of the SUMMED surface, and height, normal and foam of that same surface above world points.
+//
+// A blend is a list of up to DATUM_OCEAN_MAX_CASCADES cascades of one handle (one N).  At a position P every listed cascade c is sampled
+// at P.xy * scale_c with gen's REPEAT bilinear fetch; the displacements add in list order (the first taken as it is, one fp32 addition per
+// component for each further one), the normals add as SLOPES: the map stores m = normalize(l.z - r.z, b.z - t.z, 4 wavescale / N), so
+// m.x / m.z = -1/2 dz/dx in world units whatever the cascade's wavescale, p = sum of (m.x / m.z, m.y / m.z), dn = normalize(p.x, p.y, 1).
+//
+//   * ocean_gen_blend_kernel is ocean_gen_kernel's tile, ray stage, texel addressing, shading frame and vertex store -- the same text,
+//     ocean_gen_*.inc -- around a loop over the list.  The ray stage runs once per vertex, the addressing once per cascade.  One cascade's
+//     fetches are in flight at a time: the accumulators are 6 + 4 registers, a second cascade's 48 registers of corners would cost a wave
+//     per SIMD;
+//   * gen's per-wave shortcuts, per cascade: `shaded` (the wave needs normals) depends on the distance smoothing alone, `near` (some
+//     second texel has a weight) on scale_c -- a fine cascade is beyond 2^23 texels where a coarse one is not;
+//   * ocean_surface_blend_kernel is ocean_surface_kernel with V(b) summed over the list (SurfaceTexel per cascade); parts B and the foam
+//     planes are fetched in the final evaluation only;
+//   * the list travels in the kernel argument: 16 x (map, foam plane, scale) = 384 bytes.
+// LDS: gen's vertex staging; no scratch (make resource-usage).
+
+#pragma once
+
+#include "ocean_gen.hip"
+#include "ocean_surface.hip"
+
+namespace ocean
+{
+  struct BlendCascade
+  {
+    float4 const *map;      // the cascade's displacement map, map_cascade_bytes(N) bytes
+    float const *foam;      // the cascade's foam plane, N * N floats; nullptr while foam is OFF
+    float scale;            // the handle's 1 / wavescale of the cascade
+    int pad;
+  };
+
+  struct BlendList
+  {
+    int count;
+    int foammode;           // DATUM_OCEAN_FOAM_*: how the queries combine the planes
+    BlendCascade casc[DATUM_OCEAN_MAX_CASCADES];
+  };
+
+  struct GenBlendArgs
+  {
+    GenArgs g;              // g.map and g.set.scale are not read
+    BlendList list;
+  };
+
+  struct SurfaceBlendArgs
+  {
+    SurfaceArgs s;          // s.map, s.foam and s.set.scale are not read
+    BlendList list;
+  };
+
+  template<int LAYOUT>
+  __attribute__((amdgpu_waves_per_eu(4, 4)))
+  __global__ void __launch_bounds__(GEN_THREADS) ocean_gen_blend_kernel(GenBlendArgs b)
+  {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+    GenArgs const &g = b.g;
+
+#ifdef OCEAN_STAMPS
+    unsigned long long *stampbase = g.stamps + (size_t)blockIdx.x * 16;
+#endif
+
+    constexpr int PH = 1;
+    constexpr int ph = 0;
+
+    #include "ocean_gen_tile.inc"
+
+    p3 position[PH];
+    v2 smoothing[PH], st[PH], ct[PH];
+
+    #include "ocean_gen_ray.inc"
+
+    // wave-uniform, once: the distance smoothing does not depend on the cascade
+    bool const shaded = __builtin_amdgcn_ballot_w64(smoothing[ph].x != 1.0f || smoothing[ph].y != 1.0f) != 0;
+
+    p3 displacement = { splat(0.0f), splat(0.0f), splat(0.0f) };
+    v2 slopex = splat(0.0f), slopey = splat(0.0f);
+
+    #pragma unroll 1
+    for(int c = 0; c < b.list.count; ++c)
+    {
+      BlendCascade const &bc = b.list.casc[c];
+
+      __amdgpu_buffer_rsrc_t const rmap = make_rsrc(bc.map, map_cascade_bytes(g.N));
+
+      // (declared per cascade: nothing of one cascade's corners is carried into the next one's registers)
+      v2 w00[PH], w10[PH], w01[PH], w11[PH];
+      int o00[PH][2], o10[PH][2], o01[PH][2], o11[PH][2];
+      bool near[PH];
+      float4 a00[PH][2], a10[PH][2], a01[PH][2], a11[PH][2];
+      GenNormalFetch b00[PH][2], b10[PH][2], b01[PH][2], b11[PH][2];
+      int q00[PH][2], q10[PH][2], q01[PH][2], q11[PH][2];
+
+      #define OCEAN_GEN_TEXEL_SCALE bc.scale
+      #include "ocean_gen_texel.inc"
+      #undef OCEAN_GEN_TEXEL_SCALE
+
+      // gen's three fetch patterns (ocean_gen.hip), the normal right behind its displacement, and gen's blend
+      // w11 a11 + (w01 a01 + (w10 a10 + w00 a00)) in FMAs, each pattern blended where it is fetched: only the cascade's sample leaves the branch
+      #define OCEAN_GEN_FETCH_A(C) a##C[ph][i] = buf_load_f32x4_aux<0>(rmap, o##C[ph][i], 0)
+      #define OCEAN_GEN_FETCH_B(C) b##C[ph][i] = GenNormal::load(rmap, q##C[ph][i])
+      #define OCEAN_GEN_BLEND(T, C) pfma(w11[ph], v2{ T##11[ph][0].C, T##11[ph][1].C }, pfma(w01[ph], v2{ T##01[ph][0].C, T##01[ph][1].C }, pfma(w10[ph], v2{ T##10[ph][0].C, T##10[ph][1].C }, w00[ph] * v2{ T##00[ph][0].C, T##00[ph][1].C })))
+      #define OCEAN_GEN_BLENDN(F) pfma(w11[ph], v2{ F(a11[ph][0], b11[ph][0]), F(a11[ph][1], b11[ph][1]) }, pfma(w01[ph], v2{ F(a01[ph][0], b01[ph][0]), F(a01[ph][1], b01[ph][1]) }, pfma(w10[ph], v2{ F(a10[ph][0], b10[ph][0]), F(a10[ph][1], b10[ph][1]) }, w00[ph] * v2{ F(a00[ph][0], b00[ph][0]), F(a00[ph][1], b00[ph][1]) })))
+
+      p3 d;
+
+      if (shaded)
+      {
+        #pragma unroll
+        for(int i = 0; i < 2; ++i)
+        {
+          OCEAN_GEN_FETCH_A(00); OCEAN_GEN_FETCH_B(00);
+          OCEAN_GEN_FETCH_A(10); OCEAN_GEN_FETCH_B(10);
+          OCEAN_GEN_FETCH_A(01); OCEAN_GEN_FETCH_B(01);
+          OCEAN_GEN_FETCH_A(11); OCEAN_GEN_FETCH_B(11);
+        }
+
+        d = { OCEAN_GEN_BLEND(a, x), OCEAN_GEN_BLEND(a, y), OCEAN_GEN_BLEND(a, z) };
+
+        v2 const mx_ = OCEAN_GEN_BLENDN(GenNormal::x), my_ = OCEAN_GEN_BLENDN(GenNormal::y), mz_ = OCEAN_GEN_BLENDN(GenNormal::z);
+
+        // slopes add, unit normals do not: m.z > 0 in every texel (v_rcp_f32, 1 ulp: the shading frame amplifies nothing)
+        v2 const rz = prcp(mz_);
+
+        slopex = pfma(mx_, rz, slopex);
+        slopey = pfma(my_, rz, slopey);
+      }
+      else if (near[ph])
+      {
+        #pragma unroll
+        for(int i = 0; i < 2; ++i)
+        {
+          OCEAN_GEN_FETCH_A(00);
+          OCEAN_GEN_FETCH_A(10);
+          OCEAN_GEN_FETCH_A(01);
+          OCEAN_GEN_FETCH_A(11);
+        }
+
+        d = { OCEAN_GEN_BLEND(a, x), OCEAN_GEN_BLEND(a, y), OCEAN_GEN_BLEND(a, z) };
+      }
+      else
+      {
+        // every ray of the wave is beyond 2^23 texels of this cascade along both axes: one texel per vertex, its weight (1 - 0) * (1 - 0)
+        #pragma unroll
+        for(int i = 0; i < 2; ++i)
+          OCEAN_GEN_FETCH_A(00);
+
+        d = { w00[ph] * v2{ a00[ph][0].x, a00[ph][1].x }, w00[ph] * v2{ a00[ph][0].y, a00[ph][1].y }, w00[ph] * v2{ a00[ph][0].z, a00[ph][1].z } };
+      }
+
+      #undef OCEAN_GEN_FETCH_A
+      #undef OCEAN_GEN_FETCH_B
+      #undef OCEAN_GEN_BLEND
+      #undef OCEAN_GEN_BLENDN
+
+      // the first cascade as it is (a one-element list gives gen's bits), each further one added: one rounding per component
+      if (c == 0)
+        displacement = d;
+      else
+        displacement = { displacement.x + d.x, displacement.y + d.y, displacement.z + d.z };
+    }
+
+    float4 *mine = reinterpret_cast<float4*>(smem) + 384 * wave;
+
+    p3 const planen = { splat(p.plane[0]), splat(p.plane[1]), splat(p.plane[2]) };
+
+    p3 tbn2;
+
+    if (shaded)
+    {
+      p3 const dn = normalize3(p3{ slopex, slopey, splat(1.0f) });
+
+      #include "ocean_gen_frame.inc"
+    }
+    else
+      tbn2 = normalize3(planen);
+
+    #include "ocean_gen_store.inc"
+  }
+
+  // gen's frame m.x t0 + m.y t1 + m.z t2 normalised (ocean_surface.hip, gen.comp:101-120 with smoothing = 0), for dn = normalize(sx, sy, 1)
+  __device__ __forceinline__ void blend_surface_normal(GenFrame const &f, float st, float ct, float sx, float sy, float &mx, float &my, float &mz)
+  {
+    float nx = sx, ny = sy, nz = 1.0f;
+
+    normalize3(nx, ny, nz);
+
+    float t2x = -f.nx * ct, t2y = -f.ny * ct, t2z = fmaf(-f.nz, st, 1.0f);
+    float t0x = fmaf(-f.tx, st, 1.0f), t0y = -f.ty * st, t0z = f.tz * ct;
+
+    normalize3(t2x, t2y, t2z);
+    normalize3(t0x, t0y, t0z);
+
+    float const t1x = t0y * t2z - t0z * t2y, t1y = t0z * t2x - t0x * t2z, t1z = t0x * t2y - t0y * t2x;
+
+    mx = fmaf(nz, t2x, fmaf(ny, t1x, nx * t0x));
+    my = fmaf(nz, t2y, fmaf(ny, t1y, nx * t0y));
+    mz = fmaf(nz, t2z, fmaf(ny, t1z, nx * t0z));
+
+    normalize3(mx, my, mz);
+  }
+
+  template<int LAYOUT>
+  __global__ void __launch_bounds__(SURFACE_THREADS) ocean_surface_blend_kernel(SurfaceBlendArgs b)
+  {
+    SurfaceArgs const &s = b.s;
+
+    int const k = (int)blockIdx.x * SURFACE_THREADS + (int)threadIdx.x;
+
+    if (k >= s.count)
+      return;
+
+    datum_ocean_set const &p = s.set;
+    GenFrame const &f = s.frame;
+
+    float2 const q = s.points[k];
+
+    float4 *out = s.samples + 2 * (size_t)k;
+
+    if (!__builtin_isfinite(q.x) || !__builtin_isfinite(q.y))
+    {
+      float const nan = __builtin_nanf("");
+
+      out[0] = make_float4(nan, nan, nan, nan);
+      out[1] = make_float4(nan, nan, nan, nan);
+      return;
+    }
+
+    TexelIndex<LAYOUT> const texel(s.N);
+
+    int const nmask = s.N - 1;
+    int const count = b.list.count;
+
+    size_t const mapbytes = map_cascade_bytes(s.N);
+
+    float const dirx = p.swelldirection[0], diry = p.swelldirection[1];
+
+    float bx = q.x, by = q.y;
+
+    float st, ct, px, py;
+
+    // the updates b <- b + (q - V(b).xy): part A of every listed cascade's four corners, D.xy summed in list order
+    for(int it = 0; it < s.iterations; ++it)
+    {
+      float const theta = f.frequency * (dirx * bx + diry * by) + p.swellphase;
+
+      sincos_phase(theta, &st, &ct);
+
+      px = bx + f.gx * ct;
+      py = by + f.gy * ct;
+
+      float dx = 0.0f, dy = 0.0f;
+
+      for(int c = 0; c < count; ++c)
+      {
+        BlendCascade const &bc = b.list.casc[c];
+
+        __amdgpu_buffer_rsrc_t const rmap = make_rsrc(bc.map, mapbytes);
+
+        SurfaceTexel<LAYOUT> const t(texel, f, bc.scale, nmask, px, py);
+
+        float4 const a00 = buf_load_f32x4_aux<0>(rmap, t.o00, 0);
+        float4 const a10 = buf_load_f32x4_aux<0>(rmap, t.o10, 0);
+        float4 const a01 = buf_load_f32x4_aux<0>(rmap, t.o01, 0);
+        float4 const a11 = buf_load_f32x4_aux<0>(rmap, t.o11, 0);
+
+        float const cx = t.blend(a00.x, a10.x, a01.x, a11.x);
+        float const cy = t.blend(a00.y, a10.y, a01.y, a11.y);
+
+        dx = (c == 0) ? cx : dx + cx;
+        dy = (c == 0) ? cy : dy + cy;
+      }
+
+      float const vx = px - dx;
+      float const vy = py - dy;
+
+      bx = bx + (q.x - vx);
+      by = by + (q.y - vy);
+    }
+
+    // the final evaluation at b: parts A and B and the foam plane of every listed cascade
+    float const theta = f.frequency * (dirx * bx + diry * by) + p.swellphase;
+
+    sincos_phase(theta, &st, &ct);
+
+    px = bx + f.gx * ct;
+    py = by + f.gy * ct;
+
+    float dx = 0.0f, dy = 0.0f, dz = 0.0f, sx = 0.0f, sy = 0.0f, foam = 0.0f;
+
+    for(int c = 0; c < count; ++c)
+    {
+      BlendCascade const &bc = b.list.casc[c];
+
+      __amdgpu_buffer_rsrc_t const rmap = make_rsrc(bc.map, mapbytes);
+
+      SurfaceTexel<LAYOUT> const t(texel, f, bc.scale, nmask, px, py);
+
+      float4 const a00 = buf_load_f32x4_aux<0>(rmap, t.o00, 0);
+      float4 const a10 = buf_load_f32x4_aux<0>(rmap, t.o10, 0);
+      float4 const a01 = buf_load_f32x4_aux<0>(rmap, t.o01, 0);
+      float4 const a11 = buf_load_f32x4_aux<0>(rmap, t.o11, 0);
+
+      int const bc0 = texel.bcolumn(t.i0), bc1 = texel.bcolumn(t.i1);
+      int const br0 = MAP_PART_B - texel.brow(t.j0), br1 = MAP_PART_B - texel.brow(t.j1);
+
+      float2 const b00 = buf_load_f32x2(rmap, t.o00 + br0 - bc0, 0);
+      float2 const b10 = buf_load_f32x2(rmap, t.wantx ? t.o10 + br0 - bc1 : -256, 0);
+      float2 const b01 = buf_load_f32x2(rmap, t.wanty ? t.o01 + br1 - bc0 : -256, 0);
+      float2 const b11 = buf_load_f32x2(rmap, (t.wantx && t.wanty) ? t.o11 + br1 - bc1 : -256, 0);
+
+      if (bc.foam)
+      {
+        __amdgpu_buffer_rsrc_t const rfoam = make_rsrc(bc.foam, (size_t)s.N * s.N * sizeof(float));
+
+        float const g00 = buf_load_f32(rfoam, ((t.j0 << texel.ln) + t.i0) * 4, 0);
+        float const g10 = buf_load_f32(rfoam, t.wantx ? ((t.j0 << texel.ln) + t.i1) * 4 : -256, 0);
+        float const g01 = buf_load_f32(rfoam, t.wanty ? ((t.j1 << texel.ln) + t.i0) * 4 : -256, 0);
+        float const g11 = buf_load_f32(rfoam, (t.wantx && t.wanty) ? ((t.j1 << texel.ln) + t.i1) * 4 : -256, 0);
+
+        float const fc = t.blend(g00, g10, g01, g11);
+
+        // ACCUMULATE: the largest coverage; JACOBIAN: 1 + sum (J_c - 1), the summed displacement's Jacobian without the cross terms
+        if (b.list.foammode == DATUM_OCEAN_FOAM_JACOBIAN)
+          foam = foam + (fc - 1.0f);
+        else
+          foam = (c == 0) ? fc : fmaxf(foam, fc);
+      }
+
+      float const cx = t.blend(a00.x, a10.x, a01.x, a11.x);
+      float const cy = t.blend(a00.y, a10.y, a01.y, a11.y);
+      float const cz = t.blend(a00.z, a10.z, a01.z, a11.z);
+
+      dx = (c == 0) ? cx : dx + cx;
+      dy = (c == 0) ? cy : dy + cy;
+      dz = (c == 0) ? cz : dz + cz;
+
+      float const nx = t.blend(a00.w, a10.w, a01.w, a11.w);
+      float const ny = t.blend(b00.x, b10.x, b01.x, b11.x);
+      float const nz = t.blend(b00.y, b10.y, b01.y, b11.y);
+
+      float const rz = __builtin_amdgcn_rcpf(nz);
+
+      sx = fmaf(nx, rz, sx);
+      sy = fmaf(ny, rz, sy);
+    }
+
+    if (b.list.foammode == DATUM_OCEAN_FOAM_JACOBIAN)
+      foam = 1.0f + foam;
+
+    float const vx = px - dx, vy = py - dy, vz = (f.basez + p.swellamplitude * st) + dz;
+
+    float const rx = vx - q.x, ry = vy - q.y;
+    float const residual = __builtin_sqrtf(fmaf(ry, ry, rx * rx));
+
+    float mx, my, mz;
+
+    blend_surface_normal(f, st, ct, sx, sy, mx, my, mz);
+
+    out[0] = make_float4(vx, vy, vz, residual);
+    out[1] = make_float4(mx, my, mz, foam);
+  }
+
+  inline void const *gen_blend_kernel_for(int N)
+  {
+    switch(gen_layout(N))
+    {
+      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_gen_blend_kernel<GEN_PLAIN>);
+      default: return reinterpret_cast<void const*>(&ocean_gen_blend_kernel<GEN_BANDED>);
+    }
+  }
+
+  inline void const *surface_blend_kernel_for(int N)
+  {
+    switch(gen_layout(N))
+    {
+      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_surface_blend_kernel<GEN_PLAIN>);
+      default: return reinterpret_cast<void const*>(&ocean_surface_blend_kernel<GEN_BANDED>);
+    }
+  }
+
+  // b.g.set, b.g.vertices and b.list filled in
+  inline hipError_t launch_gen_blend(GenBlendArgs &b, int N, int sizex, int sizey, hipStream_t stream)
+  {
+    gen_shape(b.g, N, sizex, sizey);
+
+    void *args[] = { &b };
+
+    return hipLaunchKernel(gen_blend_kernel_for(N), dim3(gen_groups(b.g)), dim3(GEN_THREADS), args, GEN_LDS, stream);
+  }
+
+  // b.s.set, points, samples, N, count (> 0), iterations and b.list filled in
+  inline hipError_t launch_surface_blend(SurfaceBlendArgs &b, hipStream_t stream)
+  {
+    b.s.frame = make_gen_frame(b.s.set, b.s.N, 2, 2);      // the camera's terms are not read
+
+    void *args[] = { &b };
+
+    return hipLaunchKernel(surface_blend_kernel_for(b.s.N), dim3((unsigned)((b.s.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+  }
+}

@@ -22,6 +22,7 @@
 #include "ocean_farm.hip"
 #include "ocean_foam.hip"
 #include "ocean_surface.hip"
+#include "ocean_blend.hip"
 
 using namespace ocean;
 
@@ -2060,6 +2061,29 @@ namespace
     s.iterations = iterations;
     return s;
   }
+
+  // the host entry points' device staging of `count` points and records (grown on demand), the points copied in on the handle's stream
+  int stage_surface(datum_ocean_ctx *ctx, float const *points, size_t count)
+  {
+    if (count > ctx->surfacecapacity)
+    {
+      // the old staging may still be read by an earlier launch of this stream
+      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+      HIPCHECK(ctx, hipFree(ctx->surfacepoints));
+      HIPCHECK(ctx, hipFree(ctx->surfacesamples));
+      ctx->surfacepoints = nullptr;
+      ctx->surfacesamples = nullptr;
+      ctx->surfacecapacity = 0;
+
+      HIPCHECK(ctx, hipMalloc(&ctx->surfacepoints, count * sizeof(float2)));
+      HIPCHECK(ctx, hipMalloc(&ctx->surfacesamples, count * 2 * sizeof(float4)));
+      ctx->surfacecapacity = count;
+    }
+
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->surfacepoints, points, count * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
 }
 
 extern "C"
@@ -2088,27 +2112,141 @@ int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set con
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  if (count > ctx->surfacecapacity)
-  {
-    // the old staging may still be read by an earlier launch of this stream
-    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHECK(ctx, hipFree(ctx->surfacepoints));
-    HIPCHECK(ctx, hipFree(ctx->surfacesamples));
-    ctx->surfacepoints = nullptr;
-    ctx->surfacesamples = nullptr;
-    ctx->surfacecapacity = 0;
-
-    HIPCHECK(ctx, hipMalloc(&ctx->surfacepoints, count * sizeof(float2)));
-    HIPCHECK(ctx, hipMalloc(&ctx->surfacesamples, count * 2 * sizeof(float4)));
-    ctx->surfacecapacity = count;
-  }
-
-  HIPCHECK(ctx, hipMemcpyAsync(ctx->surfacepoints, points, count * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+  rc = stage_surface(ctx, points, count);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   SurfaceArgs s = surface_args(ctx, cascade, set, iterations, ctx->surfacepoints, count, ctx->surfacesamples);
 
   HIPCHECK(ctx, launch_surface(s, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(samples, ctx->surfacesamples, count * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
+/* -- several cascades at once (ocean_blend.hip) ------------------------------------------------------------------------------- */
+
+namespace
+{
+  // the list's checks, shared by the three entry points; `name` goes into the error text
+  int check_blend_list(datum_ocean_ctx *ctx, int const *cascades, int count, char const *name)
+  {
+    std::string const what = name;
+
+    if (!ctx)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle").c_str());
+
+    if (!cascades)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null cascade list").c_str());
+
+    if (count < 1 || count > DATUM_OCEAN_MAX_CASCADES)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": count outside [1, DATUM_OCEAN_MAX_CASCADES]").c_str());
+
+    for(int i = 0; i < count; ++i)
+      if (cascades[i] < 0 || cascades[i] >= ctx->cascades)
+        return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  BlendList blend_list(datum_ocean_ctx *ctx, int const *cascades, int count)
+  {
+    BlendList l = {};
+    l.count = count;
+    l.foammode = ctx->foammode;
+
+    for(int i = 0; i < count; ++i)
+    {
+      int const c = cascades[i];
+
+      l.casc[i].map = reinterpret_cast<float4 const*>(map_block(ctx, c));
+      l.casc[i].foam = (ctx->foammode != DATUM_OCEAN_FOAM_OFF) ? ctx->foam.get() + (size_t)c * plane(ctx) : nullptr;
+      l.casc[i].scale = ctx->casc[c].scale;
+    }
+
+    return l;
+  }
+
+  SurfaceBlendArgs surface_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  {
+    SurfaceBlendArgs b;
+    b.s = surface_args(ctx, cascades[0], set, iterations, points, n, samples);
+    b.s.map = nullptr;
+    b.s.foam = nullptr;
+    b.list = blend_list(ctx, cascades, count);
+    return b;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
+{
+  if (!ctx || !set || !vertices_device)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_gen_blend: null argument");
+
+  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_gen_blend");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (sizex < 2 || sizey < 2)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_gen_blend: mesh must be at least 2 x 2");
+
+  if ((uintptr_t)vertices_device & 15)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_gen_blend: vertex buffer must be 16-byte aligned");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  GenBlendArgs b;
+  b.g.set = *set;
+  b.g.map = nullptr;
+  b.g.vertices = (float*)vertices_device;
+  b.list = blend_list(ctx, cascades, count);
+
+  HIPCHECK(ctx, launch_gen_blend(b, ctx->N, sizex, sizey, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_sample_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
+{
+  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_sample_surface_blend");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_surface_args(ctx, cascades[0], set, iterations, points_device, n, samples_device, "datum_ocean_sample_surface_blend");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  SurfaceBlendArgs b = surface_blend_args(ctx, cascades, count, set, iterations, points_device, n, samples_device);
+
+  HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
+{
+  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_read_surface_blend");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_surface_args(ctx, cascades[0], set, iterations, points, n, samples, "datum_ocean_read_surface_blend");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  rc = stage_surface(ctx, points, n);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  SurfaceBlendArgs b = surface_blend_args(ctx, cascades, count, set, iterations, ctx->surfacepoints, n, ctx->surfacesamples);
+
+  HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(samples, ctx->surfacesamples, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;

@@ -214,6 +214,8 @@ namespace ocean
   // (One function, local arrays: with the three stages as functions over structs, or inside a loop over tiles, hipcc keeps
   // 134-154 registers instead of 86 and spills -- measured 17.7 against 16.3 us; a persistent loop, 3 or 4 workgroups
   // per CU: 17.1 / 18.1 us; a 1024-thread workgroup per CU sampling a 64^2 map from LDS: 24.5 us.  profiles/r03_gen_experiments.txt)
+  // The stages the several-cascade kernel (ocean_blend.hip) runs as well are kept as text, ocean_gen_*.inc, and included here in place:
+  // one statement of each stage, and after preprocessing this kernel is token for token what it was (make resource-usage).
 
   // The vertex stream (50 MB per 1024 x 1024 mesh, written once, read by the graphics queue) is stored non-temporally: 26.1 ->
   // 25.5 us from 1024^2 maps, nothing lost from 64^2 maps; the other policies measured in profiles/r04_gen_levers.txt.  (The
@@ -254,41 +256,7 @@ namespace ocean
 
     constexpr int PH = 1;       // sets of four rows per wave (two, software-pipelined, measured slower)
 
-    datum_ocean_set const &p = g.set;
-    GenFrame const &f = g.frame;
-
-    int const tid = threadIdx.x;
-    int const lane = tid & 63;
-    int const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    // Workgroup b runs on XCD b % 8.  A map that does not fit an XCD's 4 MB L2 is sampled in chunks of whole tile rows
-    // dealt to the XCDs in turn: neighbouring tiles share an L2 (1024^2 maps: 36.4 -> 31.0 us), and every XCD gets its
-    // share of the cheap rows above the horizon (one contiguous run of tiles per XCD: 43 us).  Small maps sit in every
-    // L2 anyway; there the launch order is kept (64^2 maps: 16.5 against 17.1 us).
-    int tile = (int)blockIdx.x + g.block0;
-
-    if (g.chunk)
-    {
-      int const slot = tile >> 3;
-
-      tile = ((slot / g.chunk) * 8 + (tile & 7)) * g.chunk + slot % g.chunk;
-
-      if (tile >= g.tiles)
-        return;
-    }
-
-    int const tilex = tile % g.tilesx, tiley = tile / g.tilesx;
-
-    int const x0 = tilex * GEN_TILE_X;
-    int const ywave = tiley * GEN_TILE_Y + 4 * PH * wave;          // first of this wave's 4 * PH rows
-
-    int const xa = x0 + (lane & 15);
-
-    float const *ip = p.invproj;
-
-    TexelIndex<LAYOUT> const texel(g.N);
-
-    int const nmask = g.N - 1;
+    #include "ocean_gen_tile.inc"
 
     __amdgpu_buffer_rsrc_t const rmap = make_rsrc(g.map, map_cascade_bytes(g.N));
 
@@ -305,95 +273,14 @@ namespace ocean
     #pragma unroll
     for(int ph = 0; ph < PH; ++ph)
     {
-      int const yy = ywave + 4 * ph + (lane >> 4);
-
-      //-- view ray, plane hit, swell phase: the shader's expressions and roundings (gen.comp:81-99) ----------------
-
-      v2 const xx = { (float)xa, (float)(xa + 16) };
-
-      v2 const u = (div_exact(2.0f * xx, splat(f.sxm1)) - 1.0f) * f.margin;
-
-      // (one row per thread: its v is the first half of a packed division whose second half repeats it)
-      float const v = ((1.0f - div_exact(splat(2.0f * (float)yy), splat(f.sym1))) * f.margin).x;
-
-      p3 viewvec = { ((ip[0] * u + ip[1] * v) + f.viewz[0]) + f.vieww[0],
-                     ((ip[4] * u + ip[5] * v) + f.viewz[1]) + f.vieww[1],
-                     ((ip[8] * u + ip[9] * v) + f.viewz[2]) + f.vieww[2] };
-
-      v2 const len = sqrt_exact(dot3(viewvec, viewvec));
-      v2 const rlen = refined_rcp(len);
-
-      p3 const worlddir = rotate(p.camera_real, p3{ div_exact(viewvec.x, len, rlen), div_exact(viewvec.y, len, rlen), div_exact(viewvec.z, len, rlen) });
-
-      v2 const costheta = worlddir.x * f.negplane[0] + worlddir.y * f.negplane[1] + worlddir.z * f.negplane[2];
-
-      v2 const hit = div_exact(splat(f.cameraheight), costheta);
-
-      v2 const dist = { (costheta.x > 0) ? hit.x : 1e6f, (costheta.y > 0) ? hit.y : 1e6f };
-
-      v2 const basex = f.camerapos[0] + dist * worlddir.x;
-      v2 const basey = f.camerapos[1] + dist * worlddir.y;
-
-      v2 const theta = f.frequency * (p.swelldirection[0] * basex + p.swelldirection[1] * basey) + p.swellphase;
-
-      // (ocean_phase.h, no copy here: always the software form -- the swell phase reaches 1e5 .. 1e6 at the horizon, far outside
-      // v_sin_f32's domain -- and pinned against float64 up to |x| = 2^21 by tests/test_gen64.py)
-      sincos_phase_pair_poly(theta, st[ph], ct[ph]);
-
-      position[ph] = { basex + f.gx * ct[ph], basey + f.gy * ct[ph], f.basez + p.swellamplitude * st[ph] };
-
-      v2 cl = dist * p.smoothing - 0.35f;
-
-      #pragma unroll
-      for(int i = 0; i < 2; ++i)       // pow(clamp(cl, 0, 1), 0.2): 0 -> 0, 1 -> 1 exactly
-        smoothing[ph][i] = __builtin_amdgcn_exp2f(0.2f * __builtin_amdgcn_logf(__builtin_amdgcn_fmed3f(cl[i], 0.0f, 1.0f)));
+      // (the stage ends in sincos_phase_pair_poly(theta, st[ph], ct[ph]) of ocean_phase.h and the position before the displacement)
+      #include "ocean_gen_ray.inc"
 
       //-- texture(sampler2DArray, REPEAT, linear, lod 0) of both layers at (position.xy * scale): texel centres at (i + 0.5) / N ----
 
-      v2 const fx = (position[ph].x * p.scale) * f.fn - 0.5f;
-      v2 const fy = (position[ph].y * p.scale) * f.fn - 0.5f;
-
-      v2 const flx = pfloor(fx), fly = pfloor(fy);
-
-      v2 const ax = fx - flx, ay = fy - fly;
-
-      // floor(coordinate) mod N: N is a power of two, so coordinate / N, its fractional part and the product with N are exact
-      v2 const wx = flx * f.rfn, wy = fly * f.rfn;
-      v2 const mx = v2{ __builtin_amdgcn_fractf(wx.x), __builtin_amdgcn_fractf(wx.y) } * f.fn;
-      v2 const my = v2{ __builtin_amdgcn_fractf(wy.x), __builtin_amdgcn_fractf(wy.y) } * f.fn;
-
-      v2 const bx = 1.0f - ax, by = 1.0f - ay;
-
-      w00[ph] = bx * by; w10[ph] = ax * by; w01[ph] = bx * ay; w11[ph] = ax * ay;
-
-      near[ph] = false;                        // some weight other than w00 is not zero
-
-      #pragma unroll
-      for(int i = 0; i < 2; ++i)
-      {
-        int const i0 = (int)mx[i], j0 = (int)my[i];
-
-        int const i1 = (i0 + 1) & nmask, j1 = (j0 + 1) & nmask;
-
-        int const c0 = texel.column(i0), c1 = texel.column(i1);
-        int const r0 = texel.row(j0), r1 = texel.row(j1);
-
-        // A zero weight along an axis (beyond |coordinate| = 2^23 texels: every ray above the horizon): the second texel of
-        // that axis is not needed (0 * finite adds nothing).  Its offset is pushed out of the buffer's range: zeros come
-        // back without a memory access, and no branch -- hence no wait -- separates the fetches.
-        bool const wantx = ax[i] != 0.0f, wanty = ay[i] != 0.0f;
-
-        o00[ph][i] = r0 + c0; o10[ph][i] = wantx ? r0 + c1 : -256; o01[ph][i] = wanty ? r1 + c0 : -256; o11[ph][i] = (wantx && wanty) ? r1 + c1 : -256;
-
-        int const bc0 = texel.bcolumn(i0), bc1 = texel.bcolumn(i1);
-        int const br0 = MAP_PART_B - texel.brow(j0), br1 = MAP_PART_B - texel.brow(j1);
-
-        q00[ph][i] = o00[ph][i] + br0 - bc0; q10[ph][i] = wantx ? o10[ph][i] + br0 - bc1 : -256; q01[ph][i] = wanty ? o01[ph][i] + br1 - bc0 : -256; q11[ph][i] = (wantx && wanty) ? o11[ph][i] + br1 - bc1 : -256;
-
-        near[ph] = near[ph] || wantx || wanty;
-      }
-
-      near[ph] = __builtin_amdgcn_ballot_w64(near[ph]) != 0;
+      #define OCEAN_GEN_TEXEL_SCALE p.scale
+      #include "ocean_gen_texel.inc"
+      #undef OCEAN_GEN_TEXEL_SCALE
 
       OCEAN_STAMP(1);
 
@@ -474,64 +361,14 @@ namespace ocean
 
         #undef OCEAN_GEN_BLENDN
 
-        // tbn[2] = normalize(-normal.xy, 1 - normal.z), tbn[0] = normalize(1 - tangent.x, -tangent.y, tangent.z), tbn[1] = tbn[0] x tbn[2]
-        p3 const t2 = normalize3(p3{ -f.nx * ct[ph], -f.ny * ct[ph], pfma(-f.nz, st[ph], 1.0f) });
-        p3 const t0 = normalize3(p3{ pfma(-f.tx, st[ph], 1.0f), -f.ty * st[ph], f.tz * ct[ph] });
-        p3 const t1 = { t0.y * t2.z - t0.z * t2.y, t0.z * t2.x - t0.x * t2.z, t0.x * t2.y - t0.y * t2.x };
-
-        // tbn * displacementnormal, mixed towards the plane normal with the distance smoothing
-        p3 const tn = { pfma(dn.z, t2.x, pfma(dn.y, t1.x, dn.x * t0.x)), pfma(dn.z, t2.y, pfma(dn.y, t1.y, dn.x * t0.y)), pfma(dn.z, t2.z, pfma(dn.y, t1.z, dn.x * t0.z)) };
-
-        v2 const keep = 1.0f - smoothing[ph];
-
-        tbn2 = normalize3(p3{ pfma(keep, tn.x, smoothing[ph] * planen.x), pfma(keep, tn.y, smoothing[ph] * planen.y), pfma(keep, tn.z, smoothing[ph] * planen.z) });
+        #include "ocean_gen_frame.inc"
       }
       else
         tbn2 = normalize3(planen);
 
       #undef OCEAN_GEN_BLEND
 
-      // tbn[0] = normalize((1, 0, 0) - tbn[2].x * tbn[2])
-      p3 const tbn0 = normalize3(p3{ pfma(-tbn2.x, tbn2.x, 1.0f), -tbn2.x * tbn2.y, -tbn2.x * tbn2.z });
-
-      OCEAN_STAMP(3);
-
-      //-- Mesh::Vertex { position3, texcoord2, normal3, tangent4 } = 48 bytes (src/renderer/mesh.h:20-26) -----------
-      // The wave's 4 rows x 32 vertices = 4 x 96 float4 go through its 6 KB of LDS: lane i then stores float4 number
-      // i, 64 + i, ... 320 + i of the wave's 384 (three 16-byte stores per vertex at a 48-byte stride touch every line three times).
-
-      v2 const px = position[ph].x - displacement.x, py = position[ph].y - displacement.y, pz = position[ph].z + displacement.z;
-      v2 const tu = 0.1f * position[ph].x, tv = 0.1f * position[ph].y;
-
-      #pragma unroll
-      for(int i = 0; i < 2; ++i)
-      {
-        float4 *vtx = mine + 3 * ((lane >> 4) * 32 + 16 * i + (lane & 15));
-
-        vtx[0] = make_float4(px[i], py[i], pz[i], tu[i]);
-        vtx[1] = make_float4(tv[i], tbn2.x[i], tbn2.y[i], tbn2.z[i]);
-        vtx[2] = make_float4(tbn0.x[i], tbn0.y[i], tbn0.z[i], -1.0f);
-      }
-
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-      int const y0 = ywave + 4 * ph;
-      int const rowlen = min(GEN_TILE_X, g.sizex - x0) * 3;                                // float4 of this tile in one mesh row
-
-      // (the wave's part of the address is uniform: a scalar base and a 32-bit offset per lane)
-      float4 *out = reinterpret_cast<float4*>(g.vertices) + ((size_t)y0 * g.sizex + x0) * 3;
-
-      #pragma unroll
-      for(int k = 0; k < 6; ++k)
-      {
-        int const j = 64 * k + lane;
-        int const r = j / 96, c = j % 96;
-
-        if (c < rowlen && y0 + r < g.sizey)
-          store_vertex_float4(out + (unsigned)(r * g.sizex * 3 + c), mine[j]);
-      }
+      #include "ocean_gen_store.inc"
 
     }
 

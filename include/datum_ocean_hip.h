@@ -46,7 +46,8 @@ extern "C" {
  *   9  the Jacobian foam plane: datum_ocean_set_foam, datum_ocean_set_foam_params, datum_ocean_reset_foam, datum_ocean_bind_foam,
  *      datum_ocean_foam_device, datum_ocean_read_foam, datum_ocean_upload_height.
  *      Later added at 9 without a bump (nothing changed, entry points were only added): the surface queries datum_ocean_sample_surface and
- *      datum_ocean_read_surface; then the phase write-back interval, datum_ocean_set_phase_writeback and datum_ocean_phase_writeback.  A consumer
+ *      datum_ocean_read_surface; then the phase write-back interval, datum_ocean_set_phase_writeback and datum_ocean_phase_writeback; then
+ *      the several-cascade calls datum_ocean_gen_blend, datum_ocean_sample_surface_blend and datum_ocean_read_surface_blend.  A consumer
  *      that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -332,6 +333,54 @@ int datum_ocean_sample_surface(datum_ocean_t ctx, int cascade, datum_ocean_set c
                                void const *points_device, size_t count, void *samples_device);
 int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, int iterations,
                              float const *points, size_t count, float *samples);
+
+/* -- several cascades at once (added at ABI 9; nothing in the reference, whose example samples one cascade) ------------------------
+ * A cascaded ocean is a few grids of different wavescale SUMMED at every vertex.  These calls are datum_ocean_gen and the surface queries
+ * for that sum: one call gives the mesh of the summed surface, one call the height, normal and foam of the same surface above world points.
+ * (Four gen launches added up by the caller repeat the ray stage and write 4 x 48 bytes per vertex; the queries cannot be added up at all:
+ * the fixed-point solve V(b).xy = q is not additive over cascades.)
+ *
+ * All cascades of a handle share N.  A blend is a list cascades[count], 1 <= count <= DATUM_OCEAN_MAX_CASCADES, every entry in
+ * [0, cascades of the handle); a cascade may be listed again and is then summed again.  Cascade c is sampled with the scale the HANDLE holds
+ * for it, scale_c = 1 / wavescale as set by datum_ocean_set_cascade or datum_ocean_rebuild_height; set->scale is ignored.  Every other
+ * field of the set means what it means to datum_ocean_gen and to the single-cascade query.
+ *
+ * For a position P (gen's position.xy after the swell; the query's P(b)) each listed cascade contributes, in list order:
+ *
+ *     t_c      = P.xy · scale_c
+ *     D_c, m_c = layer 0 (dx, dy, dz) and layer 1 (normal) of cascade c at t_c: gen's REPEAT bilinear fetch -- the same weights, fract wrap
+ *                and blend order, zero-weight corners pushed out of the buffer
+ *     D        = D_c of the first listed cascade as it is; each further D_c added in list order, one fp32 addition per component.  A
+ *                one-element list therefore gives the single-cascade call's bits (with set->scale = scale_c)
+ *     p_c      = ( m_c.x / m_c.z,  m_c.y / m_c.z )          the map stores m = normalize(l.z − r.z, b.z − t.z, 4·wavescale/N), so
+ *                m.x / m.z = −½ ∂z/∂x in world units for every cascade: SLOPES add, unit normals do not.  m_c.z > 0 in every texel
+ *     p        = Σ p_c  in list order
+ *     dn       = normalize(p.x, p.y, 1)
+ *
+ * dn takes the place of gen's displacementnormal in gen's shading (gen.comp:101-120); in the query it feeds
+ * normalize(t0·dn.x + t1·dn.y + t2·dn.z).  The mesh vertex is gen's with D and dn as above; texcoord stays 0.1 · position.xy.  The query
+ * record stays DATUM_OCEAN_SURFACE_SAMPLE_FLOATS = 8 floats with the same meaning:
+ *
+ *     V(b)  = ( P.x − D.x,  P.y − D.y,  −plane.w + A · sin θ + D.z )
+ *
+ * with exactly `iterations` updates b ← b + (q − V(b).xy) and no early exit.  The iteration converges where the SUMMED surface is a height
+ * field (the Jacobian of P − D.xy over the list is positive); elsewhere the residual stays large, as in the single-cascade query.  A
+ * non-finite q gives a record of quiet NaNs and fetches nothing.  Foam (field 7), from the listed cascades' planes sampled at t_c:
+ *     DATUM_OCEAN_FOAM_ACCUMULATE   the largest sampled coverage of the list
+ *     DATUM_OCEAN_FOAM_JACOBIAN     1 + Σ (J_c − 1): the Jacobian of the summed displacement to first order -- the cross terms between
+ *                                   cascades (products of two cascades' gradients) are left out
+ *     DATUM_OCEAN_FOAM_OFF          0
+ *
+ * Ordering and alignment are the single-cascade calls': every launch goes on the handle's stream behind the last displace, applies no
+ * pending update and reads maps and foam planes as they lie (own buffers or bound ones).  read_surface_blend is sample_surface_blend from
+ * HOST arrays, blocking, through the staging buffers datum_ocean_read_surface uses.  DATUM_OCEAN_EINVAL for a null list, count outside
+ * [1, DATUM_OCEAN_MAX_CASCADES] or an entry out of range; otherwise the single-cascade calls' errors.  n == 0 enqueues nothing. */
+int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey,
+                          void *vertices_device);
+int datum_ocean_sample_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                     void const *points_device, size_t n, void *samples_device);
+int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                   float const *points, size_t n, float *samples);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -15,6 +15,12 @@
 //
 // The phase advance is the general fmodf kernel (ocean_advance_kernel: update_ocean, ocean.cpp:217-236).  It moves 196 B/pt like the
 // reference and takes 4-17 x the fused step (tools/literal_bench.py: 44 us at 64^2, 211 us at 1024^2, 4.7 ms at 4096^2); nothing in bench.py runs it.
+//
+// What is held (tests/test_gpu_literal_pointwise.py): EVERY texel of all six channels within K_LIT * eps * log2 N (eps = 2^-24, relative to
+// the channel's RMS; the normals in the form of tests/test_gpu_pointwise.py) of the float64 evaluation of the reference's algorithm on the
+// reference's fp32 table (tests/ref64.py: lit64) -- at 64^2, 256^2, 1024^2 (fewer lanes than threads, one, four per thread), per cascade, and
+// for single bins at the corners, at k = 0 and on one row / column; at 2048^2 and 4096^2 within twice that of the fp32 oracle.  K_LIT is
+// 3 x the error of the reference's own fp32 arithmetic on the CPU against lit64 (tests/test_lit64.py, tests/pointwise.py).
 
 #pragma once
 

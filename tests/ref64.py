@@ -3,6 +3,8 @@ oracle/ocean_oracle.cpp restates them, and the two-field packing of include/datu
 
   sim64       ocean.sim from the fp32 inputs: partner h0 at (N-1-y, N-1-x) with only the bin's own phase, k = 0 guarded
   displace64  the exact 2-D inverse transform of sim64's three fields, (-1)^(x+y), ocean.map's six channels
+  lit64       the same channels through the reference's LITERAL algorithm (log2 N radix-2 Stockham stages per line, twiddles read
+              from a table handed in): what datum_ocean_set_literal_transform runs (ocean_literal.hip), in float64
   rowpass64   the packed fields C, D (datum_ocean_debug_rowpass) and their exact row transform
   colpass64   from any row-pass output (the GPU's own included): the exact column transform and the column kernel's map stage
   fp16_scales the power-of-two exponents the fp16 formats pick from max |h0| (ocean_capi.hip: size_spectrum_scale)
@@ -85,10 +87,78 @@ def displace64(h0, phase, scale, chop, return_len=False):
     del hx
     out[1] = transform2(hy).real * sg * float(chop)
     del hy, sg
+    ln = _map_normals(out, scale)
+    return (out, ln) if return_len else out
+
+
+def _map_normals(out, scale):
+    """ocean.map's normal from out[2] = dz into out[3:6]: central differences with wrap-around, nz = 4 / (scale N) (map.comp:58-78);
+    returns the length before normalisation"""
     dz = out[2]
     nx = np.roll(dz, 1, axis=1) - np.roll(dz, -1, axis=1)      # dz(x-1) - dz(x+1)
     ny = np.roll(dz, -1, axis=0) - np.roll(dz, 1, axis=0)      # dz(y+1) - dz(y-1)
-    ln = _normals(out, nx, ny, _nz(N, scale))
+    return _normals(out, nx, ny, _nz(dz.shape[0], scale))
+
+
+def normal_len(dz, scale):
+    """|(nx, ny, nz)| before normalisation [N][N] in float64, from any dz [N][N] (ocean.map's differences, as displace64's return_len)"""
+    dz = np.asarray(dz, np.float64)
+    nx = np.roll(dz, 1, axis=1) - np.roll(dz, -1, axis=1)
+    ny = np.roll(dz, -1, axis=0) - np.roll(dz, 1, axis=0)
+    nz = _nz(dz.shape[0], scale)
+    return np.sqrt(nx * nx + ny * ny + nz * nz)
+
+
+def twiddles64(N):
+    """the table of ocean.cpp:686-700 in its layout [N][2 log2 N] (cos, sin per stage s of lane i), evaluated accurately: the angle
+    -2 pi i / 2^(s+1) with the lane index reduced modulo the stage's period 2^(s+1) first, in float64"""
+    stages = N.bit_length() - 1
+    i = np.arange(N)
+    w = np.empty((N, 2 * stages), np.float64)
+    for s in range(stages):
+        period = 2 << s
+        a = -TWO_PI * (i % period) / period
+        w[:, 2 * s] = np.cos(a)
+        w[:, 2 * s + 1] = np.sin(a)
+    return w
+
+
+def stockham64(f, w, axis):
+    """one dispatch of ocean.fftx (axis = 1: every row) or ocean.ffty (axis = 0: every column) on a complex128 plane [N][N]:
+    conjugate, log2 N stages dst[i] = src[i0] + (t0 + i t1) src[i0 + N/2] with i0 = (i / n) (n / 2) + i % (n / 2), n = 2, 4 .. N
+    and (t0, t1) = w[i][2 s], w[i][2 s + 1] -- the twiddle of the FULL lane index i --, conjugate (fftx.comp:55-99).
+    One gather per stage over the whole plane; w is used value for value (float64)."""
+    N = f.shape[0]
+    stages = N.bit_length() - 1
+    assert 1 << stages == N and w.shape == (N, 2 * stages)
+    i = np.arange(N)
+    src = np.conj(f if axis == 1 else f.T)
+    for s in range(stages):
+        n = 2 << s
+        i0 = (i // n) * (n // 2) + i % (n // 2)
+        t = w[:, 2 * s] + 1j * w[:, 2 * s + 1]
+        src = src[:, i0] + t[None, :] * src[:, i0 + N // 2]
+    src = np.conj(src)
+    return src if axis == 1 else np.ascontiguousarray(src.T)
+
+
+def lit64(h0, phase, scale, chop, w, return_len=False):
+    """The literal transform mode in float64: ocean.sim (sim64), for each of the three planes ocean.fftx then ocean.ffty as radix-2
+    Stockham stages reading the table w [N][2 log2 N] (the fp32 table the module serves, datum_ocean_reference_weights, converted value
+    for value; or any other), then ocean.map: (-1)^(x+y), choppiness on dx and dy, the central-difference normal with wrap-around and
+    nz = 4 / (scale N).  [6][N][N] (dx, dy, dz, nx, ny, nz) like displace64; it is not an FFT and inherits the table's error."""
+    N = phase.shape[0]
+    w = np.asarray(w, np.float64)
+    sg = _sign(N)
+    out = np.empty((6, N, N), np.float64)
+    h, hx, hy = sim64(h0, phase, scale)
+    out[2] = stockham64(stockham64(h, w, 1), w, 0).real * sg
+    del h
+    out[0] = stockham64(stockham64(hx, w, 1), w, 0).real * sg * float(chop)
+    del hx
+    out[1] = stockham64(stockham64(hy, w, 1), w, 0).real * sg * float(chop)
+    del hy, sg
+    ln = _map_normals(out, scale)
     return (out, ln) if return_len else out
 
 

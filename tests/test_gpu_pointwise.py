@@ -26,11 +26,11 @@ import numpy as np
 import pytest
 
 import ref64
+from pointwise import EPS, pointwise as _pointwise, rms as _rms          # the error forms, shared with the literal mode's tests
 
 pytestmark = pytest.mark.gpu
 
 DT = np.float32(1.0 / 60.0)
-EPS = 2.0 ** -24
 
 # Bars: at least 3x the worst value measured on the MI355X over every case of this file (the measured worst beside each).
 K_MAP = 9.0             # random fields, every form, format and N, end to end (fp32) and column pass: measured 2.89 (512^2 fp32, e2e)
@@ -52,39 +52,10 @@ def capi():
     return c
 
 
-def _rms(a):
-    return float(np.sqrt(np.mean(np.square(a, dtype=np.float64))))
-
-
 def _state(oracle, N, rngseed, wavescale):
     p = oracle.EXAMPLE
     _, h0 = oracle.seed(N, rngseed, wavescale, p["waveamplitude"], p["windspeed"], p["winddirection"], sanitize=True)
     return h0
-
-
-def _pointwise(got, ref, ln, N, structure):
-    """(K of the displacement channels, K of the normal channels, normalised error energy per point or None): K is the worst
-    |got - ref| over the bar's scale, i.e. the smallest K_MAP / K_NORMAL that passes"""
-    L = np.log2(N)
-    s = [_rms(ref[ch]) for ch in range(3)]
-    sall = float(np.sqrt(np.mean(np.square(s))))
-    s = [max(v, 0.25 * sall, 1e-30) for v in s]
-    energy = np.zeros((N, N)) if structure else None
-    kd = 0.0
-    for ch in range(3):
-        e = np.abs(got[ch] - ref[ch]) / (EPS * L * s[ch])
-        kd = max(kd, float(e.max()))
-        if structure:
-            energy += e * e
-    rn = float(np.sqrt(np.mean(np.square(ref[3] * ln) + np.square(ref[4] * ln)) / 2))
-    den = EPS * (L * (rn + s[2]) / ln + 1.0)
-    kn = 0.0
-    for ch in range(3, 6):
-        e = np.abs(got[ch] - ref[ch]) / den
-        kn = max(kn, float(e.max()))
-        if structure:
-            energy += e * e
-    return kd, kn, energy
 
 
 def _structure(energy):

@@ -127,6 +127,8 @@ SYMBOLS = {
     "datum_ocean_gen_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, P]),
     "datum_ocean_sample_surface_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_surface_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_reduce_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
 }
 
 
@@ -147,6 +149,27 @@ FOAM_MODES = {"off": FOAM_OFF, "jacobian": FOAM_JACOBIAN, "accumulate": FOAM_ACC
 # surface queries (datum_ocean_sample_surface, added at ABI 9): floats per record and the largest iteration count
 SURFACE_SAMPLE_FLOATS = 8
 SURFACE_MAX_ITERATIONS = 16
+
+# body buoyancy (datum_ocean_reduce_bodies, added at ABI 9): floats per body record and per probe
+BODY_RECORD_FLOATS = 8
+BODY_PROBE_FLOATS = 4
+
+
+class Body(ctypes.Structure):
+    """datum_ocean_body of include/datum_ocean_hip.h: 64 bytes"""
+
+    _fields_ = [
+        ("rotation", F * 9),
+        ("position", F * 3),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("cap", F),
+        ("pad", ctypes.c_int32),
+    ]
+
+
+# the same layout for numpy: an array of this dtype is an array of Body
+BODY_DTYPE = np.dtype([("rotation", np.float32, 9), ("position", np.float32, 3), ("first", np.int32), ("count", np.int32), ("cap", np.float32), ("pad", np.int32)])
 
 
 def header_abi_version():
@@ -564,6 +587,25 @@ class Ocean:
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
         out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
+
+    # -- body buoyancy (datum_ocean_reduce_bodies): per-body force and torque from hull probes -----------------------------------------
+
+    def reduce_bodies(self, cascades, oceanset, bodies_ptr, nbodies, probes_ptr, nprobes, records_ptr, iterations=4):
+        """Enqueue the reduction of `nbodies` bodies (device pointer, 64 bytes each) over `nprobes` probes (device pointer, 16 bytes each:
+        x, y, z, weight) into `nbodies` records of 8 floats (device pointer): Fz, tau x, tau y, wet, sum m n, max residual."""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_reduce_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None, nbodies,
+                                                       P(probes_ptr) if probes_ptr else None, nprobes, P(records_ptr) if records_ptr else None))
+
+    def read_bodies(self, cascades, oceanset, bodies, probes, iterations=4):
+        """the same from host arrays, blocking: `bodies` an array of BODY_DTYPE (or of Body), `probes` (n, 4) float32; returns (nbodies, 8)"""
+        arr, n = self._list(cascades)
+        b = np.ascontiguousarray(np.frombuffer(bytes(bodies), BODY_DTYPE) if isinstance(bodies, ctypes.Array) else bodies)
+        assert b.dtype.itemsize == ctypes.sizeof(Body)
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
+        out = np.empty((b.shape[0], BODY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
         return out
 
     def algorithmic_bytes(self):

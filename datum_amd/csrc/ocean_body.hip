@@ -1,0 +1,174 @@
+// ocean_body.hip -- body buoyancy (include/datum_ocean_hip.h: datum_ocean_reduce_bodies): per body, the net buoyant force, its torque and a
+// few aggregates over the body's hull probes, each probe moved to world space with the body's pose and held against the summed surface
+// above it.  The arithmetic of a probe and the order of the sum are ocean_body.h's (a CPU walks the same functions); the surface record of
+// a probe is the several-cascade query's, the same text (ocean_surface_blend_point.inc), so its bits are datum_ocean_sample_surface_blend's.
+//
+//   * one wave per body, four bodies per 256-thread workgroup; lane l takes probes first + l, first + l + 64, ...;
+//   * a probe is one 16-byte load per lane, 64 consecutive probes per wave and pass, through a buffer resource laid over exactly the
+//     probes of that pass: no first / count can reach outside the probe array (a bad range is refused before, body_range_bad);
+//   * the body's 64 bytes are read with a wave-uniform index: scalar loads;
+//   * the 64 partials are added across lanes in registers -- the half exchange of v_permlane32_swap and v_permlane16_swap for the strides
+//     32 and 16, DPP row shifts below -- every lane alive to the end; lane 0 stores the record, two 16-byte stores;
+//   * a bad probe fetches nothing; its body's record is eight quiet NaNs.
+// No LDS, no barrier, no atomics, no scratch (make resource-usage).
+
+#pragma once
+
+#include "ocean_body.h"
+#include "ocean_blend.hip"
+
+namespace ocean
+{
+  struct BodyArgs
+  {
+    SurfaceArgs s;          // s.set, s.frame, s.N and s.iterations are read
+    BlendList list;
+    datum_ocean_body const *bodies;
+    BodyProbe const *probes;
+    float4 *records;        // 2 float4 per body
+    int nbodies;
+    int nprobes;
+  };
+
+  constexpr int BODY_THREADS = 256;
+  constexpr int BODY_WAVES = BODY_THREADS / BODY_LANES;
+
+  // lane l + S's value in lane l, for l < S (what the other lanes get is not used)
+  template<int S>
+  __device__ __forceinline__ float body_lane_up(float v)
+  {
+    unsigned int const u = __builtin_bit_cast(unsigned int, v);
+
+    // v_permlane32_swap a, b exchanges lanes 32-63 of a with lanes 0-31 of b, v_permlane16_swap the odd rows (of 16 lanes) of a with the
+    // even rows of b: given the same value twice, b then holds lane l + S's value in lane l; the builtin returns (a, b).  (The element
+    // goes through a scalar: __builtin_bit_cast applied to the element itself read element 0 with this compiler)
+    if constexpr (S == 32)
+    {
+      unsigned int const b = __builtin_amdgcn_permlane32_swap(u, u, false, false)[1];
+      return __builtin_bit_cast(float, b);
+    }
+    else if constexpr (S == 16)
+    {
+      unsigned int const b = __builtin_amdgcn_permlane16_swap(u, u, false, false)[1];
+      return __builtin_bit_cast(float, b);
+    }
+    else
+      return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, (int)u, 0x100 + S, 0xF, 0xF, true));   // row_shl:S
+  }
+
+  // the wave's 64 partials, one per lane (ocean_body.h: body_tree)
+  struct BodyWave
+  {
+    BodyPartial p;
+
+    template<int S>
+    __device__ __forceinline__ void step()
+    {
+      BodyPartial o;
+
+      #pragma unroll
+      for(int k = 0; k < BODY_FIELDS; ++k)
+        o.f[k] = body_lane_up<S>(p.f[k]);
+
+      body_add(p, o);
+    }
+  };
+
+  template<int LAYOUT>
+  __global__ void __launch_bounds__(BODY_THREADS) ocean_body_kernel(BodyArgs a)
+  {
+    int const lane = (int)threadIdx.x & (BODY_LANES - 1);
+    int const body = __builtin_amdgcn_readfirstlane((int)blockIdx.x * BODY_WAVES + ((int)threadIdx.x >> 6));
+
+    // (the whole wave: the last workgroup's waves without a body)
+    if (body >= a.nbodies)
+      return;
+
+    SurfaceArgs const &s = a.s;
+    datum_ocean_set const &p = s.set;
+    GenFrame const &f = s.frame;
+    BlendList const &list = a.list;
+
+    datum_ocean_body const B = a.bodies[body];
+
+    bool bad = body_range_bad(B, a.nprobes);
+
+    int const n = bad ? 0 : B.count;
+
+    BodyWave wave;
+    wave.p = body_zero();
+
+    bool badprobe = false;
+
+    // lane 0 has the most probes: every lane walks its passes (wave-uniform), `have` says whether a pass holds a probe for this lane
+    for(int k = 0; k < body_lane_probes(n, 0); ++k)
+    {
+      // this pass's probes and nothing else: lanes beyond the body's last probe load zeros
+      int const left = n - k * BODY_LANES;
+
+      __amdgpu_buffer_rsrc_t const rprobes = make_rsrc(a.probes + (size_t)body_lane_probe(B.first, 0, k), (size_t)(left < BODY_LANES ? left : BODY_LANES) * sizeof(BodyProbe));
+
+      float4 const raw = buf_load_f32x4_aux<0>(rprobes, lane * (int)sizeof(BodyProbe), 0);
+
+      BodyProbe const probe = { raw.x, raw.y, raw.z, raw.w };
+
+      BodyWorld const w = body_transform(B, probe);
+
+      bool const have = k < body_lane_probes(n, lane);
+      bool const probebad = body_probe_bad(w, probe.a);
+
+      badprobe = badprobe || (have && probebad);
+
+      if (have && !probebad)
+      {
+        float rec[DATUM_OCEAN_SURFACE_SAMPLE_FLOATS];
+
+        {
+          float2 const q = make_float2(w.x, w.y);
+
+          #include "ocean_surface_blend_point.inc"
+
+          rec[0] = vx; rec[1] = vy; rec[2] = vz; rec[3] = residual;
+          rec[4] = mx; rec[5] = my; rec[6] = mz; rec[7] = foam;
+        }
+
+        body_add(wave.p, body_terms(B, w, probe.a, rec));
+      }
+    }
+
+    bad = bad || __builtin_amdgcn_ballot_w64(badprobe) != 0;
+
+    body_tree(wave);
+
+    if (lane == 0)
+    {
+      float const nan = __builtin_nanf("");
+
+      float const *r = wave.p.f;
+
+      __amdgpu_buffer_rsrc_t const rrecord = make_rsrc(a.records + 2 * (size_t)body, 2 * sizeof(float4));
+
+      buf_store_f32x4_aux<0>(bad ? make_float4(nan, nan, nan, nan) : make_float4(r[0], r[1], r[2], r[3]), rrecord, 0, 0);
+      buf_store_f32x4_aux<0>(bad ? make_float4(nan, nan, nan, nan) : make_float4(r[4], r[5], r[6], r[7]), rrecord, 16, 0);
+    }
+  }
+
+  inline void const *body_kernel_for(int N)
+  {
+    switch(gen_layout(N))
+    {
+      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_body_kernel<GEN_PLAIN>);
+      default: return reinterpret_cast<void const*>(&ocean_body_kernel<GEN_BANDED>);
+    }
+  }
+
+  // a.s.set, N, iterations, a.list, bodies, probes, records, nbodies (> 0) and nprobes filled in
+  inline hipError_t launch_bodies(BodyArgs &a, hipStream_t stream)
+  {
+    a.s.frame = make_gen_frame(a.s.set, a.s.N, 2, 2);      // the camera's terms are not read
+
+    void *args[] = { &a };
+
+    return hipLaunchKernel(body_kernel_for(a.s.N), dim3((unsigned)(((size_t)a.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
+  }
+}

@@ -23,6 +23,7 @@
 #include "ocean_foam.hip"
 #include "ocean_surface.hip"
 #include "ocean_blend.hip"
+#include "ocean_body.hip"
 
 using namespace ocean;
 
@@ -119,6 +120,13 @@ struct datum_ocean_ctx
   float2 *surfacepoints = nullptr;
   float4 *surfacesamples = nullptr;
   size_t surfacecapacity = 0;         // points both hold
+
+  // datum_ocean_read_bodies' device staging, each grown on demand: bodies with their records, and probes
+  datum_ocean_body *bodystage = nullptr;
+  float4 *bodyrecords = nullptr;
+  size_t bodycapacity = 0;            // bodies both hold
+  BodyProbe *probestage = nullptr;
+  size_t probecapacity = 0;
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -896,6 +904,9 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->foam.own);
   (void)hipFree(ctx->surfacepoints);
   (void)hipFree(ctx->surfacesamples);
+  (void)hipFree(ctx->bodystage);
+  (void)hipFree(ctx->bodyrecords);
+  (void)hipFree(ctx->probestage);
 
   if (ctx->ownstream)
     (void)hipStreamDestroy(ctx->ownstream);
@@ -2247,6 +2258,139 @@ int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int c
 
   HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(samples, ctx->surfacesamples, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
+/* -- body buoyancy (ocean_body.hip) -------------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // the checks both entry points share; `name` goes into the error text
+  int check_body_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
+                      void const *probes, size_t nprobes, void const *records, char const *name)
+  {
+    int rc = check_blend_list(ctx, cascades, count, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (!set)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
+
+    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
+
+    if ((nbodies > 0 && (!bodies || !records)) || (nprobes > 0 && !probes))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null bodies, probes or records").c_str());
+
+    if (((uintptr_t)bodies & 15) || ((uintptr_t)probes & 15) || ((uintptr_t)records & 15))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": bodies, probes and records must be 16-byte aligned").c_str());
+
+    if (nbodies > (size_t)INT32_MAX || nprobes > (size_t)INT32_MAX)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": nbodies or nprobes above INT32_MAX").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  BodyArgs body_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
+                     void const *probes, size_t nprobes, void *records)
+  {
+    BodyArgs a;
+    a.s = surface_args(ctx, cascades[0], set, iterations, nullptr, 0, nullptr);
+    a.s.map = nullptr;
+    a.s.foam = nullptr;
+    a.list = blend_list(ctx, cascades, count);
+    a.bodies = static_cast<datum_ocean_body const*>(bodies);
+    a.probes = static_cast<BodyProbe const*>(probes);
+    a.records = static_cast<float4*>(records);
+    a.nbodies = (int)nbodies;
+    a.nprobes = (int)nprobes;
+    return a;
+  }
+
+  // the host entry point's device staging of `nbodies` bodies with their records and of `nprobes` probes, each grown on demand, the
+  // arrays copied in on the handle's stream
+  int stage_bodies(datum_ocean_ctx *ctx, datum_ocean_body const *bodies, size_t nbodies, float const *probes, size_t nprobes)
+  {
+    if (nbodies > ctx->bodycapacity || nprobes > ctx->probecapacity)
+    {
+      // the old staging may still be read by an earlier launch of this stream
+      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+      if (nbodies > ctx->bodycapacity)
+      {
+        HIPCHECK(ctx, hipFree(ctx->bodystage));
+        HIPCHECK(ctx, hipFree(ctx->bodyrecords));
+        ctx->bodystage = nullptr;
+        ctx->bodyrecords = nullptr;
+        ctx->bodycapacity = 0;
+
+        HIPCHECK(ctx, hipMalloc(&ctx->bodystage, nbodies * sizeof(datum_ocean_body)));
+        HIPCHECK(ctx, hipMalloc(&ctx->bodyrecords, nbodies * 2 * sizeof(float4)));
+        ctx->bodycapacity = nbodies;
+      }
+
+      if (nprobes > ctx->probecapacity)
+      {
+        HIPCHECK(ctx, hipFree(ctx->probestage));
+        ctx->probestage = nullptr;
+        ctx->probecapacity = 0;
+
+        HIPCHECK(ctx, hipMalloc(&ctx->probestage, nprobes * sizeof(BodyProbe)));
+        ctx->probecapacity = nprobes;
+      }
+    }
+
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->bodystage, bodies, nbodies * sizeof(datum_ocean_body), hipMemcpyHostToDevice, ctx->stream));
+
+    if (nprobes > 0)
+      HIPCHECK(ctx, hipMemcpyAsync(ctx->probestage, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_reduce_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                              void const *bodies_device, size_t nbodies, void const *probes_device, size_t nprobes, void *records_device)
+{
+  int rc = check_body_args(ctx, cascades, count, set, iterations, bodies_device, nbodies, probes_device, nprobes, records_device, "datum_ocean_reduce_bodies");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  BodyArgs a = body_args(ctx, cascades, count, set, iterations, bodies_device, nbodies, probes_device, nprobes, records_device);
+
+  HIPCHECK(ctx, launch_bodies(a, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                            datum_ocean_body const *bodies, size_t nbodies, float const *probes, size_t nprobes, float *records)
+{
+  int rc = check_body_args(ctx, cascades, count, set, iterations, bodies, nbodies, probes, nprobes, records, "datum_ocean_read_bodies");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  rc = stage_bodies(ctx, bodies, nbodies, probes, nprobes);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  BodyArgs a = body_args(ctx, cascades, count, set, iterations, ctx->bodystage, nbodies, ctx->probestage, nprobes, ctx->bodyrecords);
+
+  HIPCHECK(ctx, launch_bodies(a, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->bodyrecords, nbodies * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;

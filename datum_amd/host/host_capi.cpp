@@ -329,6 +329,16 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_reduce_ocean_bodies(void *c, void *p, void const *bodies, size_t nbodies, float const *probes, size_t nprobes, float *records, int iterations)
+  {
+    try
+    {
+      reduce_ocean_bodies(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), static_cast<datum_ocean_body const*>(bodies), nbodies, reinterpret_cast<OceanBodyProbe const*>(probes), nprobes, reinterpret_cast<OceanBodyRecord*>(records), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

@@ -891,6 +891,20 @@ void query_ocean_surface(OceanContext &context, OceanParams const &params, Vec2 
 }
 
 
+///////////////////////// reduce_ocean_bodies ///////////////////////////////
+void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, size_t nbodies, OceanBodyProbe const *probes, size_t nprobes, OceanBodyRecord *records, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("reduce_ocean_bodies: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_bodies(context.hip, &cascade, 1, &set, iterations, bodies, nbodies, reinterpret_cast<float const*>(probes), nprobes, reinterpret_cast<float*>(records)), "datum_ocean_read_bodies");
+}
+
+
 ///////////////////////// read_ocean_displacement ///////////////////////////
 void read_ocean_displacement(OceanContext &context, float *maps)
 {

@@ -356,6 +356,29 @@ static_assert(sizeof(OceanSurfaceSample) == 32, "OceanSurfaceSample must be the 
 
 void query_ocean_surface(OceanContext &context, OceanParams const &params, lml::Vec2 const *positions, std::size_t count, OceanSurfaceSample *samples, int iterations = 4);
 
+// body buoyancy (include/datum_ocean_hip.h: datum_ocean_read_bodies, the definition there): per body the net buoyant force, its torque
+// and a few aggregates over the body's hull probes, reduced on the device.  One cascade, as query_ocean_surface; the maps the context last
+// displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before prepare_ocean_context
+struct OceanBodyProbe
+{
+  lml::Vec3 position;                     // body-local, metres
+  float weight;                           // the cross-section the probe stands for, m^2 (the result is linear in it: fold rho g in, or multiply after)
+};
+
+struct OceanBodyRecord
+{
+  float force;                            // Fz = sum weight * submersion
+  float torquex, torquey;                 // about the body origin
+  float wet;                              // sum of the weights of the submerged probes
+  lml::Vec3 normal;                       // sum of (weight * submersion) * the surface normal above the probe
+  float residual;                         // the largest residual of the probes' surface records
+};
+
+static_assert(sizeof(OceanBodyProbe) == 16, "OceanBodyProbe must be the C ABI's probe");
+static_assert(sizeof(OceanBodyRecord) == 32, "OceanBodyRecord must be the C ABI's record of DATUM_OCEAN_BODY_RECORD_FLOATS floats");
+
+void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, OceanBodyRecord *records, int iterations = 4);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

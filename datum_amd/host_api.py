@@ -98,6 +98,7 @@ def load():
             "datum_host_set_ocean_foam_params": (I, [P, F, F, F]),
             "datum_host_read_ocean_foam": (I, [P, P]),
             "datum_host_query_ocean_surface": (I, [P, P, P, ctypes.c_size_t, P, I]),
+            "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -309,6 +310,16 @@ class OceanContext:
         pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         out = np.empty((pts.shape[0], capi.SURFACE_SAMPLE_FLOATS), np.float32)
         self._check(self.lib.datum_host_query_ocean_surface(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
+        return out
+
+    def reduce_ocean_bodies(self, params, bodies, probes, iterations=4):
+        """reduce_ocean_bodies: `bodies` an array of capi.BODY_DTYPE, `probes` (n, 4) float32 (x, y, z, weight); returns (nbodies, 8) float32
+        records (OceanBodyRecord: force, torque x, torque y, wet, weighted normal, largest residual)"""
+        b = np.ascontiguousarray(bodies)
+        assert b.dtype.itemsize == ctypes.sizeof(capi.Body)
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
+        out = np.empty((b.shape[0], capi.BODY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_reduce_ocean_bodies(self.c, params.p, b.ctypes.data_as(P), b.shape[0], pr.ctypes.data_as(P), pr.shape[0], out.ctypes.data_as(P), iterations))
         return out
 
     def read_vertices(self, mesh):

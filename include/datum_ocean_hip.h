@@ -47,8 +47,9 @@ extern "C" {
  *      datum_ocean_foam_device, datum_ocean_read_foam, datum_ocean_upload_height.
  *      Later added at 9 without a bump (nothing changed, entry points were only added): the surface queries datum_ocean_sample_surface and
  *      datum_ocean_read_surface; then the phase write-back interval, datum_ocean_set_phase_writeback and datum_ocean_phase_writeback; then
- *      the several-cascade calls datum_ocean_gen_blend, datum_ocean_sample_surface_blend and datum_ocean_read_surface_blend.  A consumer
- *      that needs them detects them by symbol (dlsym), not by the version */
+ *      the several-cascade calls datum_ocean_gen_blend, datum_ocean_sample_surface_blend and datum_ocean_read_surface_blend; then body
+ *      buoyancy, datum_ocean_reduce_bodies and datum_ocean_read_bodies.  A consumer that needs them detects them by symbol (dlsym), not
+ *      by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
 
@@ -381,6 +382,62 @@ int datum_ocean_sample_surface_blend(datum_ocean_t ctx, int const *cascades, int
                                      void const *points_device, size_t n, void *samples_device);
 int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                    float const *points, size_t n, float *samples);
+
+/* -- body buoyancy (added at ABI 9; nothing in the reference) ------------------------------------------------------------------------
+ * Bodies floating on the summed surface: per body the net buoyant force, its torque about the body origin and a few aggregates, reduced on
+ * the device from the body's hull probes.  (With the surface queries alone a caller transforms every probe, uploads 8 bytes and reads back
+ * 32 bytes per probe and sums on the host; here 32 bytes per BODY come back.)
+ *
+ * A call takes a blend list cascades[count] -- the several-cascade calls' rules, the handle's scale_c, set->scale ignored; a one-element
+ * list is the single-cascade case -- a set, an iteration count and two DEVICE arrays:
+ *     probe, 16 bytes    (x, y, z, a): the body-local position in metres and the weight a, the cross-section the probe stands for in m².
+ *                        The result is linear in a: fold ρ·g into it or multiply afterwards
+ *     body, 64 bytes     datum_ocean_body below: rotation (row-major, local → world), position, the body's range [first, first + count)
+ *                        of the probe array (ranges may share probes), and cap, the largest submersion one probe may report (the hull's
+ *                        height above the probe; +inf: none)
+ *
+ * For probe i of body B, with R = rotation, T = position, every operation one fp32 operation as written (no contraction):
+ *
+ *     w.x = ((R[0]·x + R[1]·y) + R[2]·z) + T.x          w.y, w.z with rows 1, 2
+ *     rec = the record of datum_ocean_sample_surface_blend for q = (w.x, w.y) with this list, set and iterations, bit for bit
+ *     d   = min(max(rec.z − w.z, 0), cap)                submersion
+ *     m   = a · d                                        force term, vertical (Archimedes)
+ *     r   = (w.x − T.x, w.y − T.y)                       lever arm about the body origin
+ *     terms: Fz = m,  τx = r.y · m,  τy = −(r.x · m),  wet = (d > 0 ? a : 0),  nx, ny, nz = m · rec.normal,  res = rec.residual
+ *
+ * Each body gets a record of DATUM_OCEAN_BODY_RECORD_FLOATS = 8 floats (32 bytes):
+ *     Fz, τx, τy, wet, Σ m·n.x, Σ m·n.y, Σ m·n.z, max residual
+ * The order of the sum is part of the definition, so that a result repeats from run to run and can be checked on a CPU: lane l (0 … 63)
+ * holds one partial per field, started at +0.0f, and adds the terms of probes first + l, first + l + 64, … in increasing order; then for
+ * s = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l + s] for l < s; p[0] is the record.  Field 7 is the maximum (fmaxf) instead of the sum.
+ * count == 0 gives eight zeros.  A body's record is eight quiet NaNs, and nothing is fetched for its bad probes, if its range is not
+ * inside the probe array (first < 0, count < 0 or first + count > nprobes), if cap is a NaN, or if any probe of it has a non-finite w or a.
+ * No index can fault: a body is read only for an index below nbodies, a probe only through a buffer resource laid over probes of its
+ * body's range, after that range was found to lie inside the probe array.
+ * A hull of more than a few thousand probes is better split into several bodies of the same pose: the records add, field 7 is their maximum.
+ *
+ *   reduce_bodies   enqueue and return: one kernel on the handle's stream behind the last displace; it applies no pending update and reads
+ *                   maps and foam planes as they lie (own buffers or bound ones).  bodies_device: nbodies × 64 bytes; probes_device:
+ *                   nprobes × 16 bytes; records_device: nbodies × 32 bytes; DEVICE pointers, 16-byte aligned
+ *   read_bodies     the same from HOST arrays, blocking, through device staging buffers of its own (grown on demand, freed by
+ *                   datum_ocean_destroy), all on the handle's stream
+ * DATUM_OCEAN_EINVAL for what the several-cascade query refuses (list, handle, set, iterations), for a null bodies or records array with
+ * nbodies > 0, a null probes array with nprobes > 0, misaligned arrays, and nbodies or nprobes above INT32_MAX.  nbodies == 0 enqueues
+ * nothing.  A call writes only the records. */
+#define DATUM_OCEAN_BODY_RECORD_FLOATS 8
+typedef struct datum_ocean_body
+{
+  float rotation[9];       /*   0  row-major, body-local → world   */
+  float position[3];       /*  36  the body origin in world space  */
+  int32_t first;           /*  48  the body's first probe ...      */
+  int32_t count;           /*  52  ... and how many                */
+  float cap;               /*  56  largest submersion of one probe */
+  int32_t pad;             /*  60                                  */
+} datum_ocean_body;
+int datum_ocean_reduce_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                              void const *bodies_device, size_t nbodies, void const *probes_device, size_t nprobes, void *records_device);
+int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                            datum_ocean_body const *bodies, size_t nbodies, float const *probes, size_t nprobes, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -129,6 +129,8 @@ SYMBOLS = {
     "datum_ocean_read_surface_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_reduce_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
     "datum_ocean_read_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
+    "datum_ocean_cast_rays": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_rays": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -170,6 +172,14 @@ class Body(ctypes.Structure):
 
 # the same layout for numpy: an array of this dtype is an array of Body
 BODY_DTYPE = np.dtype([("rotation", np.float32, 9), ("position", np.float32, 3), ("first", np.int32), ("count", np.int32), ("cap", np.float32), ("pad", np.int32)])
+
+# ray casts (datum_ocean_cast_rays, added at ABI 9): floats per ray (ox, oy, oz, tmin, dx, dy, dz, tmax) and per record (hi, lo, g(hi), status,
+# the query's record at hi), the ranges of steps and refine, and the status values
+RAY_FLOATS = 8
+RAY_RECORD_FLOATS = 12
+RAY_MAX_STEPS = 1024
+RAY_MAX_REFINE = 24
+RAY_MISS, RAY_ENTER, RAY_LEAVE = 0, 1, 2
 
 
 def header_abi_version():
@@ -606,6 +616,23 @@ class Ocean:
         pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
         out = np.empty((b.shape[0], BODY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
+        return out
+
+    # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------
+
+    def cast_rays(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
+        """Enqueue the cast of `n` rays (device pointer, 32 bytes each: ox, oy, oz, tmin, dx, dy, dz, tmax) into `n` records of 12 floats
+        (device pointer): hi, lo, g(hi), status (0 miss, 1 enter, 2 leave) and the surface record at hi."""
+        arr, c = self._list(cascades)
+        self._check(self.lib.datum_ocean_cast_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, P(rays_ptr) if rays_ptr else None, n,
+                                                   P(records_ptr) if records_ptr else None))
+
+    def read_rays(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
+        """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
+        arr, c = self._list(cascades)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
+        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
         return out
 
     def algorithmic_bytes(self):

@@ -24,6 +24,7 @@
 #include "ocean_surface.hip"
 #include "ocean_blend.hip"
 #include "ocean_body.hip"
+#include "ocean_ray.hip"
 
 using namespace ocean;
 
@@ -127,6 +128,11 @@ struct datum_ocean_ctx
   size_t bodycapacity = 0;            // bodies both hold
   BodyProbe *probestage = nullptr;
   size_t probecapacity = 0;
+
+  // datum_ocean_read_rays' device staging, grown on demand: rays with their records
+  float4 *raystage = nullptr;
+  float4 *rayrecords = nullptr;
+  size_t raycapacity = 0;             // rays both hold
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -907,6 +913,8 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->bodystage);
   (void)hipFree(ctx->bodyrecords);
   (void)hipFree(ctx->probestage);
+  (void)hipFree(ctx->raystage);
+  (void)hipFree(ctx->rayrecords);
 
   if (ctx->ownstream)
     (void)hipStreamDestroy(ctx->ownstream);
@@ -2391,6 +2399,128 @@ int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, d
 
   HIPCHECK(ctx, launch_bodies(a, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(records, ctx->bodyrecords, nbodies * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
+/* -- ray casts (ocean_ray.hip) ---------------------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // the checks both entry points share; `name` goes into the error text
+  int check_ray_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                     void const *rays, size_t n, void const *records, char const *name)
+  {
+    int rc = check_blend_list(ctx, cascades, count, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (!set)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
+
+    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
+
+    if (steps < 1 || steps > DATUM_OCEAN_RAY_MAX_STEPS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": steps outside [1, DATUM_OCEAN_RAY_MAX_STEPS]").c_str());
+
+    if (refine < 0 || refine > DATUM_OCEAN_RAY_MAX_REFINE)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": refine outside [0, DATUM_OCEAN_RAY_MAX_REFINE]").c_str());
+
+    if (n > 0 && (!rays || !records))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null rays or records").c_str());
+
+    if (((uintptr_t)rays & 15) || ((uintptr_t)records & 15))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": rays and records must be 16-byte aligned").c_str());
+
+    if (n > (size_t)INT32_MAX)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  RayArgs ray_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                   void const *rays, size_t n, void *records)
+  {
+    RayArgs a;
+    a.s = surface_args(ctx, cascades[0], set, iterations, nullptr, 0, nullptr);
+    a.s.map = nullptr;
+    a.s.foam = nullptr;
+    a.list = blend_list(ctx, cascades, count);
+    a.rays = static_cast<float4 const*>(rays);
+    a.records = static_cast<float4*>(records);
+    a.n = (int)n;
+    a.steps = steps;
+    a.refine = refine;
+    a.inv = 0.0f;           // launch_rays
+    return a;
+  }
+
+  // the host entry point's device staging of `n` rays and records (grown on demand), the rays copied in on the handle's stream
+  int stage_rays(datum_ocean_ctx *ctx, float const *rays, size_t n)
+  {
+    if (n > ctx->raycapacity)
+    {
+      // the old staging may still be read by an earlier launch of this stream
+      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+      HIPCHECK(ctx, hipFree(ctx->raystage));
+      HIPCHECK(ctx, hipFree(ctx->rayrecords));
+      ctx->raystage = nullptr;
+      ctx->rayrecords = nullptr;
+      ctx->raycapacity = 0;
+
+      HIPCHECK(ctx, hipMalloc(&ctx->raystage, n * RAY_BYTES));
+      HIPCHECK(ctx, hipMalloc(&ctx->rayrecords, n * RAY_RECORD_BYTES));
+      ctx->raycapacity = n;
+    }
+
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->raystage, rays, n * RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_cast_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                          void const *rays_device, size_t n, void *records_device)
+{
+  int rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  RayArgs a = ray_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
+
+  HIPCHECK(ctx, launch_rays(a, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                          float const *rays, size_t n, float *records)
+{
+  int rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, "datum_ocean_read_rays");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  rc = stage_rays(ctx, rays, n);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  RayArgs a = ray_args(ctx, cascades, count, set, iterations, steps, refine, ctx->raystage, n, ctx->rayrecords);
+
+  HIPCHECK(ctx, launch_rays(a, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->rayrecords, n * RAY_RECORD_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;

@@ -3,6 +3,8 @@
 // from b = q, then the final evaluation at b.
 //   in scope: SurfaceArgs const &s (N, iterations), datum_ocean_set const &p, GenFrame const &f, BlendList const &list, float2 q (finite)
 //   leaves:   vx, vy, vz, residual, mx, my, mz, foam -- the record's eight fields
+// With OCEAN_SURFACE_BLEND_POINT_HEIGHT defined by the includer (ocean_ray.hip's search) the final evaluation keeps to part A and leaves vz
+// alone, the same operations in the same order: the height has the record's bits, parts B and the foam planes are not fetched.
 TexelIndex<LAYOUT> const texel(s.N);
 
 int const nmask = s.N - 1;
@@ -62,6 +64,32 @@ sincos_phase(theta, &st, &ct);
 
 px = bx + f.gx * ct;
 py = by + f.gy * ct;
+
+#ifdef OCEAN_SURFACE_BLEND_POINT_HEIGHT
+
+float dz = 0.0f;
+
+for(int c = 0; c < count; ++c)
+{
+  BlendCascade const &bc = list.casc[c];
+
+  __amdgpu_buffer_rsrc_t const rmap = make_rsrc(bc.map, mapbytes);
+
+  SurfaceTexel<LAYOUT> const t(texel, f, bc.scale, nmask, px, py);
+
+  float4 const a00 = buf_load_f32x4_aux<0>(rmap, t.o00, 0);
+  float4 const a10 = buf_load_f32x4_aux<0>(rmap, t.o10, 0);
+  float4 const a01 = buf_load_f32x4_aux<0>(rmap, t.o01, 0);
+  float4 const a11 = buf_load_f32x4_aux<0>(rmap, t.o11, 0);
+
+  float const cz = t.blend(a00.z, a10.z, a01.z, a11.z);
+
+  dz = (c == 0) ? cz : dz + cz;
+}
+
+float const vz = (f.basez + p.swellamplitude * st) + dz;
+
+#else
 
 float dx = 0.0f, dy = 0.0f, dz = 0.0f, sx = 0.0f, sy = 0.0f, foam = 0.0f;
 
@@ -133,3 +161,5 @@ float const residual = __builtin_sqrtf(fmaf(ry, ry, rx * rx));
 float mx, my, mz;
 
 blend_surface_normal(f, st, ct, sx, sy, mx, my, mz);
+
+#endif

@@ -339,6 +339,16 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_cast_ocean_rays(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
+  {
+    try
+    {
+      cast_ocean_rays(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

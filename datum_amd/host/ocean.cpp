@@ -905,6 +905,20 @@ void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum
 }
 
 
+///////////////////////// cast_ocean_rays ///////////////////////////////////
+void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
+{
+  if (!context.ready)
+    throw runtime_error("cast_ocean_rays: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_rays(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays");
+}
+
+
 ///////////////////////// read_ocean_displacement ///////////////////////////
 void read_ocean_displacement(OceanContext &context, float *maps)
 {

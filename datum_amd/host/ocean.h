@@ -379,6 +379,32 @@ static_assert(sizeof(OceanBodyRecord) == 32, "OceanBodyRecord must be the C ABI'
 
 void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, OceanBodyRecord *records, int iterations = 4);
 
+// ray casts (include/datum_ocean_hip.h: datum_ocean_read_rays, the definition there): per ray a fixed march of `steps` samples to the first
+// change of side, `refine` bisections of that bracket, and the surface sample at the bracket's far end.  One cascade, as
+// query_ocean_surface; the maps the context last displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before
+// prepare_ocean_context
+struct OceanRay
+{
+  lml::Vec3 origin;
+  float tmin;
+  lml::Vec3 direction;                    // need not be normalised
+  float tmax;
+};
+
+struct OceanRayRecord
+{
+  float hi;                               // the first parameter known to lie on the other side of the surface (a miss: tmax)
+  float lo;                               // the last one known to lie on the starting side
+  float g;                                // point(hi).z - the water height there
+  float status;                           // 0 miss, 1 enter (started above), 2 leave (started below)
+  OceanSurfaceSample sample;              // the surface at point(hi)
+};
+
+static_assert(sizeof(OceanRay) == 32, "OceanRay must be the C ABI's ray of DATUM_OCEAN_RAY_FLOATS floats");
+static_assert(sizeof(OceanRayRecord) == 48, "OceanRayRecord must be the C ABI's record of DATUM_OCEAN_RAY_RECORD_FLOATS floats");
+
+void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

@@ -99,6 +99,7 @@ def load():
             "datum_host_read_ocean_foam": (I, [P, P]),
             "datum_host_query_ocean_surface": (I, [P, P, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
+            "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -320,6 +321,14 @@ class OceanContext:
         pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
         out = np.empty((b.shape[0], capi.BODY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_reduce_ocean_bodies(self.c, params.p, b.ctypes.data_as(P), b.shape[0], pr.ctypes.data_as(P), pr.shape[0], out.ctypes.data_as(P), iterations))
+        return out
+
+    def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):
+        """cast_ocean_rays: `rays` (n, 8) float32 (origin, tmin, direction, tmax); returns (n, 12) float32 records (OceanRayRecord: hi, lo,
+        g(hi), status, the surface sample at hi)"""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
+        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_cast_ocean_rays(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
         return out
 
     def read_vertices(self, mesh):

@@ -48,8 +48,8 @@ extern "C" {
  *      Later added at 9 without a bump (nothing changed, entry points were only added): the surface queries datum_ocean_sample_surface and
  *      datum_ocean_read_surface; then the phase write-back interval, datum_ocean_set_phase_writeback and datum_ocean_phase_writeback; then
  *      the several-cascade calls datum_ocean_gen_blend, datum_ocean_sample_surface_blend and datum_ocean_read_surface_blend; then body
- *      buoyancy, datum_ocean_reduce_bodies and datum_ocean_read_bodies.  A consumer that needs them detects them by symbol (dlsym), not
- *      by the version */
+ *      buoyancy, datum_ocean_reduce_bodies and datum_ocean_read_bodies; then ray casts, datum_ocean_cast_rays and datum_ocean_read_rays.
+ *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
 
@@ -438,6 +438,62 @@ int datum_ocean_reduce_bodies(datum_ocean_t ctx, int const *cascades, int count,
                               void const *bodies_device, size_t nbodies, void const *probes_device, size_t nprobes, void *records_device);
 int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                             datum_ocean_body const *bodies, size_t nbodies, float const *probes, size_t nprobes, float *records);
+
+/* -- ray casts (added at ABI 9; nothing in the reference) -----------------------------------------------------------------------------
+ * Where a segment meets the summed surface: picking, line of sight, projectiles, "is this sensor under water along its beam".  The result
+ * is NOT "the intersection": it is the outcome of a fixed sequence of height evaluations, each of them the several-cascade query's, so
+ * that a cast repeats from run to run and can be restated on a CPU on top of datum_ocean_read_surface_blend, bit for bit.  (With the
+ * queries alone a caller spends one launch per evaluation, 8 bytes in and 32 bytes out per ray each time, with host logic in between.)
+ *
+ * A call takes a blend list cascades[count] -- the several-cascade calls' rules, the handle's scale_c, set->scale ignored; a one-element
+ * list is the single-cascade case -- a set, the query's iteration count, steps S in [1, DATUM_OCEAN_RAY_MAX_STEPS], refine R in
+ * [0, DATUM_OCEAN_RAY_MAX_REFINE] and n rays.  A ray is 32 bytes, (ox, oy, oz, tmin, dx, dy, dz, tmax); the direction need not be
+ * normalised.  Every operation below is one fp32 operation as written (no contraction):
+ *
+ *     point(t) = ( ox + t·dx,  oy + t·dy,  oz + t·dz )
+ *     rec(t)   = the record of datum_ocean_sample_surface_blend for q = point(t).xy with this list, set and iterations, bit for bit
+ *                (eight NaNs where q is not finite, as there)
+ *     g(t)     = point(t).z − rec(t).z
+ *     below(t) = g(t) < 0                                 as written: a NaN is "not below"
+ *     inv      = 1.0f / (float)S                          rounded once on the host and passed to the kernel
+ *     Δ        = (tmax − tmin) · inv
+ *     t_i      = tmin + (float)i · Δ   for i = 0 … S−1,   t_S = tmax
+ *
+ * March: side = below(t_0); take i = 1, 2, … S in order and stop at the first i with below(t_i) != side: lo = t_(i−1), hi = t_i.  If there
+ * is none the ray is a MISS, lo = hi = tmax, and it is not refined.  A ray stops marching at its own bracket; its result depends on no
+ * other ray.
+ * Refinement, exactly R times on a bracket:
+ *     mid = 0.5f · (lo + hi);   if below(mid) == side: lo = mid   else: hi = mid
+ *
+ * Each ray gets a record of DATUM_OCEAN_RAY_RECORD_FLOATS = 12 floats (48 bytes):
+ *     0      hi, the first parameter known to lie on the other side (MISS: tmax)
+ *     1      lo
+ *     2      g(hi)
+ *     3      the status as a float: 0 MISS, 1 ENTER (side was "not below"), 2 LEAVE (side was "below")
+ *     4–11   rec(hi), the query's eight floats
+ * A MISS with field 2 < 0 is a segment that lies under water throughout (as far as S samples can tell).
+ * A ray is bad if any of its eight floats is not finite, if tmax < tmin, or if point(tmin) or point(tmax) is not finite: it gets twelve
+ * quiet NaNs and fetches nothing.  No index can fault: a ray is read and a record written only through buffer resources laid over the rays
+ * and records of the ray's own workgroup, the maps through the query's.
+ *
+ *   cast_rays   enqueue and return: one kernel on the handle's stream behind the last displace; it applies no pending update and reads
+ *               maps and foam planes as they lie (own buffers or bound ones).  rays_device: n × 32 bytes; records_device: n × 48 bytes;
+ *               DEVICE pointers, 16-byte aligned
+ *   read_rays   the same from HOST arrays, blocking, through device staging buffers of its own (grown on demand, freed by
+ *               datum_ocean_destroy), all on the handle's stream
+ * DATUM_OCEAN_EINVAL for what the several-cascade query refuses (list, handle, set, iterations), for steps or refine out of range, a null
+ * rays or records array with n > 0, misaligned arrays, and n above INT32_MAX.  n == 0 enqueues nothing.  A call writes only the records. */
+#define DATUM_OCEAN_RAY_FLOATS 8
+#define DATUM_OCEAN_RAY_RECORD_FLOATS 12
+#define DATUM_OCEAN_RAY_MAX_STEPS 1024
+#define DATUM_OCEAN_RAY_MAX_REFINE 24
+#define DATUM_OCEAN_RAY_MISS 0
+#define DATUM_OCEAN_RAY_ENTER 1
+#define DATUM_OCEAN_RAY_LEAVE 2
+int datum_ocean_cast_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                          void const *rays_device, size_t n, void *records_device);
+int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                          float const *rays, size_t n, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -131,6 +131,12 @@ SYMBOLS = {
     "datum_ocean_read_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
     "datum_ocean_cast_rays": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_rays": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_reduce_bounds": (I, [P]),
+    "datum_ocean_bounds_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
+    "datum_ocean_read_bounds": (I, [P, P]),
+    "datum_ocean_surface_slab": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), P, P, P, P]),
+    "datum_ocean_cast_rays_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_rays_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -180,6 +186,9 @@ RAY_RECORD_FLOATS = 12
 RAY_MAX_STEPS = 1024
 RAY_MAX_REFINE = 24
 RAY_MISS, RAY_ENTER, RAY_LEAVE = 0, 1, 2
+
+# surface bounds (datum_ocean_reduce_bounds, added at ABI 9): floats per cascade record (zmin, zmax, xmin, xmax, ymin, ymax, nonfinite, 0)
+BOUNDS_RECORD_FLOATS = 8
 
 
 def header_abi_version():
@@ -633,6 +642,48 @@ class Ocean:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
         out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
+        return out
+
+    # -- surface bounds (datum_ocean_reduce_bounds) and the ray casts that skip the samples they decide ------------------------------------
+
+    def reduce_bounds(self):
+        """Enqueue the reduction of every cascade's maps to its record; the records are current until the next displace or bind_maps."""
+        self._check(self.lib.datum_ocean_reduce_bounds(self.h))
+
+    def bounds_device(self):
+        """(device pointer, bytes) of the handle's records, cascades x 32 bytes"""
+        p = P()
+        n = ctypes.c_size_t()
+        self._check(self.lib.datum_ocean_bounds_device(self.h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def read_bounds(self):
+        """reduce_bounds and a blocking read: (cascades, 8) float32 -- zmin, zmax, xmin, xmax, ymin, ymax, nonfinite, 0"""
+        out = np.empty((self.cascades, BOUNDS_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_bounds(self.h, _ptr(out)))
+        return out
+
+    def surface_slab(self, cascades, oceanset):
+        """blocking: (zlo, zhi, reachx, reachy) of the listed cascades' summed surface under `oceanset`, as float32"""
+        arr, c = self._list(cascades)
+        out = np.zeros(4, np.float32)
+        base = out.ctypes.data
+        self._check(self.lib.datum_ocean_surface_slab(self.h, arr, c, ctypes.byref(oceanset), P(base), P(base + 4), P(base + 8), P(base + 12)))
+        return out[0], out[1], out[2], out[3]
+
+    def cast_rays_bounded(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
+        """cast_rays with the samples outside the slab decided without a height evaluation: the same records bit for bit.  Needs current
+        bounds (reduce_bounds after the last displace or bind_maps), else OceanError(ESTATE)."""
+        arr, c = self._list(cascades)
+        self._check(self.lib.datum_ocean_cast_rays_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, P(rays_ptr) if rays_ptr else None, n,
+                                                           P(records_ptr) if records_ptr else None))
+
+    def read_rays_bounded(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
+        """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
+        arr, c = self._list(cascades)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
+        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_rays_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
         return out
 
     def algorithmic_bytes(self):

@@ -25,6 +25,7 @@
 #include "ocean_blend.hip"
 #include "ocean_body.hip"
 #include "ocean_ray.hip"
+#include "ocean_bounds.hip"
 
 using namespace ocean;
 
@@ -133,6 +134,12 @@ struct datum_ocean_ctx
   float4 *raystage = nullptr;
   float4 *rayrecords = nullptr;
   size_t raycapacity = 0;             // rays both hold
+
+  // datum_ocean_reduce_bounds: the records, [cascades] x 32 bytes, and the workgroups' partials, both allocated by the first reduce
+  float4 *bounds = nullptr;
+  float4 *boundspartials = nullptr;
+  int boundsgroups = 0;               // workgroups per cascade the partials were sized for
+  bool boundscurrent = false;         // the records are those of the maps as they lie: set by reduce_bounds, cleared by displace, bind_maps and a release_memory that unbinds the maps
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -915,6 +922,8 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->probestage);
   (void)hipFree(ctx->raystage);
   (void)hipFree(ctx->rayrecords);
+  (void)hipFree(ctx->bounds);
+  (void)hipFree(ctx->boundspartials);
 
   if (ctx->ownstream)
     (void)hipStreamDestroy(ctx->ownstream);
@@ -942,8 +951,14 @@ int datum_ocean_bind_maps(datum_ocean_t ctx, void *device_ptr, size_t bytes)
   if (!ctx)
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_bind_maps: null handle");
 
-  return bind_plane(ctx, ctx->maps, device_ptr, bytes, ctx->cascades * map_cascade_bytes(ctx->N),
-                    "datum_ocean_bind_maps: buffer smaller than cascades * N * N * texel_bytes (datum_ocean_map_layout)", "datum_ocean_bind_maps: buffer must be 16-byte aligned");
+  int const rc = bind_plane(ctx, ctx->maps, device_ptr, bytes, ctx->cascades * map_cascade_bytes(ctx->N),
+                            "datum_ocean_bind_maps: buffer smaller than cascades * N * N * texel_bytes (datum_ocean_map_layout)", "datum_ocean_bind_maps: buffer must be 16-byte aligned");
+
+  // other maps: the bounds records (datum_ocean_reduce_bounds) are no longer theirs
+  if (rc == DATUM_OCEAN_OK)
+    ctx->boundscurrent = false;
+
+  return rc;
 }
 
 int datum_ocean_maps_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
@@ -1364,6 +1379,9 @@ int datum_ocean_displace(datum_ocean_t ctx)
     fa = foam_args(ctx);
 
   ctx->foamdt = 0.0;
+
+  // new maps from here on: the bounds records (datum_ocean_reduce_bounds) are no longer theirs
+  ctx->boundscurrent = false;
 
   if (sampling)
     ctx->profcalls += 1;
@@ -2528,6 +2546,187 @@ int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, dat
 
 }   // extern "C"
 
+/* -- surface bounds and the bounded ray casts (ocean_bounds.hip) ------------------------------------------------------------------------ */
+
+namespace
+{
+  // the records and the partials, allocated by the first reduce, and the two launches
+  int reduce_bounds(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    if (!ctx->bounds)
+    {
+      int const groups = bounds_groups(ctx->N, ctx->cascades);
+
+      float4 *records = nullptr, *partials = nullptr;
+
+      HIPCHECK(ctx, hipMalloc(&records, (size_t)ctx->cascades * BOUNDS_BYTES));
+
+      hipError_t const e = hipMalloc(&partials, (size_t)ctx->cascades * groups * BOUNDS_BYTES);
+
+      if (e != hipSuccess)
+      {
+        (void)hipFree(records);
+        return fail(ctx, (int)e, "datum_ocean_reduce_bounds: hipMalloc");
+      }
+
+      ctx->bounds = records;
+      ctx->boundspartials = partials;
+      ctx->boundsgroups = groups;
+    }
+
+    BoundsArgs a;
+    a.maps = ctx->maps.get();
+    a.partials = ctx->boundspartials;
+    a.records = ctx->bounds;
+    a.N = ctx->N;
+    a.groups = ctx->boundsgroups;
+
+    HIPCHECK(ctx, launch_bounds(a, ctx->cascades, ctx->stream));
+
+    ctx->boundscurrent = true;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // cast_rays' checks, then the state both bounded entry points need
+  int check_ray_bounded_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                             void const *rays, size_t n, void const *records, char const *name)
+  {
+    int rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    if (!ctx->boundscurrent)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (std::string(name) + ": the bounds are not current (datum_ocean_reduce_bounds after the last displace or bind_maps)").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  RayBoundedArgs ray_bounded_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  void const *rays, size_t n, void *records)
+  {
+    RayBoundedArgs a;
+    a.r = ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records);
+    a.bounds = reinterpret_cast<float const*>(ctx->bounds);
+
+    for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
+      a.cascades[c] = (c < count) ? cascades[c] : 0;
+
+    return a;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_reduce_bounds(datum_ocean_t ctx)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_reduce_bounds: null handle");
+
+  return reduce_bounds(ctx);
+}
+
+int datum_ocean_bounds_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
+{
+  if (!ctx || !device_ptr)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_bounds_device: null argument");
+
+  if (!ctx->bounds)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_bounds_device: no records yet (datum_ocean_reduce_bounds)");
+
+  *device_ptr = ctx->bounds;
+
+  if (bytes)
+    *bytes = (size_t)ctx->cascades * BOUNDS_BYTES;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_bounds(datum_ocean_t ctx, float *records)
+{
+  if (!ctx || !records)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_bounds: null argument");
+
+  int rc = reduce_bounds(ctx);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->bounds, (size_t)ctx->cascades * BOUNDS_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_surface_slab(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, float *zlo, float *zhi, float *reachx, float *reachy)
+{
+  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_surface_slab");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!set)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_surface_slab: null set");
+
+  float records[DATUM_OCEAN_MAX_CASCADES * BOUNDS_FIELDS];
+
+  rc = datum_ocean_read_bounds(ctx, records);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  GenFrame const f = make_gen_frame(*set, ctx->N, 2, 2);      // the camera's terms are not read
+
+  BoundsSlab const s = bounds_slab(records, cascades, count, f.basez, set->swellamplitude, f.gx, f.gy);
+
+  if (zlo) *zlo = s.zlo;
+  if (zhi) *zhi = s.zhi;
+  if (reachx) *reachx = s.reachx;
+  if (reachy) *reachy = s.reachy;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_cast_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  void const *rays_device, size_t n, void *records_device)
+{
+  int rc = check_ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_bounded");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  RayBoundedArgs a = ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
+
+  HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  float const *rays, size_t n, float *records)
+{
+  int rc = check_ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, "datum_ocean_read_rays_bounded");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  rc = stage_rays(ctx, rays, n);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  RayBoundedArgs a = ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, ctx->raystage, n, ctx->rayrecords);
+
+  HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->rayrecords, n * RAY_RECORD_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
 // a cascade's maps as the reference's 2-layer RGBA32F image (datum_ocean_export_maps); one thread per texel.  LAYOUT (up to 1024^2): in the
 // order of the map layout like the pack kernel -- consecutive lanes read consecutive parts A and B of a patch, 16-byte stores in runs of
 // a patch row (1024^2: 13.0 -> 9.3 us); otherwise in the order of the image -- from 2048^2 up, beyond the Infinity Cache, whole lines
@@ -2878,8 +3077,12 @@ int datum_ocean_release_memory(datum_ocean_t ctx, void *device_ptr)
       char const *lo = static_cast<char const*>(device_ptr), *hi = lo + ctx->importedmemory[i].bytes;
       auto inside = [lo, hi](void const *p) { return static_cast<char const*>(p) >= lo && static_cast<char const*>(p) < hi; };
 
+      // (other maps from here on, as after datum_ocean_bind_maps: the bounds records are no longer theirs)
       if (inside(ctx->maps.bound))
+      {
         ctx->maps.bound = nullptr;
+        ctx->boundscurrent = false;
+      }
 
       if (inside(ctx->foam.bound))
         ctx->foam.bound = nullptr;

@@ -349,6 +349,38 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_reduce_ocean_bounds(void *c)
+  {
+    try
+    {
+      reduce_ocean_bounds(static_cast<HostContext*>(c)->context);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  // slab[4]: zlo, zhi, reach.x, reach.y
+  int datum_host_ocean_surface_slab(void *c, void *p, float *slab)
+  {
+    try
+    {
+      OceanSurfaceSlab const s = ocean_surface_slab(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p));
+      slab[0] = s.zlo; slab[1] = s.zhi; slab[2] = s.reach.x; slab[3] = s.reach.y;
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_cast_ocean_rays_bounded(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
+  {
+    try
+    {
+      cast_ocean_rays_bounded(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

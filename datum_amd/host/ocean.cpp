@@ -919,6 +919,48 @@ void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay 
 }
 
 
+///////////////////////// reduce_ocean_bounds ///////////////////////////////
+void reduce_ocean_bounds(OceanContext &context)
+{
+  if (!context.ready)
+    throw runtime_error("reduce_ocean_bounds: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_reduce_bounds(context.hip), "datum_ocean_reduce_bounds");
+}
+
+
+///////////////////////// ocean_surface_slab ////////////////////////////////
+OceanSurfaceSlab ocean_surface_slab(OceanContext &context, OceanParams const &params)
+{
+  if (!context.ready)
+    throw runtime_error("ocean_surface_slab: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  OceanSurfaceSlab slab;
+
+  check(context.hip, datum_ocean_surface_slab(context.hip, &cascade, 1, &set, &slab.zlo, &slab.zhi, &slab.reach.x, &slab.reach.y), "datum_ocean_surface_slab");
+
+  return slab;
+}
+
+
+///////////////////////// cast_ocean_rays_bounded ///////////////////////////
+void cast_ocean_rays_bounded(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
+{
+  if (!context.ready)
+    throw runtime_error("cast_ocean_rays_bounded: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_rays_bounded(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays_bounded");
+}
+
+
 ///////////////////////// read_ocean_displacement ///////////////////////////
 void read_ocean_displacement(OceanContext &context, float *maps)
 {

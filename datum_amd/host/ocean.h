@@ -405,6 +405,22 @@ static_assert(sizeof(OceanRayRecord) == 48, "OceanRayRecord must be the C ABI's 
 
 void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
 
+// surface bounds (include/datum_ocean_hip.h: datum_ocean_reduce_bounds, the definition there): the extrema of the displacement the context
+// last displaced, reduced on the device, and what they say about the surface under `params`: every height lies strictly between zlo and
+// zhi, every vertex within `reach` of its undisplaced position along x and y.  One cascade, as query_ocean_surface.  reduce_ocean_bounds
+// enqueues and returns; ocean_surface_slab reduces and blocks; cast_ocean_rays_bounded is cast_ocean_rays with the samples outside the slab
+// decided without a height evaluation -- the same records bit for bit -- and throws unless reduce_ocean_bounds (or ocean_surface_slab) was
+// called after the last render_ocean_surface / displace_ocean_surface.  All three throw before prepare_ocean_context
+struct OceanSurfaceSlab
+{
+  float zlo, zhi;
+  lml::Vec2 reach;
+};
+
+void reduce_ocean_bounds(OceanContext &context);
+OceanSurfaceSlab ocean_surface_slab(OceanContext &context, OceanParams const &params);
+void cast_ocean_rays_bounded(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

@@ -100,6 +100,9 @@ def load():
             "datum_host_query_ocean_surface": (I, [P, P, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
+            "datum_host_reduce_ocean_bounds": (I, [P]),
+            "datum_host_ocean_surface_slab": (I, [P, P, P]),
+            "datum_host_cast_ocean_rays_bounded": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -329,6 +332,23 @@ class OceanContext:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
         out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_cast_ocean_rays(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
+        return out
+
+    def reduce_ocean_bounds(self):
+        """reduce_ocean_bounds: enqueue the reduction of the displacement last computed; current until the next render / displace"""
+        self._check(self.lib.datum_host_reduce_ocean_bounds(self.c))
+
+    def ocean_surface_slab(self, params):
+        """ocean_surface_slab: (zlo, zhi, reach.x, reach.y) as float32, blocking"""
+        out = np.zeros(4, np.float32)
+        self._check(self.lib.datum_host_ocean_surface_slab(self.c, params.p, out.ctypes.data_as(P)))
+        return out[0], out[1], out[2], out[3]
+
+    def cast_ocean_rays_bounded(self, params, rays, iterations=4, steps=32, refine=8):
+        """cast_ocean_rays_bounded: cast_ocean_rays' arguments and records; raises unless the bounds are current"""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
+        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_cast_ocean_rays_bounded(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
         return out
 
     def read_vertices(self, mesh):

@@ -48,7 +48,9 @@ extern "C" {
  *      Later added at 9 without a bump (nothing changed, entry points were only added): the surface queries datum_ocean_sample_surface and
  *      datum_ocean_read_surface; then the phase write-back interval, datum_ocean_set_phase_writeback and datum_ocean_phase_writeback; then
  *      the several-cascade calls datum_ocean_gen_blend, datum_ocean_sample_surface_blend and datum_ocean_read_surface_blend; then body
- *      buoyancy, datum_ocean_reduce_bodies and datum_ocean_read_bodies; then ray casts, datum_ocean_cast_rays and datum_ocean_read_rays.
+ *      buoyancy, datum_ocean_reduce_bodies and datum_ocean_read_bodies; then ray casts, datum_ocean_cast_rays and datum_ocean_read_rays; then
+ *      surface bounds, datum_ocean_reduce_bounds, datum_ocean_bounds_device, datum_ocean_read_bounds and datum_ocean_surface_slab, with the
+ *      bounded casts datum_ocean_cast_rays_bounded and datum_ocean_read_rays_bounded.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -494,6 +496,65 @@ int datum_ocean_cast_rays(datum_ocean_t ctx, int const *cascades, int count, dat
                           void const *rays_device, size_t n, void *records_device);
 int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                           float const *rays, size_t n, float *records);
+
+/* -- surface bounds per cascade, and ray casts that skip known air (added at ABI 9; nothing in the reference) ---------------------------
+ * How high and how low can the water be right now, and how far can a vertex move sideways?  For frustum culling, the near plane, the
+ * mesh's bounding box -- without datum_ocean_read_maps' 32 bytes per texel over the bus -- and for ray casts, whose march samples far
+ * above the highest crest need no height evaluation to be known as "not below".
+ *
+ * Per cascade a record of DATUM_OCEAN_BOUNDS_RECORD_FLOATS = 8 floats (32 bytes):
+ *     0, 1   zmin, zmax     2, 3   xmin, xmax     4, 5   ymin, ymax     6   nonfinite     7   0
+ * the extrema over all N² texels of dz, dx, dy of map layer 0 AS STORED (the choppiness is in dx, dy), combined with fminf / fmaxf from
+ * +inf / −inf: a NaN enters no extremum, an infinity does.  nonfinite is the number of texels with a non-finite dx, dy or dz.  The
+ * extrema are exact and do not depend on the order of the reduction, but for the sign of a zero: compare them by value.
+ *
+ * The slab of a blend list cascades[count] under a set, each line one fp32 operation as written, sums taken in list order from the
+ * parenthesised start (basez = −plane.w; A = swellamplitude; gx, gy = the Gerstner terms (qi·A)·swelldirection of the queries):
+ *
+ *     mag  = (|basez| + |A|) + Σ_c max(|zmin_c|, |zmax_c|)
+ *     pad  = mag · 2^-16
+ *     zhi  = ((basez + |A|) + Σ_c zmax_c) + pad
+ *     zlo  = ((basez − |A|) + Σ_c zmin_c) − pad
+ *     reach.x = |gx| + Σ_c max(|xmin_c|, |xmax_c|)         reach.y likewise
+ *
+ * Every height datum_ocean_sample_surface_blend can give for that list and set lies strictly between zlo and zhi, and its record's
+ * position within reach of the point it was evaluated at.  pad is a stated margin, about 256 ulp of the magnitudes involved, for the
+ * phase's sine (≤ 1 + 5e-7), the blend weights' sum and one rounding per cascade sum.  If a listed cascade has nonfinite > 0,
+ * zlo = zhi = NaN: the slab then says nothing.
+ *
+ * The bounded cast is datum_ocean_cast_rays with
+ *     below'(t) = point(t).z > zhi ? false : point(t).z < zlo ? true : below(t)
+ * on every sample whose point(t).xy is finite: the first two cases evaluate no height.  A NaN point(t).z or a NaN bound makes both
+ * comparisons false, and the sample is evaluated as in cast_rays.
+ *
+ *   reduce_bounds       enqueue and return: two launches on the handle's stream behind the last displace; reads the maps as they lie (own
+ *                       buffer or a bound one) and applies no pending update.  The handle then holds the records and marks them CURRENT;
+ *                       datum_ocean_displace and datum_ocean_bind_maps clear that mark, and so does a datum_ocean_release_memory that
+ *                       unbinds the maps (a map buffer bound inside the released block: the handle's own maps are in use again, as
+ *                       after bind_maps(NULL)); no other call does (datum_ocean_bind_foam leaves it: the records read no foam plane)
+ *   bounds_device       the records on the device, cascades × 32 bytes, handle-owned (allocated by the first reduce, freed by
+ *                       datum_ocean_destroy); DATUM_OCEAN_ESTATE before the first reduce.  Ordered on the handle's stream
+ *   read_bounds         reduce_bounds, then a blocking read of cascades × 8 floats
+ *   surface_slab        blocking: read_bounds, then the slab above on the host.  Any of the four outputs may be NULL
+ *   cast_rays_bounded, read_rays_bounded
+ *                       cast_rays' and read_rays' arguments, rules and DATUM_OCEAN_EINVAL cases.  DATUM_OCEAN_ESTATE unless the records
+ *                       are current: a bounded cast that returns DATUM_OCEAN_OK has therefore written datum_ocean_cast_rays' records
+ *                       BIT FOR BIT, all twelve floats of every ray.  A caller who writes into a bound map buffer behind the module's
+ *                       back (datum_ocean_device_write, a kernel of its own) without a new reduce_bounds forfeits that guarantee.
+ * When to use which: the bounded cast gains where march samples lie outside the slab -- a camera fan from above, long rays through air or
+ * deep water.  Measured (tools/bounds_bench.py, 10^6 rays, 1024^2 maps, lists of 1 and 4): 0.57-0.60 of cast_rays' time
+ * on the camera fan and 0.64 on the random set, whose rays start 0.5 to 4 m from the level and so mostly outside the slab as well; no
+ * measured set was slower.  Rays that start and end inside the slab evaluate every sample either way and pay the comparisons and the
+ * slab on top (not measured as a set of their own): for those datum_ocean_cast_rays is the call to prefer. */
+#define DATUM_OCEAN_BOUNDS_RECORD_FLOATS 8
+int datum_ocean_reduce_bounds(datum_ocean_t ctx);
+int datum_ocean_bounds_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes);
+int datum_ocean_read_bounds(datum_ocean_t ctx, float *records);
+int datum_ocean_surface_slab(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, float *zlo, float *zhi, float *reachx, float *reachy);
+int datum_ocean_cast_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  void const *rays_device, size_t n, void *records_device);
+int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  float const *rays, size_t n, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -137,6 +137,12 @@ SYMBOLS = {
     "datum_ocean_surface_slab": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), P, P, P, P]),
     "datum_ocean_cast_rays_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_rays_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_set_velocity": (I, [P, I]),
+    "datum_ocean_bind_velocity": (I, [P, P, ctypes.c_size_t]),
+    "datum_ocean_velocity_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
+    "datum_ocean_read_velocity": (I, [P, I, P]),
+    "datum_ocean_sample_velocity_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_velocity_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -149,6 +155,10 @@ SPECTRUM_FORMATS = {"fp32": 0, "fp16": 1, "fp16h0": 2}
 
 # datum_ocean_set_map_store_policy's values
 MAP_STORE_POLICIES = {"auto": 0, "written through": 1, "streamed": 2}
+
+# datum_ocean_set_velocity's modes, and the floats of a velocity query's record
+VELOCITY_MODES = {"off": 0, "on": 1}
+VELOCITY_SAMPLE_FLOATS = 8
 
 # datum_ocean_set_foam's modes (ABI 9)
 FOAM_OFF, FOAM_JACOBIAN, FOAM_ACCUMULATE = 0, 1, 2
@@ -606,6 +616,45 @@ class Ocean:
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
         out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
+
+    # -- surface velocity (datum_ocean_set_velocity): d/dt of map layer 0, one float4 plane per cascade -----------------------------------
+
+    def set_velocity(self, mode):
+        """"off" (default) or "on": datum_ocean_displace then writes (vx, vy, vz, 0) per texel"""
+        if isinstance(mode, bool):
+            mode = int(mode)
+        self._check(self.lib.datum_ocean_set_velocity(self.h, VELOCITY_MODES[mode] if isinstance(mode, str) else int(mode)))
+
+    def bind_velocity(self, device_ptr, nbytes):
+        """caller-owned device memory (cascades * N * N * 16 bytes) becomes the velocity plane; None / 0 restores the handle's own"""
+        self._check(self.lib.datum_ocean_bind_velocity(self.h, P(device_ptr) if device_ptr else None, nbytes))
+
+    def velocity_device(self):
+        """(device pointer, bytes) of the velocity plane in use"""
+        p = P()
+        n = ctypes.c_size_t()
+        self._check(self.lib.datum_ocean_velocity_device(self.h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def read_velocity(self, cascade):
+        """the cascade's plane [N][N][4] float32: (vx, vy, vz, 0)"""
+        out = np.empty((self.N, self.N, 4), np.float32)
+        self._check(self.lib.datum_ocean_read_velocity(self.h, cascade, _ptr(out)))
+        return out
+
+    def sample_velocity_blend(self, cascades, oceanset, points_ptr, count, out_ptr, iterations=4):
+        """sample_surface_blend()'s solve, then the listed cascades' velocity planes at the same texels: device pointers, enqueued"""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_sample_velocity_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
+                                                               count, P(out_ptr) if out_ptr else None))
+
+    def read_velocity_blend(self, cascades, oceanset, points, iterations=4):
+        """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32: V(b), residual, velocity, 0"""
+        arr, n = self._list(cascades)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], VELOCITY_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_velocity_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
         return out
 
     # -- body buoyancy (datum_ocean_reduce_bodies): per-body force and torque from hull probes -----------------------------------------

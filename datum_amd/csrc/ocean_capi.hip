@@ -26,6 +26,7 @@
 #include "ocean_body.hip"
 #include "ocean_ray.hip"
 #include "ocean_bounds.hip"
+#include "ocean_velocity.hip"
 
 using namespace ocean;
 
@@ -117,6 +118,14 @@ struct datum_ocean_ctx
   BindablePlane<float> foam;          // the own plane exists while foam is on; off, nothing reads the plane (a binding is kept)
   FoamKernels foamkernels = {};
   double foamdt = 0.0;                // sum of the update dt's since the last displace (pending can be flushed at any time)
+
+  // surface velocity (datum_ocean_set_velocity): one float4 plane per cascade, computed by displace after the column pass and the foam
+  int velocitymode = DATUM_OCEAN_VELOCITY_OFF;
+  BindablePlane<float4> velocity;     // the own plane exists while velocity is on (a binding is kept)
+  VelocityKernels velocitykernels;    // configured when velocity is first switched on
+  cf *velocitywork = nullptr;         // [group][3][N*N] between the two velocity passes, while velocity is on
+  int velocityworkgroup = 0;          // cascades it was sized for
+  bool velocitycurrent = false;       // a displace has written the plane since velocity was switched on
 
   // datum_ocean_read_surface's device staging of points and records, grown on demand
   float2 *surfacepoints = nullptr;
@@ -697,6 +706,65 @@ namespace
     return fa;
   }
 
+  size_t velocity_bytes(datum_ocean_ctx const *ctx) { return (size_t)ctx->cascades * plane(ctx) * sizeof(float4); }
+
+  // the velocity passes' work buffer, sized for `group` cascades (grown where the cascade group has grown since velocity was switched on)
+  int ensure_velocity_work(datum_ocean_ctx *ctx, int group)
+  {
+    if (ctx->velocitywork && ctx->velocityworkgroup >= group)
+      return DATUM_OCEAN_OK;
+
+    if (ctx->velocitywork)
+    {
+      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+      HIPCHECK(ctx, hipFree(ctx->velocitywork));
+      ctx->velocitywork = nullptr;
+      ctx->velocityworkgroup = 0;
+    }
+
+    HIPCHECK(ctx, hipMalloc(&ctx->velocitywork, (size_t)group * 3 * plane(ctx) * sizeof(cf)));
+    ctx->velocityworkgroup = group;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the arguments of a displace call's velocity launches: the stored phase is behind the step's by the dt's its row pass did not store
+  VelocityArgs velocity_args(datum_ocean_ctx *ctx, PhaseWriteback::Launch const &step)
+  {
+    VelocityArgs va = {};
+    va.h0 = ctx->h0;
+    va.phase = ctx->phase;
+    va.omega = ctx->omega;
+    va.tw = ctx->tw;
+    va.work = ctx->velocitywork;
+    va.vel = ctx->velocity.get();
+    va.ndt = step.store ? 0 : step.ndt;
+
+    for(int c = 0; c < ctx->cascades; ++c)
+      va.wild = va.wild || ctx->cstate[c].wild;
+
+    for(int i = 0; i < MAX_PENDING; ++i)
+      va.dt[i] = (i < va.ndt) ? step.dt[i] : 0.0f;
+
+    memcpy(va.casc, ctx->casc, sizeof(va.casc));
+
+    return va;
+  }
+
+  // the velocity plane of the cascades [first, first + count): column pass, then row pass, on the handle's stream behind the group's step
+  int launch_velocity(datum_ocean_ctx *ctx, VelocityArgs &va, int first, int count, bool streamed)
+  {
+    va.first = first;
+
+    void *args[] = { &va };
+    VelocityKernels const &k = ctx->velocitykernels;
+
+    HIPCHECK(ctx, hipLaunchKernel(k.col, dim3(k.coltiles, count), dim3(k.colthreads), args, k.collds, ctx->stream));
+    HIPCHECK(ctx, hipLaunchKernel(k.row[streamed], dim3(k.rowgroups, count), dim3(k.rowthreads), args, k.rowlds, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
   // an ncclResult_t never leaves the module
   int fail_comm(datum_ocean_ctx *ctx, ocean::RcclApi *api, ncclComm_t comm, ncclResult_t r, char const *what)
   {
@@ -915,6 +983,8 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->litweights);
   (void)hipFree(ctx->scratch);
   (void)hipFree(ctx->foam.own);
+  (void)hipFree(ctx->velocity.own);
+  (void)hipFree(ctx->velocitywork);
   (void)hipFree(ctx->surfacepoints);
   (void)hipFree(ctx->surfacesamples);
   (void)hipFree(ctx->bodystage);
@@ -1359,6 +1429,18 @@ int datum_ocean_displace(datum_ocean_t ctx)
     plan.groups = 1;
   }
 
+  bool const velocity = ctx->velocitymode != DATUM_OCEAN_VELOCITY_OFF;
+
+  // (the velocity column pass multiplies by the dispersion even where no update is queued)
+  if (velocity)
+  {
+    rc = ensure_omega(ctx);
+    if (rc == DATUM_OCEAN_OK)
+      rc = ensure_velocity_work(ctx, plan.group);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+  }
+
   bool const sampling = ctx->profiling && ctx->profsteps < ctx->profmax;
   bool const prof = sampling && ctx->profcalls % ctx->profstride == 0;
 
@@ -1379,6 +1461,11 @@ int datum_ocean_displace(datum_ocean_t ctx)
     fa = foam_args(ctx);
 
   ctx->foamdt = 0.0;
+
+  VelocityArgs va;
+
+  if (velocity)
+    va = velocity_args(ctx, step);
 
   // new maps from here on: the bounds records (datum_ocean_reduce_bounds) are no longer theirs
   ctx->boundscurrent = false;
@@ -1413,7 +1500,18 @@ int datum_ocean_displace(datum_ocean_t ctx)
       if (rc != DATUM_OCEAN_OK)
         return rc;
     }
+
+    // ... and its velocity plane (not sampled either)
+    if (velocity)
+    {
+      rc = launch_velocity(ctx, va, a.first, a.cascades, plan.streamed);
+      if (rc != DATUM_OCEAN_OK)
+        return rc;
+    }
   }
+
+  if (velocity)
+    ctx->velocitycurrent = true;
 
   if (prof)
     ctx->profsteps += 1;
@@ -2291,6 +2389,196 @@ int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int c
 
 }   // extern "C"
 
+/* -- surface velocity (ocean_velocity.hip) -------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // what read_velocity and the two queries refuse; `name` goes into the error text
+  int check_velocity_state(datum_ocean_ctx *ctx, char const *name)
+  {
+    std::string const what = name;
+
+    if (ctx->velocitymode == DATUM_OCEAN_VELOCITY_OFF)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": velocity is off (datum_ocean_set_velocity)").c_str());
+
+    if (!ctx->velocitycurrent)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": no datum_ocean_displace since velocity was switched on").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  VelocityBlendArgs velocity_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *out)
+  {
+    VelocityBlendArgs vb = {};
+    vb.b = surface_blend_args(ctx, cascades, count, set, iterations, points, n, out);
+
+    for(int i = 0; i < count; ++i)
+      vb.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+
+    return vb;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_set_velocity(datum_ocean_t ctx, int mode)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_velocity: null handle");
+
+  if (mode != DATUM_OCEAN_VELOCITY_OFF && mode != DATUM_OCEAN_VELOCITY_ON)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_velocity: unknown mode");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  if (mode == DATUM_OCEAN_VELOCITY_OFF)
+  {
+    HIPCHECK(ctx, hipFree(ctx->velocity.own));
+    ctx->velocity.own = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->velocitywork));
+    ctx->velocitywork = nullptr;
+    ctx->velocityworkgroup = 0;
+    ctx->velocitymode = mode;
+    ctx->velocitycurrent = false;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  if (ctx->velocitymode == mode)
+    return DATUM_OCEAN_OK;
+
+  // the LDS limit of the kernels the mode launches: a kernel the module launches is one it configured
+  if (!ctx->velocitykernels.col)
+  {
+    VelocityKernels k;
+
+    DISPATCH_N(ctx->N, k = velocity_kernels<NN>());
+
+    HIPCHECK(ctx, hipFuncSetAttribute(k.col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.collds));
+    HIPCHECK(ctx, hipFuncSetAttribute(k.row[0], hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.rowlds));
+    HIPCHECK(ctx, hipFuncSetAttribute(k.row[1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.rowlds));
+
+    ctx->velocitykernels = k;
+  }
+
+  if (!ctx->velocity.own)
+    HIPCHECK(ctx, hipMalloc(&ctx->velocity.own, velocity_bytes(ctx)));
+
+  HIPCHECK(ctx, hipMemsetAsync(ctx->velocity.own, 0, velocity_bytes(ctx), ctx->stream));
+
+  int rc = ensure_velocity_work(ctx, plan_step(ctx).group);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  ctx->velocitymode = mode;
+  ctx->velocitycurrent = false;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_bind_velocity(datum_ocean_t ctx, void *device_ptr, size_t bytes)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_bind_velocity: null handle");
+
+  int rc = bind_plane(ctx, ctx->velocity, device_ptr, bytes, velocity_bytes(ctx),
+                      "datum_ocean_bind_velocity: buffer smaller than cascades * N * N * 16 bytes", "datum_ocean_bind_velocity: buffer must be 16-byte aligned");
+
+  // the plane in use changed: it holds a velocity again after the next displace
+  if (rc == DATUM_OCEAN_OK)
+    ctx->velocitycurrent = false;
+
+  return rc;
+}
+
+int datum_ocean_velocity_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
+{
+  if (!ctx || !device_ptr)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_velocity_device: null argument");
+
+  if (ctx->velocitymode == DATUM_OCEAN_VELOCITY_OFF)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_velocity_device: velocity is off (datum_ocean_set_velocity)");
+
+  *device_ptr = ctx->velocity.get();
+
+  if (bytes)
+    *bytes = velocity_bytes(ctx);
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_velocity(datum_ocean_t ctx, int cascade, float *vel)
+{
+  if (!ctx || !vel)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_velocity: null argument");
+
+  if (cascade < 0 || cascade >= ctx->cascades)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_velocity: cascade out of range");
+
+  int rc = check_velocity_state(ctx, "datum_ocean_read_velocity");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  size_t const P = plane(ctx);
+
+  HIPCHECK(ctx, hipMemcpyAsync(vel, ctx->velocity.get() + cascade * P, P * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_sample_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *out_device)
+{
+  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_sample_velocity_blend");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_surface_args(ctx, cascades[0], set, iterations, points_device, n, out_device, "datum_ocean_sample_velocity_blend");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_velocity_state(ctx, "datum_ocean_sample_velocity_blend");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  VelocityBlendArgs vb = velocity_blend_args(ctx, cascades, count, set, iterations, points_device, n, out_device);
+
+  HIPCHECK(ctx, launch_velocity_blend(vb, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *out)
+{
+  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_read_velocity_blend");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_surface_args(ctx, cascades[0], set, iterations, points, n, out, "datum_ocean_read_velocity_blend");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_velocity_state(ctx, "datum_ocean_read_velocity_blend");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  rc = stage_surface(ctx, points, n);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  VelocityBlendArgs vb = velocity_blend_args(ctx, cascades, count, set, iterations, ctx->surfacepoints, n, ctx->surfacesamples);
+
+  HIPCHECK(ctx, launch_velocity_blend(vb, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(out, ctx->surfacesamples, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
 /* -- body buoyancy (ocean_body.hip) -------------------------------------------------------------------------------------------- */
 
 namespace
@@ -3086,6 +3374,12 @@ int datum_ocean_release_memory(datum_ocean_t ctx, void *device_ptr)
 
       if (inside(ctx->foam.bound))
         ctx->foam.bound = nullptr;
+
+      if (inside(ctx->velocity.bound))
+      {
+        ctx->velocity.bound = nullptr;
+        ctx->velocitycurrent = false;
+      }
 
       hipError_t e = hipDestroyExternalMemory(ctx->importedmemory[i].memory);
 

@@ -5,6 +5,9 @@
 //   leaves:   vx, vy, vz, residual, mx, my, mz, foam -- the record's eight fields
 // With OCEAN_SURFACE_BLEND_POINT_HEIGHT defined by the includer (ocean_ray.hip's search) the final evaluation keeps to part A and leaves vz
 // alone, the same operations in the same order: the height has the record's bits, parts B and the foam planes are not fetched.
+// With OCEAN_SURFACE_BLEND_POINT_VELOCITY defined as the array of the listed cascades' velocity planes (ocean_velocity.hip) the final
+// evaluation leaves vx, vy, vz and residual with the record's bits, and ux, uy, uz: the planes sampled at t_c with the same fetch, summed
+// in list order; parts B and the foam planes are not fetched.
 TexelIndex<LAYOUT> const texel(s.N);
 
 int const nmask = s.N - 1;
@@ -88,6 +91,51 @@ for(int c = 0; c < count; ++c)
 }
 
 float const vz = (f.basez + p.swellamplitude * st) + dz;
+
+#elif defined(OCEAN_SURFACE_BLEND_POINT_VELOCITY)
+
+float dx = 0.0f, dy = 0.0f, dz = 0.0f, ux = 0.0f, uy = 0.0f, uz = 0.0f;
+
+for(int c = 0; c < count; ++c)
+{
+  BlendCascade const &bc = list.casc[c];
+
+  __amdgpu_buffer_rsrc_t const rmap = make_rsrc(bc.map, mapbytes);
+  __amdgpu_buffer_rsrc_t const rvel = make_rsrc((OCEAN_SURFACE_BLEND_POINT_VELOCITY)[c], (size_t)s.N * s.N * sizeof(float4));
+
+  SurfaceTexel<LAYOUT> const t(texel, f, bc.scale, nmask, px, py);
+
+  float4 const a00 = buf_load_f32x4_aux<0>(rmap, t.o00, 0);
+  float4 const a10 = buf_load_f32x4_aux<0>(rmap, t.o10, 0);
+  float4 const a01 = buf_load_f32x4_aux<0>(rmap, t.o01, 0);
+  float4 const a11 = buf_load_f32x4_aux<0>(rmap, t.o11, 0);
+
+  float4 const u00 = buf_load_f32x4_aux<0>(rvel, ((t.j0 << texel.ln) + t.i0) * 16, 0);
+  float4 const u10 = buf_load_f32x4_aux<0>(rvel, t.wantx ? ((t.j0 << texel.ln) + t.i1) * 16 : -256, 0);
+  float4 const u01 = buf_load_f32x4_aux<0>(rvel, t.wanty ? ((t.j1 << texel.ln) + t.i0) * 16 : -256, 0);
+  float4 const u11 = buf_load_f32x4_aux<0>(rvel, (t.wantx && t.wanty) ? ((t.j1 << texel.ln) + t.i1) * 16 : -256, 0);
+
+  float const cx = t.blend(a00.x, a10.x, a01.x, a11.x);
+  float const cy = t.blend(a00.y, a10.y, a01.y, a11.y);
+  float const cz = t.blend(a00.z, a10.z, a01.z, a11.z);
+
+  dx = (c == 0) ? cx : dx + cx;
+  dy = (c == 0) ? cy : dy + cy;
+  dz = (c == 0) ? cz : dz + cz;
+
+  float const wx = t.blend(u00.x, u10.x, u01.x, u11.x);
+  float const wy = t.blend(u00.y, u10.y, u01.y, u11.y);
+  float const wz = t.blend(u00.z, u10.z, u01.z, u11.z);
+
+  ux = (c == 0) ? wx : ux + wx;
+  uy = (c == 0) ? wy : uy + wy;
+  uz = (c == 0) ? wz : uz + wz;
+}
+
+float const vx = px - dx, vy = py - dy, vz = (f.basez + p.swellamplitude * st) + dz;
+
+float const rx = vx - q.x, ry = vy - q.y;
+float const residual = __builtin_sqrtf(fmaf(ry, ry, rx * rx));
 
 #else
 

@@ -329,6 +329,36 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_velocity(void *c, int mode)
+  {
+    try
+    {
+      set_ocean_velocity(static_cast<HostContext*>(c)->context, mode);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_read_ocean_velocity(void *c, float *velocity)
+  {
+    try
+    {
+      read_ocean_velocity(static_cast<HostContext*>(c)->context, velocity);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_query_ocean_velocity(void *c, void *p, float const *xy, size_t count, float *samples, int iterations)
+  {
+    try
+    {
+      query_ocean_velocity(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanVelocitySample*>(samples), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_reduce_ocean_bodies(void *c, void *p, void const *bodies, size_t nbodies, float const *probes, size_t nprobes, float *records, int iterations)
   {
     try

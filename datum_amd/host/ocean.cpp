@@ -891,6 +891,34 @@ void query_ocean_surface(OceanContext &context, OceanParams const &params, Vec2 
 }
 
 
+///////////////////////// velocity //////////////////////////////////////////
+void set_ocean_velocity(OceanContext &context, int mode)
+{
+  assert(context.ready);
+
+  check(context.hip, datum_ocean_set_velocity(context.hip, mode), "datum_ocean_set_velocity");
+}
+
+void read_ocean_velocity(OceanContext &context, float *velocity)
+{
+  assert(context.ready);
+
+  check(context.hip, datum_ocean_read_velocity(context.hip, 0, velocity), "datum_ocean_read_velocity");
+}
+
+void query_ocean_velocity(OceanContext &context, OceanParams const &params, Vec2 const *positions, size_t count, OceanVelocitySample *samples, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("query_ocean_velocity: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_velocity_blend(context.hip, &cascade, 1, &set, iterations, reinterpret_cast<float const*>(positions), count, reinterpret_cast<float*>(samples)), "datum_ocean_read_velocity_blend");
+}
+
+
 ///////////////////////// reduce_ocean_bodies ///////////////////////////////
 void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, size_t nbodies, OceanBodyProbe const *probes, size_t nprobes, OceanBodyRecord *records, int iterations)
 {

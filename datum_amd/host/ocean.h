@@ -356,6 +356,24 @@ static_assert(sizeof(OceanSurfaceSample) == 32, "OceanSurfaceSample must be the 
 
 void query_ocean_surface(OceanContext &context, OceanParams const &params, lml::Vec2 const *positions, std::size_t count, OceanSurfaceSample *samples, int iterations = 4);
 
+// surface velocity (include/datum_ocean_hip.h: datum_ocean_set_velocity, the definition there): d/dt of the displacement at every texel,
+// computed by every displace while on (DATUM_OCEAN_VELOCITY_OFF / _ON), and the same surface point as query_ocean_surface with the
+// velocity there instead of normal and foam.  One cascade, as query_ocean_surface; the swell's own motion is not included.  Blocking.
+// read_ocean_velocity and query_ocean_velocity throw while velocity is off and until a displace has written the plane
+struct OceanVelocitySample
+{
+  lml::Vec3 position;                     // the surface point found: query_ocean_surface's, bit for bit
+  float residual;                         // ... and its residual
+  lml::Vec3 velocity;                     // (vx, vy, vz) in metres per second
+  float pad;                              // 0
+};
+
+static_assert(sizeof(OceanVelocitySample) == 32, "OceanVelocitySample must be the C ABI's record of DATUM_OCEAN_VELOCITY_SAMPLE_FLOATS floats");
+
+void set_ocean_velocity(OceanContext &context, int mode);
+void read_ocean_velocity(OceanContext &context, float *velocity /* [N][N][4] */);
+void query_ocean_velocity(OceanContext &context, OceanParams const &params, lml::Vec2 const *positions, std::size_t count, OceanVelocitySample *samples, int iterations = 4);
+
 // body buoyancy (include/datum_ocean_hip.h: datum_ocean_read_bodies, the definition there): per body the net buoyant force, its torque
 // and a few aggregates over the body's hull probes, reduced on the device.  One cascade, as query_ocean_surface; the maps the context last
 // displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before prepare_ocean_context

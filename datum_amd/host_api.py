@@ -98,6 +98,9 @@ def load():
             "datum_host_set_ocean_foam_params": (I, [P, F, F, F]),
             "datum_host_read_ocean_foam": (I, [P, P]),
             "datum_host_query_ocean_surface": (I, [P, P, P, ctypes.c_size_t, P, I]),
+            "datum_host_set_ocean_velocity": (I, [P, I]),
+            "datum_host_read_ocean_velocity": (I, [P, P]),
+            "datum_host_query_ocean_velocity": (I, [P, P, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
@@ -314,6 +317,23 @@ class OceanContext:
         pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         out = np.empty((pts.shape[0], capi.SURFACE_SAMPLE_FLOATS), np.float32)
         self._check(self.lib.datum_host_query_ocean_surface(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
+        return out
+
+    def set_velocity(self, mode):
+        """set_ocean_velocity: "off", "on" or a capi.VELOCITY_MODES value"""
+        self._check(self.lib.datum_host_set_ocean_velocity(self.c, capi.VELOCITY_MODES[mode] if isinstance(mode, str) else int(mode)))
+
+    def read_velocity(self):
+        """read_ocean_velocity: [N][N][4] float32 (vx, vy, vz, 0)"""
+        out = np.empty((self.N, self.N, 4), np.float32)
+        self._check(self.lib.datum_host_read_ocean_velocity(self.c, out.ctypes.data_as(P)))
+        return out
+
+    def query_ocean_velocity(self, params, xy, iterations=4):
+        """query_ocean_velocity: (M, 8) float32 records (OceanVelocitySample: position, residual, velocity, 0)"""
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], capi.VELOCITY_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_host_query_ocean_velocity(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
         return out
 
     def reduce_ocean_bodies(self, params, bodies, probes, iterations=4):

@@ -50,7 +50,9 @@ extern "C" {
  *      the several-cascade calls datum_ocean_gen_blend, datum_ocean_sample_surface_blend and datum_ocean_read_surface_blend; then body
  *      buoyancy, datum_ocean_reduce_bodies and datum_ocean_read_bodies; then ray casts, datum_ocean_cast_rays and datum_ocean_read_rays; then
  *      surface bounds, datum_ocean_reduce_bounds, datum_ocean_bounds_device, datum_ocean_read_bounds and datum_ocean_surface_slab, with the
- *      bounded casts datum_ocean_cast_rays_bounded and datum_ocean_read_rays_bounded.
+ *      bounded casts datum_ocean_cast_rays_bounded and datum_ocean_read_rays_bounded; then the surface velocity, datum_ocean_set_velocity,
+ *      datum_ocean_bind_velocity, datum_ocean_velocity_device, datum_ocean_read_velocity, datum_ocean_sample_velocity_blend and
+ *      datum_ocean_read_velocity_blend.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -555,6 +557,62 @@ int datum_ocean_cast_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
                                   void const *rays_device, size_t n, void *records_device);
 int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   float const *rays, size_t n, float *records);
+
+/* -- surface velocity (added at ABI 9; nothing in the reference) ------------------------------------------------------------------------
+ * How is the water moving?  For drag and slamming forces on floating bodies, drift of debris and spray, foam advection, a renderer's
+ * motion vectors.  The maps are overwritten every step and the difference of two steps cancels to noise in fp32 at a small dt; but the
+ * maps are a linear function of h0 e^{i phase} with d phase / dt = omega(k), so the exact time derivative is one more spectrum and one
+ * more pair of transforms.  In the notation of oracle/ocean_oracle.cpp: sim_rows / map_rows, with a = h0[k], m = h0[(N-1-y, N-1-x)],
+ * phase = the phase the step's maps were formed from, omega = the value update_ocean advances that texel's phase by per second (the
+ * handle's dispersion table) and k^ as in sim:
+ *
+ *     ht.re = omega · ( −(a.x + m.x) sin phase − (a.y + m.y) cos phase )
+ *     ht.im = omega · (  (a.x − m.x) cos phase − (a.y − m.y) sin phase )        (= omega · d/d phase of sim's h)
+ *     htx   = ( ht.im k^x, −ht.re k^x ),   hty = ( ht.im k^y, −ht.re k^y )
+ *     vz = Re T(ht)·sigma,   vx = Re T(htx)·sigma·choppiness,   vy = Re T(hty)·sigma·choppiness
+ *
+ * T is the step's own 2-D transform, sigma = (−1)^(x+y).  (vx, vy, vz) is d/dt of map layer 0's (dx, dy, dz) at a fixed texel, in metres
+ * per second where dt is in seconds.  THE SWELL IS NOT INCLUDED: the swell term of datum_ocean_gen is the caller's -- swellphase is a field
+ * of the set the module does not advance -- and so is its time derivative.
+ *
+ * Modes, per handle (datum_ocean_set_velocity): OFF (default) -- nothing is computed or allocated, every other call behaves as without
+ * velocity; ON -- datum_ocean_displace writes the plane.
+ * STORAGE: one plane per cascade, row-major [cascade][y][x] of float4 (vx, vy, vz, 0), 16 * N * N bytes -- a plain RGBA32F image a renderer
+ * samples with the displacement map's texture coordinate (and repeat addressing), or imports (datum_ocean_bind_velocity).  The plain
+ * layout at every N, not the maps' patches.
+ * Computed by datum_ocean_displace in every configuration (spectrum formats, literal mode, map-store policies, cascade groups, phase
+ * write-back intervals, bound maps): two launches (columns, then rows) after each cascade group's column pass and foam launch (after the literal dispatches in
+ * the literal mode).  They read the fp32 h0, the phase and the dispersion table whatever the spectrum format, and a work buffer of their own
+ * (24 * N * N bytes per cascade of a group).  Maps, phase and foam are bit for bit those of a handle with velocity off, and the plane does
+ * not depend on the write-back interval: where the step's row pass did not store the phase, the velocity column pass applies the same dt's
+ * to the stored value by the same operations and stores nothing.
+ * NOT included in: the farm payloads, datum_ocean_gen, datum_ocean_export_maps, the profile's events, datum_ocean_algorithmic_bytes.
+ *   set_velocity            mode: ON allocates the own plane (zero-filled) and the work buffer; OFF frees both.  Drains the stream
+ *   bind_velocity           caller-owned DEVICE memory of at least cascades * N * N * 16 bytes, 16-byte aligned, becomes the plane; NULL
+ *                           restores the handle's own.  Allowed in any mode
+ *   velocity_device         the plane in use and its bytes; ESTATE while velocity is OFF
+ *   read_velocity           blocking read of the cascade's N * N * 4 floats (host pointer)
+ *   sample_velocity_blend   datum_ocean_sample_surface_blend's arguments and rules (list, set, iterations, alignment, ordering; the
+ *                           handle's scale_c).  Each point gets a record of DATUM_OCEAN_VELOCITY_SAMPLE_FLOATS = 8 floats (32 bytes):
+ *                             0-3  datum_ocean_sample_surface_blend's V(b) and residual, bit for bit
+ *                             4-6  the sum over the list of the REPEAT bilinear sample of cascade c's velocity plane at t_c: the same weights,
+ *                                  fract wrap and blend order; added in list order, the first cascade taken as it is
+ *                             7    0
+ *                           A non-finite q gives a record of quiet NaNs and fetches nothing
+ *   read_velocity_blend     the same from HOST arrays, blocking, through the staging buffers datum_ocean_read_surface uses
+ * DATUM_OCEAN_ESTATE from read_velocity and the two queries while velocity is OFF, and while no datum_ocean_displace has run since velocity
+ * was switched on (the plane holds nothing yet); otherwise the foam calls' and the several-cascade query's errors. */
+#define DATUM_OCEAN_VELOCITY_OFF 0
+#define DATUM_OCEAN_VELOCITY_ON 1
+#define DATUM_OCEAN_VELOCITY_SAMPLE_FLOATS 8
+int datum_ocean_set_velocity(datum_ocean_t ctx, int mode);
+int datum_ocean_bind_velocity(datum_ocean_t ctx, void *device_ptr, size_t bytes);
+int datum_ocean_velocity_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes);
+int datum_ocean_read_velocity(datum_ocean_t ctx, int cascade, float *vel);
+int datum_ocean_sample_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                      void const *points_device, size_t n, void *out_device);
+int datum_ocean_read_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                    float const *points, size_t n, float *out);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -5,7 +5,7 @@ HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -fno-f
 
 LIB = datum_amd/lib/libdatum_ocean_hip.so
 SRC = datum_amd/csrc/ocean_capi.hip
-DEPS = datum_amd/csrc/ocean_kernels.hip datum_amd/csrc/ocean_literal.hip datum_amd/csrc/ocean_gen.hip datum_amd/csrc/ocean_farm.hip datum_amd/csrc/ocean_foam.hip datum_amd/csrc/ocean_surface.hip datum_amd/csrc/ocean_blend.hip datum_amd/csrc/ocean_body.hip datum_amd/csrc/ocean_body.h datum_amd/csrc/ocean_ray.hip datum_amd/csrc/ocean_ray.h datum_amd/csrc/ocean_bounds.hip datum_amd/csrc/ocean_bounds.h datum_amd/csrc/ocean_velocity.hip datum_amd/csrc/ocean_velocity.h $(wildcard datum_amd/csrc/ocean_gen_*.inc datum_amd/csrc/ocean_surface_*.inc) datum_amd/csrc/ocean_fft_core.h datum_amd/csrc/ocean_layout.h datum_amd/csrc/ocean_writeback.h datum_amd/csrc/ocean_phase.h include/datum_ocean_hip.h
+DEPS = datum_amd/csrc/ocean_kernels.hip datum_amd/csrc/ocean_literal.hip datum_amd/csrc/ocean_gen.hip datum_amd/csrc/ocean_farm.hip datum_amd/csrc/ocean_foam.hip datum_amd/csrc/ocean_surface.hip datum_amd/csrc/ocean_query.hip datum_amd/csrc/ocean_blend.hip datum_amd/csrc/ocean_body.hip datum_amd/csrc/ocean_body.h datum_amd/csrc/ocean_ray.hip datum_amd/csrc/ocean_ray.h datum_amd/csrc/ocean_bounds.hip datum_amd/csrc/ocean_bounds.h datum_amd/csrc/ocean_velocity.hip datum_amd/csrc/ocean_velocity.h $(wildcard datum_amd/csrc/ocean_gen_*.inc) datum_amd/csrc/ocean_fft_core.h datum_amd/csrc/ocean_layout.h datum_amd/csrc/ocean_writeback.h datum_amd/csrc/ocean_phase.h include/datum_ocean_hip.h
 
 HOSTLIB = datum_amd/lib/libdatum_ocean_host.so
 HOSTSRC = datum_amd/host/ocean.cpp datum_amd/host/host_capi.cpp

@@ -12,34 +12,19 @@
 //     per SIMD;
 //   * gen's per-wave shortcuts, per cascade: `shaded` (the wave needs normals) depends on the distance smoothing alone, `near` (some
 //     second texel has a weight) on scale_c -- a fine cascade is beyond 2^23 texels where a coarse one is not;
-//   * ocean_surface_blend_kernel is ocean_surface_kernel with V(b) summed over the list (SurfaceTexel per cascade); parts B and the foam
-//     planes are fetched in the final evaluation only.  The solve and the final evaluation of one point are text of their own
-//     (ocean_surface_blend_point.inc), which ocean_body_kernel (ocean_body.hip) includes as well;
+//   * ocean_surface_blend_kernel is ocean_surface_kernel with V(b) summed over the list; parts B and the foam planes are fetched in the
+//     final evaluation only.  The solve and the final evaluations of one point are functions of their own (ocean_query.hip: query_solve,
+//     query_record, ...), which the body, ray and velocity kernels call as well;
 //   * the list travels in the kernel argument: 16 x (map, foam plane, scale) = 384 bytes.
 // LDS: gen's vertex staging; no scratch (make resource-usage).
 
 #pragma once
 
 #include "ocean_gen.hip"
-#include "ocean_surface.hip"
+#include "ocean_query.hip"
 
 namespace ocean
 {
-  struct BlendCascade
-  {
-    float4 const *map;      // the cascade's displacement map, map_cascade_bytes(N) bytes
-    float const *foam;      // the cascade's foam plane, N * N floats; nullptr while foam is OFF
-    float scale;            // the handle's 1 / wavescale of the cascade
-    int pad;
-  };
-
-  struct BlendList
-  {
-    int count;
-    int foammode;           // DATUM_OCEAN_FOAM_*: how the queries combine the planes
-    BlendCascade casc[DATUM_OCEAN_MAX_CASCADES];
-  };
-
   struct GenBlendArgs
   {
     GenArgs g;              // g.map and g.set.scale are not read
@@ -48,8 +33,10 @@ namespace ocean
 
   struct SurfaceBlendArgs
   {
-    SurfaceArgs s;          // s.map, s.foam and s.set.scale are not read
-    BlendList list;
+    QueryArgs q;
+    float2 const *points;
+    float4 *samples;        // 2 float4 per point
+    int count;
   };
 
   template<int LAYOUT>
@@ -182,60 +169,10 @@ namespace ocean
     #include "ocean_gen_store.inc"
   }
 
-  // gen's frame m.x t0 + m.y t1 + m.z t2 normalised (ocean_surface.hip, gen.comp:101-120 with smoothing = 0), for dn = normalize(sx, sy, 1)
-  __device__ __forceinline__ void blend_surface_normal(GenFrame const &f, float st, float ct, float sx, float sy, float &mx, float &my, float &mz)
-  {
-    float nx = sx, ny = sy, nz = 1.0f;
-
-    normalize3(nx, ny, nz);
-
-    float t2x = -f.nx * ct, t2y = -f.ny * ct, t2z = fmaf(-f.nz, st, 1.0f);
-    float t0x = fmaf(-f.tx, st, 1.0f), t0y = -f.ty * st, t0z = f.tz * ct;
-
-    normalize3(t2x, t2y, t2z);
-    normalize3(t0x, t0y, t0z);
-
-    float const t1x = t0y * t2z - t0z * t2y, t1y = t0z * t2x - t0x * t2z, t1z = t0x * t2y - t0y * t2x;
-
-    mx = fmaf(nz, t2x, fmaf(ny, t1x, nx * t0x));
-    my = fmaf(nz, t2y, fmaf(ny, t1y, nx * t0y));
-    mz = fmaf(nz, t2z, fmaf(ny, t1z, nx * t0z));
-
-    normalize3(mx, my, mz);
-  }
-
   template<int LAYOUT>
   __global__ void __launch_bounds__(SURFACE_THREADS) ocean_surface_blend_kernel(SurfaceBlendArgs b)
   {
-    SurfaceArgs const &s = b.s;
-
-    int const k = (int)blockIdx.x * SURFACE_THREADS + (int)threadIdx.x;
-
-    if (k >= s.count)
-      return;
-
-    datum_ocean_set const &p = s.set;
-    GenFrame const &f = s.frame;
-
-    float2 const q = s.points[k];
-
-    float4 *out = s.samples + 2 * (size_t)k;
-
-    if (!__builtin_isfinite(q.x) || !__builtin_isfinite(q.y))
-    {
-      float const nan = __builtin_nanf("");
-
-      out[0] = make_float4(nan, nan, nan, nan);
-      out[1] = make_float4(nan, nan, nan, nan);
-      return;
-    }
-
-    BlendList const &list = b.list;
-
-    #include "ocean_surface_blend_point.inc"
-
-    out[0] = make_float4(vx, vy, vz, residual);
-    out[1] = make_float4(mx, my, mz, foam);
+    query_each_point(b.points, b.samples, b.count, [&](float2 q) { return query_record<LAYOUT>(b.q, query_solve<LAYOUT>(b.q, q), q); });
   }
 
   inline void const *gen_blend_kernel_for(int N)
@@ -266,13 +203,13 @@ namespace ocean
     return hipLaunchKernel(gen_blend_kernel_for(N), dim3(gen_groups(b.g)), dim3(GEN_THREADS), args, GEN_LDS, stream);
   }
 
-  // b.s.set, points, samples, N, count (> 0), iterations and b.list filled in
+  // b.q (but its frame), points, samples and count (> 0) filled in
   inline hipError_t launch_surface_blend(SurfaceBlendArgs &b, hipStream_t stream)
   {
-    b.s.frame = make_gen_frame(b.s.set, b.s.N, 2, 2);      // the camera's terms are not read
+    query_frame(b.q);
 
     void *args[] = { &b };
 
-    return hipLaunchKernel(surface_blend_kernel_for(b.s.N), dim3((unsigned)((b.s.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+    return hipLaunchKernel(surface_blend_kernel_for(b.q.N), dim3((unsigned)((b.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
   }
 }

@@ -1,7 +1,8 @@
 // ocean_body.hip -- body buoyancy (include/datum_ocean_hip.h: datum_ocean_reduce_bodies): per body, the net buoyant force, its torque and a
 // few aggregates over the body's hull probes, each probe moved to world space with the body's pose and held against the summed surface
 // above it.  The arithmetic of a probe and the order of the sum are ocean_body.h's (a CPU walks the same functions); the surface record of
-// a probe is the several-cascade query's, the same text (ocean_surface_blend_point.inc), so its bits are datum_ocean_sample_surface_blend's.
+// a probe is the several-cascade query's, the same functions (ocean_query.hip: query_solve, query_record), so its bits are
+// datum_ocean_sample_surface_blend's.
 //
 //   * one wave per body, four bodies per 256-thread workgroup; lane l takes probes first + l, first + l + 64, ...;
 //   * a probe is one 16-byte load per lane, 64 consecutive probes per wave and pass, through a buffer resource laid over exactly the
@@ -21,8 +22,7 @@ namespace ocean
 {
   struct BodyArgs
   {
-    SurfaceArgs s;          // s.set, s.frame, s.N and s.iterations are read
-    BlendList list;
+    QueryArgs q;
     datum_ocean_body const *bodies;
     BodyProbe const *probes;
     float4 *records;        // 2 float4 per body
@@ -84,11 +84,6 @@ namespace ocean
     if (body >= a.nbodies)
       return;
 
-    SurfaceArgs const &s = a.s;
-    datum_ocean_set const &p = s.set;
-    GenFrame const &f = s.frame;
-    BlendList const &list = a.list;
-
     datum_ocean_body const B = a.bodies[body];
 
     bool bad = body_range_bad(B, a.nprobes);
@@ -121,16 +116,11 @@ namespace ocean
 
       if (have && !probebad)
       {
-        float rec[DATUM_OCEAN_SURFACE_SAMPLE_FLOATS];
+        float2 const q = make_float2(w.x, w.y);
 
-        {
-          float2 const q = make_float2(w.x, w.y);
+        QueryRecord const r = query_record<LAYOUT>(a.q, query_solve<LAYOUT>(a.q, q), q);
 
-          #include "ocean_surface_blend_point.inc"
-
-          rec[0] = vx; rec[1] = vy; rec[2] = vz; rec[3] = residual;
-          rec[4] = mx; rec[5] = my; rec[6] = mz; rec[7] = foam;
-        }
+        float const rec[DATUM_OCEAN_SURFACE_SAMPLE_FLOATS] = { r.v.x, r.v.y, r.v.z, r.v.w, r.m.x, r.m.y, r.m.z, r.m.w };
 
         body_add(wave.p, body_terms(B, w, probe.a, rec));
       }
@@ -162,13 +152,13 @@ namespace ocean
     }
   }
 
-  // a.s.set, N, iterations, a.list, bodies, probes, records, nbodies (> 0) and nprobes filled in
+  // a.q (but its frame), bodies, probes, records, nbodies (> 0) and nprobes filled in
   inline hipError_t launch_bodies(BodyArgs &a, hipStream_t stream)
   {
-    a.s.frame = make_gen_frame(a.s.set, a.s.N, 2, 2);      // the camera's terms are not read
+    query_frame(a.q);
 
     void *args[] = { &a };
 
-    return hipLaunchKernel(body_kernel_for(a.s.N), dim3((unsigned)(((size_t)a.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
+    return hipLaunchKernel(body_kernel_for(a.q.N), dim3((unsigned)(((size_t)a.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
   }
 }

@@ -11,9 +11,9 @@
 //   * ocean_bounds_final_kernel: one wave per cascade folds the G partials (a workgroup without texels wrote the identity) into the record;
 //   * cache policy: plain loads, the foam kernel's choice for the same 16 bytes per point right behind the column pass (ocean_foam.hip;
 //     DESIGN.md 5.10): the maps of a resident handle are in the Infinity Cache then, and a streamed handle's are not whatever the load says;
-//   * ocean_ray_bounded_kernel: ocean_ray_kernel's body (ocean_ray.hip) with ray_search_bounded in place of ray_search.  The slab is formed
-//     at the top from the listed cascades' records in the handle's bounds buffer: wave-uniform reads of at most 16 x 32 bytes.  Every
-//     height is still ocean_surface_blend_point.inc with OCEAN_SURFACE_BLEND_POINT_HEIGHT, the record at `hi` the full text once.
+//   * ocean_ray_bounded_kernel: ocean_ray_kernel's body (ocean_ray.hip: ray_cast) with ray_search_bounded in place of ray_search.  The slab
+//     is formed at the top from the listed cascades' records in the handle's bounds buffer: wave-uniform reads of at most 16 x 32 bytes.
+//     Every height is still query_height, the record at `hi` query_record once (ocean_query.hip).
 // LDS: 3 x 32 bytes in the partial kernel; no scratch (make resource-usage).
 
 #pragma once
@@ -207,89 +207,23 @@ namespace ocean
 
   struct RayBoundedArgs
   {
-    RayArgs r;
+    QueryArgs q;
+    RayBatch r;
     float const *bounds;    // the handle's records, [cascade][BOUNDS_FIELDS]
-    int cascades[DATUM_OCEAN_MAX_CASCADES];   // the list as cascade numbers (r.list holds their maps)
+    int cascades[DATUM_OCEAN_MAX_CASCADES];   // the list as cascade numbers (q.list holds their maps)
   };
 
   // (eight waves per SIMD as ocean_ray_kernel has them: left alone the compiler takes 106 scalar registers, which leaves room for seven)
   template<int LAYOUT>
   __attribute__((amdgpu_waves_per_eu(8, 8)))
-  __global__ void __launch_bounds__(RAY_THREADS) ocean_ray_bounded_kernel(RayBoundedArgs ba)
+  __global__ void __launch_bounds__(RAY_THREADS) ocean_ray_bounded_kernel(RayBoundedArgs a)
   {
-    RayArgs const &a = ba.r;
+    RayBatch const &r = a.r;
 
     // the slab of the list under the set: the records through a wave-uniform index (scalar loads)
-    BoundsSlab const slab = bounds_slab(ba.bounds, ba.cascades, a.list.count, a.s.frame.basez, a.s.set.swellamplitude, a.s.frame.gx, a.s.frame.gy);
+    BoundsSlab const slab = bounds_slab(a.bounds, a.cascades, a.q.list.count, a.q.frame.basez, a.q.set.swellamplitude, a.q.frame.gx, a.q.frame.gy);
 
-    // the workgroup's rays and records and nothing else (n <= INT32_MAX: first < 2^31)
-    int const first = (int)blockIdx.x * RAY_THREADS;
-    int const left = a.n - first;
-    int const here = left < RAY_THREADS ? left : RAY_THREADS;
-    int const lane = (int)threadIdx.x;
-
-    if (lane >= here)
-      return;
-
-    __amdgpu_buffer_rsrc_t const rrays = make_rsrc(a.rays + 2 * (size_t)first, (size_t)here * RAY_BYTES);
-    __amdgpu_buffer_rsrc_t const rrecords = make_rsrc(a.records + 3 * (size_t)first, (size_t)here * RAY_RECORD_BYTES);
-
-    float4 const r0 = buf_load_f32x4_aux<0>(rrays, lane * RAY_BYTES, 0);
-    float4 const r1 = buf_load_f32x4_aux<0>(rrays, lane * RAY_BYTES + 16, 0);
-
-    Ray const ray = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
-
-    int const out = lane * RAY_RECORD_BYTES;
-
-    float const nan = __builtin_nanf("");
-
-    if (ray_bad(ray))
-    {
-      buf_store_f32x4_aux<0>(make_float4(nan, nan, nan, nan), rrecords, out, 0);
-      buf_store_f32x4_aux<0>(make_float4(nan, nan, nan, nan), rrecords, out, 16);
-      buf_store_f32x4_aux<0>(make_float4(nan, nan, nan, nan), rrecords, out, 32);
-      return;
-    }
-
-    SurfaceArgs const &s = a.s;
-    datum_ocean_set const &p = s.set;
-    GenFrame const &f = s.frame;
-    BlendList const &list = a.list;
-
-    // rec.z of the query above (x, y), a NaN where the query gives NaNs
-    auto height = [&](float x, float y) -> float
-    {
-      if (!ray_finite(x) || !ray_finite(y))
-        return nan;
-
-      float2 const q = make_float2(x, y);
-
-      #define OCEAN_SURFACE_BLEND_POINT_HEIGHT
-      #include "ocean_surface_blend_point.inc"
-      #undef OCEAN_SURFACE_BLEND_POINT_HEIGHT
-
-      return vz;
-    };
-
-    RayBracket const b = ray_search_bounded(ray, a.steps, a.inv, a.refine, slab.zlo, slab.zhi, height);
-
-    RayPoint const at = ray_point(ray, b.hi);
-
-    float4 rec0 = make_float4(nan, nan, nan, nan), rec1 = rec0;
-
-    if (ray_finite(at.x) && ray_finite(at.y))
-    {
-      float2 const q = make_float2(at.x, at.y);
-
-      #include "ocean_surface_blend_point.inc"
-
-      rec0 = make_float4(vx, vy, vz, residual);
-      rec1 = make_float4(mx, my, mz, foam);
-    }
-
-    buf_store_f32x4_aux<0>(make_float4(b.hi, b.lo, ray_g(at.z, rec0.z), ray_status(b.hit, b.side)), rrecords, out, 0);
-    buf_store_f32x4_aux<0>(rec0, rrecords, out, 16);
-    buf_store_f32x4_aux<0>(rec1, rrecords, out, 32);
+    ray_cast<LAYOUT>(a.q, r, [&](Ray const &ray, auto &height) { return ray_search_bounded(ray, r.steps, r.inv, r.refine, slab.zlo, slab.zhi, height); });
   }
 
   inline void const *ray_bounded_kernel_for(int N)
@@ -301,14 +235,9 @@ namespace ocean
     }
   }
 
-  // a.r as launch_rays takes it; a.bounds and a.cascades filled in
+  // a.q and a.r as launch_rays takes them; a.bounds and a.cascades filled in
   inline hipError_t launch_rays_bounded(RayBoundedArgs &a, hipStream_t stream)
   {
-    a.r.s.frame = make_gen_frame(a.r.s.set, a.r.s.N, 2, 2);      // the camera's terms are not read
-    a.r.inv = 1.0f / (float)a.r.steps;
-
-    void *args[] = { &a };
-
-    return hipLaunchKernel(ray_bounded_kernel_for(a.r.s.N), dim3((unsigned)(((size_t)a.r.n + RAY_THREADS - 1) / RAY_THREADS)), dim3(RAY_THREADS), args, 0, stream);
+    return ray_launch(ray_bounded_kernel_for(a.q.N), a.q, a.r, &a, stream);
   }
 }

@@ -22,6 +22,7 @@
 #include "ocean_farm.hip"
 #include "ocean_foam.hip"
 #include "ocean_surface.hip"
+#include "ocean_query.hip"
 #include "ocean_blend.hip"
 #include "ocean_body.hip"
 #include "ocean_ray.hip"
@@ -56,6 +57,18 @@ struct BindablePlane
   T *bound = nullptr;
   T *get() const { return bound ? bound : own; }   // the plane in use
 };
+
+// a device buffer of a host entry point's (read_*) staging, grown on demand
+struct Staging
+{
+  void *ptr = nullptr;
+  size_t capacity = 0;                // bytes
+
+  int reserve(struct datum_ocean_ctx *ctx, size_t bytes);
+};
+
+// one per array a read_* query stages, kept apart per family: a family's growth frees nothing another family's launch may still read
+enum { STAGE_POINTS, STAGE_SAMPLES, STAGE_BODIES, STAGE_BODY_RECORDS, STAGE_PROBES, STAGE_RAYS, STAGE_RAY_RECORDS, STAGE_COUNT };
 
 // the host's record of one cascade (what the kernels read of it is CascadeConst)
 struct CascadeState
@@ -127,22 +140,7 @@ struct datum_ocean_ctx
   int velocityworkgroup = 0;          // cascades it was sized for
   bool velocitycurrent = false;       // a displace has written the plane since velocity was switched on
 
-  // datum_ocean_read_surface's device staging of points and records, grown on demand
-  float2 *surfacepoints = nullptr;
-  float4 *surfacesamples = nullptr;
-  size_t surfacecapacity = 0;         // points both hold
-
-  // datum_ocean_read_bodies' device staging, each grown on demand: bodies with their records, and probes
-  datum_ocean_body *bodystage = nullptr;
-  float4 *bodyrecords = nullptr;
-  size_t bodycapacity = 0;            // bodies both hold
-  BodyProbe *probestage = nullptr;
-  size_t probecapacity = 0;
-
-  // datum_ocean_read_rays' device staging, grown on demand: rays with their records
-  float4 *raystage = nullptr;
-  float4 *rayrecords = nullptr;
-  size_t raycapacity = 0;             // rays both hold
+  Staging staging[STAGE_COUNT];       // the read_* queries' device staging
 
   // datum_ocean_reduce_bounds: the records, [cascades] x 32 bytes, and the workgroups' partials, both allocated by the first reduce
   float4 *bounds = nullptr;
@@ -985,13 +983,10 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->foam.own);
   (void)hipFree(ctx->velocity.own);
   (void)hipFree(ctx->velocitywork);
-  (void)hipFree(ctx->surfacepoints);
-  (void)hipFree(ctx->surfacesamples);
-  (void)hipFree(ctx->bodystage);
-  (void)hipFree(ctx->bodyrecords);
-  (void)hipFree(ctx->probestage);
-  (void)hipFree(ctx->raystage);
-  (void)hipFree(ctx->rayrecords);
+
+  for(Staging &st : ctx->staging)
+    (void)hipFree(st.ptr);
+
   (void)hipFree(ctx->bounds);
   (void)hipFree(ctx->boundspartials);
 
@@ -2155,24 +2150,63 @@ int datum_ocean_read_foam(datum_ocean_t ctx, int cascade, float *foam)
 
 /* -- surface queries ------------------------------------------------------------------------------------------------------- */
 
+int Staging::reserve(datum_ocean_ctx *ctx, size_t bytes)
+{
+  if (bytes <= capacity)
+    return DATUM_OCEAN_OK;
+
+  // the old staging may still be read by an earlier launch of this stream (a call that grows several buffers waits once for
+  // each: after the first the stream holds at most that call's own copy in)
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHECK(ctx, hipFree(ptr));
+  ptr = nullptr;
+  capacity = 0;
+
+  HIPCHECK(ctx, hipMalloc(&ptr, bytes));
+  capacity = bytes;
+
+  return DATUM_OCEAN_OK;
+}
+
 namespace
 {
-  // the argument checks both entry points share; `name` goes into the error text
-  int check_surface_args(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void const *samples, char const *name)
+  // a read_* twin behind its checks: `in` and `out` grown to hold the call's arrays, `src` copied in on the handle's stream, `run` -- the
+  // device-array twin's own launch path -- on the staging, the result copied out to `dst` and waited for
+  template<class Run>
+  int read_staged(datum_ocean_ctx *ctx, Staging &in, void const *src, size_t inbytes, Staging &out, void *dst, size_t outbytes, Run &&run)
+  {
+    int rc = in.reserve(ctx, inbytes);
+    if (rc == DATUM_OCEAN_OK)
+      rc = out.reserve(ctx, outbytes);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    HIPCHECK(ctx, hipMemcpyAsync(in.ptr, src, inbytes, hipMemcpyHostToDevice, ctx->stream));
+
+    rc = run(in.ptr, out.ptr);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    HIPCHECK(ctx, hipMemcpyAsync(dst, out.ptr, outbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // ... of a one-point-per-thread query: `count` points in, two float4 per point out
+  template<class Run>
+  int read_points(datum_ocean_ctx *ctx, float const *points, size_t count, float *samples, Run &&run)
+  {
+    return read_staged(ctx, ctx->staging[STAGE_POINTS], points, count * sizeof(float2), ctx->staging[STAGE_SAMPLES], samples, count * 2 * sizeof(float4), run);
+  }
+
+  // the arrays of a one-point-per-thread query; `name` goes into the error text
+  int check_points(datum_ocean_ctx *ctx, void const *points, size_t count, void const *samples, char const *name)
   {
     std::string const what = name;
 
-    if (!ctx || !set)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle or set").c_str());
-
     if (count > 0 && (!points || !samples))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or samples").c_str());
-
-    if (cascade < 0 || cascade >= ctx->cascades)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
-
-    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
 
     if (((uintptr_t)points & 7) || ((uintptr_t)samples & 15))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and samples 16-byte aligned").c_str());
@@ -2183,7 +2217,25 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  SurfaceArgs surface_args(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void *samples)
+  // the argument checks both single-cascade entry points share
+  int check_surface_args(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void const *samples, char const *name)
+  {
+    std::string const what = name;
+
+    if (!ctx || !set)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle or set").c_str());
+
+    if (cascade < 0 || cascade >= ctx->cascades)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
+
+    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
+
+    return check_points(ctx, points, count, samples, name);
+  }
+
+  // the launch both single-cascade entry points share: device arrays, count > 0
+  int run_surface(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void *samples)
   {
     SurfaceArgs s;
     s.set = *set;
@@ -2194,28 +2246,8 @@ namespace
     s.N = ctx->N;
     s.count = (int)count;
     s.iterations = iterations;
-    return s;
-  }
 
-  // the host entry points' device staging of `count` points and records (grown on demand), the points copied in on the handle's stream
-  int stage_surface(datum_ocean_ctx *ctx, float const *points, size_t count)
-  {
-    if (count > ctx->surfacecapacity)
-    {
-      // the old staging may still be read by an earlier launch of this stream
-      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCHECK(ctx, hipFree(ctx->surfacepoints));
-      HIPCHECK(ctx, hipFree(ctx->surfacesamples));
-      ctx->surfacepoints = nullptr;
-      ctx->surfacesamples = nullptr;
-      ctx->surfacecapacity = 0;
-
-      HIPCHECK(ctx, hipMalloc(&ctx->surfacepoints, count * sizeof(float2)));
-      HIPCHECK(ctx, hipMalloc(&ctx->surfacesamples, count * 2 * sizeof(float4)));
-      ctx->surfacecapacity = count;
-    }
-
-    HIPCHECK(ctx, hipMemcpyAsync(ctx->surfacepoints, points, count * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, launch_surface(s, ctx->stream));
 
     return DATUM_OCEAN_OK;
   }
@@ -2232,11 +2264,7 @@ int datum_ocean_sample_surface(datum_ocean_t ctx, int cascade, datum_ocean_set c
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  SurfaceArgs s = surface_args(ctx, cascade, set, iterations, points_device, count, samples_device);
-
-  HIPCHECK(ctx, launch_surface(s, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return run_surface(ctx, cascade, set, iterations, points_device, count, samples_device);
 }
 
 int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set const *set, int iterations, float const *points, size_t count, float *samples)
@@ -2247,17 +2275,7 @@ int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set con
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  rc = stage_surface(ctx, points, count);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  SurfaceArgs s = surface_args(ctx, cascade, set, iterations, ctx->surfacepoints, count, ctx->surfacesamples);
-
-  HIPCHECK(ctx, launch_surface(s, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(samples, ctx->surfacesamples, count * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return read_points(ctx, points, count, samples, [&](void const *in, void *out) { return run_surface(ctx, cascade, set, iterations, in, count, out); });
 }
 
 }   // extern "C"
@@ -2266,7 +2284,7 @@ int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set con
 
 namespace
 {
-  // the list's checks, shared by the three entry points; `name` goes into the error text
+  // the list's checks, shared by every entry point that takes one; `name` goes into the error text
   int check_blend_list(datum_ocean_ctx *ctx, int const *cascades, int count, char const *name)
   {
     std::string const what = name;
@@ -2283,6 +2301,24 @@ namespace
     for(int i = 0; i < count; ++i)
       if (cascades[i] < 0 || cascades[i] >= ctx->cascades)
         return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // what every query on the summed surface checks first: the handle and the list, the set, the iterations
+  int check_query(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, char const *name)
+  {
+    int rc = check_blend_list(ctx, cascades, count, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (!set)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
+
+    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
 
     return DATUM_OCEAN_OK;
   }
@@ -2305,14 +2341,36 @@ namespace
     return l;
   }
 
-  SurfaceBlendArgs surface_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  // (the frame is the launch's: query_frame)
+  QueryArgs query_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations)
+  {
+    QueryArgs q = {};
+    q.set = *set;
+    q.list = blend_list(ctx, cascades, count);
+    q.N = ctx->N;
+    q.iterations = iterations;
+    return q;
+  }
+
+  int check_surface_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void const *samples, char const *name)
+  {
+    int rc = check_query(ctx, cascades, count, set, iterations, name);
+
+    return rc != DATUM_OCEAN_OK ? rc : check_points(ctx, points, n, samples, name);
+  }
+
+  // device arrays, n > 0
+  int run_surface_blend(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
   {
     SurfaceBlendArgs b;
-    b.s = surface_args(ctx, cascades[0], set, iterations, points, n, samples);
-    b.s.map = nullptr;
-    b.s.foam = nullptr;
-    b.list = blend_list(ctx, cascades, count);
-    return b;
+    b.q = query_args(ctx, cascades, count, set, iterations);
+    b.points = static_cast<float2 const*>(points);
+    b.samples = static_cast<float4*>(samples);
+    b.count = (int)n;
+
+    HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
+
+    return DATUM_OCEAN_OK;
   }
 }
 
@@ -2349,42 +2407,24 @@ int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, dat
 
 int datum_ocean_sample_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
 {
-  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_sample_surface_blend");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_args(ctx, cascades[0], set, iterations, points_device, n, samples_device, "datum_ocean_sample_surface_blend");
+  int rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points_device, n, samples_device, "datum_ocean_sample_surface_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  SurfaceBlendArgs b = surface_blend_args(ctx, cascades, count, set, iterations, points_device, n, samples_device);
-
-  HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return run_surface_blend(ctx, cascades, count, set, iterations, points_device, n, samples_device);
 }
 
 int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
 {
-  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_read_surface_blend");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_args(ctx, cascades[0], set, iterations, points, n, samples, "datum_ocean_read_surface_blend");
+  int rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples, "datum_ocean_read_surface_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  rc = stage_surface(ctx, points, n);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  SurfaceBlendArgs b = surface_blend_args(ctx, cascades, count, set, iterations, ctx->surfacepoints, n, ctx->surfacesamples);
-
-  HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(samples, ctx->surfacesamples, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend(ctx, cascades, count, set, iterations, in, n, out); });
 }
 
 }   // extern "C"
@@ -2407,15 +2447,29 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  VelocityBlendArgs velocity_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *out)
+  // the several-cascade query's checks, then the state both velocity queries need
+  int check_velocity_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void const *out, char const *name)
+  {
+    int rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points, n, out, name);
+
+    return rc != DATUM_OCEAN_OK ? rc : check_velocity_state(ctx, name);
+  }
+
+  // device arrays, n > 0
+  int run_velocity_blend(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *out)
   {
     VelocityBlendArgs vb = {};
-    vb.b = surface_blend_args(ctx, cascades, count, set, iterations, points, n, out);
+    vb.q = query_args(ctx, cascades, count, set, iterations);
+    vb.points = static_cast<float2 const*>(points);
+    vb.samples = static_cast<float4*>(out);
+    vb.count = (int)n;
 
     for(int i = 0; i < count; ++i)
       vb.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
 
-    return vb;
+    HIPCHECK(ctx, launch_velocity_blend(vb, ctx->stream));
+
+    return DATUM_OCEAN_OK;
   }
 }
 
@@ -2535,46 +2589,24 @@ int datum_ocean_read_velocity(datum_ocean_t ctx, int cascade, float *vel)
 
 int datum_ocean_sample_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *out_device)
 {
-  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_sample_velocity_blend");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_args(ctx, cascades[0], set, iterations, points_device, n, out_device, "datum_ocean_sample_velocity_blend");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_velocity_state(ctx, "datum_ocean_sample_velocity_blend");
+  int rc = check_velocity_blend_args(ctx, cascades, count, set, iterations, points_device, n, out_device, "datum_ocean_sample_velocity_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  VelocityBlendArgs vb = velocity_blend_args(ctx, cascades, count, set, iterations, points_device, n, out_device);
-
-  HIPCHECK(ctx, launch_velocity_blend(vb, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return run_velocity_blend(ctx, cascades, count, set, iterations, points_device, n, out_device);
 }
 
 int datum_ocean_read_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *out)
 {
-  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_read_velocity_blend");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_args(ctx, cascades[0], set, iterations, points, n, out, "datum_ocean_read_velocity_blend");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_velocity_state(ctx, "datum_ocean_read_velocity_blend");
+  int rc = check_velocity_blend_args(ctx, cascades, count, set, iterations, points, n, out, "datum_ocean_read_velocity_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  rc = stage_surface(ctx, points, n);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  VelocityBlendArgs vb = velocity_blend_args(ctx, cascades, count, set, iterations, ctx->surfacepoints, n, ctx->surfacesamples);
-
-  HIPCHECK(ctx, launch_velocity_blend(vb, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(out, ctx->surfacesamples, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return read_points(ctx, points, n, out, [&](void const *in, void *dev) { return run_velocity_blend(ctx, cascades, count, set, iterations, in, n, dev); });
 }
 
 }   // extern "C"
@@ -2587,17 +2619,11 @@ namespace
   int check_body_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
                       void const *probes, size_t nprobes, void const *records, char const *name)
   {
-    int rc = check_blend_list(ctx, cascades, count, name);
+    int rc = check_query(ctx, cascades, count, set, iterations, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
-
-    if (!set)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
-
-    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
 
     if ((nbodies > 0 && (!bodies || !records)) || (nprobes > 0 && !probes))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null bodies, probes or records").c_str());
@@ -2611,59 +2637,19 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  BodyArgs body_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
-                     void const *probes, size_t nprobes, void *records)
+  // device arrays, nbodies > 0
+  int run_bodies(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
+                 void const *probes, size_t nprobes, void *records)
   {
     BodyArgs a;
-    a.s = surface_args(ctx, cascades[0], set, iterations, nullptr, 0, nullptr);
-    a.s.map = nullptr;
-    a.s.foam = nullptr;
-    a.list = blend_list(ctx, cascades, count);
+    a.q = query_args(ctx, cascades, count, set, iterations);
     a.bodies = static_cast<datum_ocean_body const*>(bodies);
     a.probes = static_cast<BodyProbe const*>(probes);
     a.records = static_cast<float4*>(records);
     a.nbodies = (int)nbodies;
     a.nprobes = (int)nprobes;
-    return a;
-  }
 
-  // the host entry point's device staging of `nbodies` bodies with their records and of `nprobes` probes, each grown on demand, the
-  // arrays copied in on the handle's stream
-  int stage_bodies(datum_ocean_ctx *ctx, datum_ocean_body const *bodies, size_t nbodies, float const *probes, size_t nprobes)
-  {
-    if (nbodies > ctx->bodycapacity || nprobes > ctx->probecapacity)
-    {
-      // the old staging may still be read by an earlier launch of this stream
-      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-      if (nbodies > ctx->bodycapacity)
-      {
-        HIPCHECK(ctx, hipFree(ctx->bodystage));
-        HIPCHECK(ctx, hipFree(ctx->bodyrecords));
-        ctx->bodystage = nullptr;
-        ctx->bodyrecords = nullptr;
-        ctx->bodycapacity = 0;
-
-        HIPCHECK(ctx, hipMalloc(&ctx->bodystage, nbodies * sizeof(datum_ocean_body)));
-        HIPCHECK(ctx, hipMalloc(&ctx->bodyrecords, nbodies * 2 * sizeof(float4)));
-        ctx->bodycapacity = nbodies;
-      }
-
-      if (nprobes > ctx->probecapacity)
-      {
-        HIPCHECK(ctx, hipFree(ctx->probestage));
-        ctx->probestage = nullptr;
-        ctx->probecapacity = 0;
-
-        HIPCHECK(ctx, hipMalloc(&ctx->probestage, nprobes * sizeof(BodyProbe)));
-        ctx->probecapacity = nprobes;
-      }
-    }
-
-    HIPCHECK(ctx, hipMemcpyAsync(ctx->bodystage, bodies, nbodies * sizeof(datum_ocean_body), hipMemcpyHostToDevice, ctx->stream));
-
-    if (nprobes > 0)
-      HIPCHECK(ctx, hipMemcpyAsync(ctx->probestage, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, launch_bodies(a, ctx->stream));
 
     return DATUM_OCEAN_OK;
   }
@@ -2681,11 +2667,7 @@ int datum_ocean_reduce_bodies(datum_ocean_t ctx, int const *cascades, int count,
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  BodyArgs a = body_args(ctx, cascades, count, set, iterations, bodies_device, nbodies, probes_device, nprobes, records_device);
-
-  HIPCHECK(ctx, launch_bodies(a, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return run_bodies(ctx, cascades, count, set, iterations, bodies_device, nbodies, probes_device, nprobes, records_device);
 }
 
 int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
@@ -2697,17 +2679,18 @@ int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, d
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  rc = stage_bodies(ctx, bodies, nbodies, probes, nprobes);
+  // the probes beside the bodies: a staging of their own, grown on its own
+  Staging &dprobes = ctx->staging[STAGE_PROBES];
+
+  rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  BodyArgs a = body_args(ctx, cascades, count, set, iterations, ctx->bodystage, nbodies, ctx->probestage, nprobes, ctx->bodyrecords);
+  if (nprobes > 0)
+    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
 
-  HIPCHECK(ctx, launch_bodies(a, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->bodyrecords, nbodies * 2 * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
+                     [&](void const *in, void *out) { return run_bodies(ctx, cascades, count, set, iterations, in, nbodies, dprobes.ptr, nprobes, out); });
 }
 
 }   // extern "C"
@@ -2716,21 +2699,15 @@ int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, d
 
 namespace
 {
-  // the checks both entry points share; `name` goes into the error text
+  // the checks the four entry points share; `name` goes into the error text
   int check_ray_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                      void const *rays, size_t n, void const *records, char const *name)
   {
-    int rc = check_blend_list(ctx, cascades, count, name);
+    int rc = check_query(ctx, cascades, count, set, iterations, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
-
-    if (!set)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
-
-    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
 
     if (steps < 1 || steps > DATUM_OCEAN_RAY_MAX_STEPS)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": steps outside [1, DATUM_OCEAN_RAY_MAX_STEPS]").c_str());
@@ -2750,44 +2727,36 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  RayArgs ray_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-                   void const *rays, size_t n, void *records)
+  RayBatch ray_batch(int steps, int refine, void const *rays, size_t n, void *records)
   {
-    RayArgs a;
-    a.s = surface_args(ctx, cascades[0], set, iterations, nullptr, 0, nullptr);
-    a.s.map = nullptr;
-    a.s.foam = nullptr;
-    a.list = blend_list(ctx, cascades, count);
-    a.rays = static_cast<float4 const*>(rays);
-    a.records = static_cast<float4*>(records);
-    a.n = (int)n;
-    a.steps = steps;
-    a.refine = refine;
-    a.inv = 0.0f;           // launch_rays
-    return a;
+    RayBatch r;
+    r.rays = static_cast<float4 const*>(rays);
+    r.records = static_cast<float4*>(records);
+    r.n = (int)n;
+    r.steps = steps;
+    r.refine = refine;
+    r.inv = 0.0f;           // ray_launch
+    return r;
   }
 
-  // the host entry point's device staging of `n` rays and records (grown on demand), the rays copied in on the handle's stream
-  int stage_rays(datum_ocean_ctx *ctx, float const *rays, size_t n)
+  // device arrays, n > 0
+  int run_rays(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+               void const *rays, size_t n, void *records)
   {
-    if (n > ctx->raycapacity)
-    {
-      // the old staging may still be read by an earlier launch of this stream
-      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCHECK(ctx, hipFree(ctx->raystage));
-      HIPCHECK(ctx, hipFree(ctx->rayrecords));
-      ctx->raystage = nullptr;
-      ctx->rayrecords = nullptr;
-      ctx->raycapacity = 0;
+    RayArgs a;
+    a.q = query_args(ctx, cascades, count, set, iterations);
+    a.r = ray_batch(steps, refine, rays, n, records);
 
-      HIPCHECK(ctx, hipMalloc(&ctx->raystage, n * RAY_BYTES));
-      HIPCHECK(ctx, hipMalloc(&ctx->rayrecords, n * RAY_RECORD_BYTES));
-      ctx->raycapacity = n;
-    }
-
-    HIPCHECK(ctx, hipMemcpyAsync(ctx->raystage, rays, n * RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, launch_rays(a, ctx->stream));
 
     return DATUM_OCEAN_OK;
+  }
+
+  // a read_* twin of a ray cast: `n` rays in, a record per ray out
+  template<class Run>
+  int read_rays(datum_ocean_ctx *ctx, float const *rays, size_t n, float *records, Run &&run)
+  {
+    return read_staged(ctx, ctx->staging[STAGE_RAYS], rays, n * RAY_BYTES, ctx->staging[STAGE_RAY_RECORDS], records, n * RAY_RECORD_BYTES, run);
   }
 }
 
@@ -2803,11 +2772,7 @@ int datum_ocean_cast_rays(datum_ocean_t ctx, int const *cascades, int count, dat
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  RayArgs a = ray_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
-
-  HIPCHECK(ctx, launch_rays(a, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return run_rays(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
 }
 
 int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
@@ -2819,17 +2784,7 @@ int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, dat
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  rc = stage_rays(ctx, rays, n);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  RayArgs a = ray_args(ctx, cascades, count, set, iterations, steps, refine, ctx->raystage, n, ctx->rayrecords);
-
-  HIPCHECK(ctx, launch_rays(a, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->rayrecords, n * RAY_RECORD_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
 }
 
 }   // extern "C"
@@ -2892,17 +2847,21 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  RayBoundedArgs ray_bounded_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-                                  void const *rays, size_t n, void *records)
+  // device arrays, n > 0
+  int run_rays_bounded(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                       void const *rays, size_t n, void *records)
   {
     RayBoundedArgs a;
-    a.r = ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records);
+    a.q = query_args(ctx, cascades, count, set, iterations);
+    a.r = ray_batch(steps, refine, rays, n, records);
     a.bounds = reinterpret_cast<float const*>(ctx->bounds);
 
     for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
       a.cascades[c] = (c < count) ? cascades[c] : 0;
 
-    return a;
+    HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
   }
 }
 
@@ -2984,11 +2943,7 @@ int datum_ocean_cast_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  RayBoundedArgs a = ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
-
-  HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return run_rays_bounded(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
 }
 
 int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
@@ -3000,17 +2955,7 @@ int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  rc = stage_rays(ctx, rays, n);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  RayBoundedArgs a = ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, ctx->raystage, n, ctx->rayrecords);
-
-  HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(records, ctx->rayrecords, n * RAY_RECORD_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_bounded(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
 }
 
 }   // extern "C"

@@ -325,46 +325,19 @@ namespace ocean
 
   struct VelocityBlendArgs
   {
-    SurfaceBlendArgs b;                                   // the several-cascade query's own arguments; b.list's foam planes are not read
+    QueryArgs q;                                          // q.list's foam planes are not read
+    float2 const *points;
+    float4 *samples;                                      // 2 float4 per point
+    int count;
     float4 const *vel[DATUM_OCEAN_MAX_CASCADES];          // the listed cascades' velocity planes, in list order
   };
 
-  // datum_ocean_sample_velocity_blend: the several-cascade query's solve and V(b) (ocean_surface_blend_point.inc, bit for bit), then the
-  // listed cascades' velocity planes at the same texture coordinates with the same fetch
+  // datum_ocean_sample_velocity_blend: the several-cascade query's solve and V(b) (ocean_query.hip: query_solve, bit for bit), then the
+  // listed cascades' velocity planes at the same texture coordinates with the same fetch (query_velocity)
   template<int LAYOUT>
   __global__ void __launch_bounds__(SURFACE_THREADS) ocean_velocity_blend_kernel(VelocityBlendArgs vb)
   {
-    SurfaceArgs const &s = vb.b.s;
-
-    int const k = (int)blockIdx.x * SURFACE_THREADS + (int)threadIdx.x;
-
-    if (k >= s.count)
-      return;
-
-    datum_ocean_set const &p = s.set;
-    GenFrame const &f = s.frame;
-
-    float2 const q = s.points[k];
-
-    float4 *out = s.samples + 2 * (size_t)k;
-
-    if (!__builtin_isfinite(q.x) || !__builtin_isfinite(q.y))
-    {
-      float const nan = __builtin_nanf("");
-
-      out[0] = make_float4(nan, nan, nan, nan);
-      out[1] = make_float4(nan, nan, nan, nan);
-      return;
-    }
-
-    BlendList const &list = vb.b.list;
-
-    #define OCEAN_SURFACE_BLEND_POINT_VELOCITY vb.vel
-    #include "ocean_surface_blend_point.inc"
-    #undef OCEAN_SURFACE_BLEND_POINT_VELOCITY
-
-    out[0] = make_float4(vx, vy, vz, residual);
-    out[1] = make_float4(ux, uy, uz, 0.0f);
+    query_each_point(vb.points, vb.samples, vb.count, [&](float2 q) { return query_velocity<LAYOUT>(vb.q, query_solve<LAYOUT>(vb.q, q), q, vb.vel); });
   }
 
   inline void const *velocity_blend_kernel_for(int N)
@@ -376,13 +349,13 @@ namespace ocean
     }
   }
 
-  // vb.b.s.set, points, samples, N, count (> 0), iterations, vb.b.list and vb.vel filled in
+  // vb.q (but its frame), points, samples, count (> 0) and vb.vel filled in
   inline hipError_t launch_velocity_blend(VelocityBlendArgs &vb, hipStream_t stream)
   {
-    vb.b.s.frame = make_gen_frame(vb.b.s.set, vb.b.s.N, 2, 2);      // the camera's terms are not read
+    query_frame(vb.q);
 
     void *args[] = { &vb };
 
-    return hipLaunchKernel(velocity_blend_kernel_for(vb.b.s.N), dim3((unsigned)((vb.b.s.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+    return hipLaunchKernel(velocity_blend_kernel_for(vb.q.N), dim3((unsigned)((vb.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
   }
 }

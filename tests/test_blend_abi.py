@@ -76,7 +76,8 @@ def test_the_shared_mesh_stages_are_stated_once():
     # what tests/test_gen64.py pins for ocean_gen.hip holds for the included text as well -- the header's sin / cos, no copy of its constants
     csrc = os.path.join(ROOT, "datum_amd", "csrc")
     read = lambda name: open(os.path.join(csrc, name), encoding="utf-8").read()
-    gen, blend = read("ocean_gen.hip"), read("ocean_blend.hip")
+    # (the blend kernels with the per-point query functions they include: ocean_query.hip holds the queries' frame)
+    gen, blend = read("ocean_gen.hip"), read("ocean_query.hip") + read("ocean_blend.hip")
     for stage in ("tile", "ray", "texel", "frame", "store"):
         inc = f'#include "ocean_gen_{stage}.inc"'
         assert gen.count(inc) == 1 and blend.count(inc) == 1, stage

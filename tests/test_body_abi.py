@@ -1,6 +1,6 @@
 """CPU tests of body buoyancy's interface (include/datum_ocean_hip.h: datum_ocean_reduce_bodies): the header declares the entry points and
 states the definition, the library exports them, the binding has its methods, signatures and the body's layout, the argument checks that
-need no device answer, and the per-point text of the several-cascade query is included once by each of its two kernels."""
+need no device answer, and the per-point functions of the several-cascade query are defined once and are what its kernels call."""
 
 import ctypes
 import os
@@ -83,11 +83,37 @@ def test_argument_errors_without_gpu():
         assert name.encode() in lib.datum_ocean_last_error(None)
 
 
+CSRC = os.path.join(ROOT, "datum_amd", "csrc")
+QUERY_FUNCTIONS = ("query_solve", "query_height", "query_record", "query_velocity")
+
+
+def read_csrc(name):
+    return open(os.path.join(CSRC, name), encoding="utf-8").read()
+
+
+def assert_query_is_stated_once():
+    """the fixed-point solve and each final evaluation of the several-cascade query: functions of ocean_query.hip, defined once in the whole
+    module, over one corner fetch (the only place beside the single-cascade kernel that makes a SurfaceTexel); the text they replace is gone"""
+    assert not os.path.exists(os.path.join(CSRC, "ocean_surface_blend_point.inc"))
+    assert "ocean_surface_" not in open(os.path.join(ROOT, "Makefile"), encoding="utf-8").read().replace("ocean_surface.hip", "")
+    sources = {name: read_csrc(name) for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".h", ".inc"))}
+    for fn in QUERY_FUNCTIONS:
+        defined = {name: len(re.findall(r"__device__ __forceinline__ \w+ %s\(" % fn, text)) for name, text in sources.items()}
+        assert defined.pop("ocean_query.hip") == 1 and not any(defined.values()), (fn, defined)
+    assert sum(text.count("struct QueryCorners") for text in sources.values()) == 1
+    assert sum(text.count("void query_each_point(") for text in sources.values()) == 1
+    users = sorted(name for name, text in sources.items() if re.search(r"SurfaceTexel<LAYOUT>\s+(const\s+)?&?\w", text))
+    assert users == ["ocean_query.hip", "ocean_surface.hip"], users
+    assert sources["ocean_query.hip"].count("buf_load_f32x4_aux<0>(rmap") == 4           # the four corners' part A, once
+
+
 def test_the_point_evaluation_is_stated_once():
-    # the fixed-point solve and the final evaluation of the several-cascade query: one text, included by the query and by the body kernel
-    csrc = os.path.join(ROOT, "datum_amd", "csrc")
-    read = lambda name: open(os.path.join(csrc, name), encoding="utf-8").read()
-    blend, body, point = read("ocean_blend.hip"), read("ocean_body.hip"), read("ocean_surface_blend_point.inc")
-    inc = '#include "ocean_surface_blend_point.inc"'
-    assert blend.count(inc) == 1 and body.count(inc) == 1
-    assert len(point) > 0
+    # the query kernel and the body kernel reach their records through the functions alone: neither makes a texel or loads from a map
+    assert_query_is_stated_once()
+    blend, body = read_csrc("ocean_blend.hip"), read_csrc("ocean_body.hip")
+    kernel = blend.split("ocean_surface_blend_kernel(SurfaceBlendArgs b)")[1].split("inline void const *gen_blend_kernel_for")[0]
+    for text in (kernel, body):
+        assert text.count("query_record<LAYOUT>(") == 1 and text.count("query_solve<LAYOUT>(") == 1
+        assert "SurfaceTexel" not in text and "rmap" not in text and ".map" not in text
+    assert "buf_load" not in kernel and "query_each_point(" in kernel
+    assert re.findall(r"buf_load\w*(?:<\d+>)?\((\w+)", body) == ["rprobes"]

@@ -94,14 +94,17 @@ def test_argument_errors_without_gpu():
 
 
 def test_the_height_is_the_query_text():
-    # the bounded kernel is text of its own beside the ray kernel's (which is as it was): the several-cascade query's one text twice, once
-    # for the height alone; the search is ocean_bounds.h's, which has no fmaf and leaves ray_search to ocean_ray.h
-    csrc = os.path.join(ROOT, "datum_amd", "csrc")
-    read = lambda name: open(os.path.join(csrc, name), encoding="utf-8").read()
-    inc = '#include "ocean_surface_blend_point.inc"'
-    assert read("ocean_bounds.hip").count(inc) == 2 and read("ocean_ray.hip").count(inc) == 2
-    assert read("ocean_bounds.hip").count("#define OCEAN_SURFACE_BLEND_POINT_HEIGHT") == 1
-    assert "ray_search_bounded(" in read("ocean_bounds.hip") and "ray_search_bounded" not in read("ocean_ray.hip") + read("ocean_ray.h")
+    # the bounded kernel is the ray kernel's one body (ray_cast, ocean_ray.hip) around a search of its own: it states no height, record,
+    # texel or load itself; the search is ocean_bounds.h's, which has no fmaf and leaves ray_search to ocean_ray.h
+    from test_body_abi import assert_query_is_stated_once, read_csrc as read
+
+    assert_query_is_stated_once()
+    rays = read("ocean_bounds.hip").split("struct RayBoundedArgs")[1]
+    assert rays.count("ray_cast<LAYOUT>(") == 1 and read("ocean_ray.hip").count("void ray_cast(") == 1
+    for word in ("SurfaceTexel", "buf_load", "buf_store", "query_", "rmap", ".map"):
+        assert word not in rays, word
+    assert "amdgpu_waves_per_eu(8, 8)" in rays
+    assert "ray_search_bounded(" in rays and "ray_search_bounded" not in read("ocean_ray.hip") + read("ocean_ray.h")
     assert "fmaf" not in read("ocean_bounds.h").replace("there is no fmaf here", "")
     assert "LAYOUT" not in read("ocean_bounds.hip").split("ocean_bounds_partial_kernel(BoundsArgs a)")[1].split("struct RayBoundedArgs")[0]
     assert '#include "ocean_bounds.hip"' in read("ocean_capi.hip")

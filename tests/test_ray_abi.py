@@ -84,12 +84,15 @@ def test_argument_errors_without_gpu():
 
 
 def test_the_height_is_the_query_text():
-    # the search's height and the record at hi: the several-cascade query's one text, included twice by the ray kernel (once for the height
-    # alone), and still once by the query and by the body kernel
-    csrc = os.path.join(ROOT, "datum_amd", "csrc")
-    read = lambda name: open(os.path.join(csrc, name), encoding="utf-8").read()
-    inc = '#include "ocean_surface_blend_point.inc"'
-    assert read("ocean_blend.hip").count(inc) == 1 and read("ocean_body.hip").count(inc) == 1 and read("ocean_ray.hip").count(inc) == 2
-    assert read("ocean_ray.hip").count("#define OCEAN_SURFACE_BLEND_POINT_HEIGHT") == 1
+    # the search's height and the record at hi: the several-cascade query's functions, each called once by the one ray-cast body; the
+    # kernel loads its rays and nothing of a map
+    from test_body_abi import assert_query_is_stated_once, read_csrc as read
+
+    assert_query_is_stated_once()
+    ray = read("ocean_ray.hip")
+    assert ray.count("query_height<LAYOUT>(") == 1 and ray.count("query_record<LAYOUT>(") == 1 and ray.count("query_solve<LAYOUT>(") == 2
+    assert "SurfaceTexel" not in ray and "rmap" not in ray and ".map" not in ray
+    assert re.findall(r"buf_load\w*(?:<\d+>)?\((\w+)", ray) == ["rrays", "rrays"]
+    assert ray.count("void ray_cast(") == 1 and ray.count("ray_cast<LAYOUT>(") == 1 and "ray_search(ray," in ray
     assert "fmaf" not in read("ocean_ray.h").replace("there is no fmaf here", "")
     assert '#include "ocean_ray.hip"' in read("ocean_capi.hip")

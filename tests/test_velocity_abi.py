@@ -96,6 +96,12 @@ def test_ocean_binding_has_velocity_methods():
 
 
 def test_the_blend_point_text_is_guarded():
-    text = open(os.path.join(ROOT, "datum_amd", "csrc", "ocean_surface_blend_point.inc"), encoding="utf-8").read()
-    assert text.count("#elif defined(OCEAN_SURFACE_BLEND_POINT_VELOCITY)") == 1
-    assert text.count("#ifdef OCEAN_SURFACE_BLEND_POINT_HEIGHT") == 1
+    # the velocity query is the several-cascade query's prologue and solve with a final evaluation of its own beside the record's and the
+    # height's, each a function defined once; the query kernel states no texel and no load itself
+    from test_body_abi import assert_query_is_stated_once, read_csrc as read
+
+    assert_query_is_stated_once()
+    kernel = read("ocean_velocity.hip").split("struct VelocityBlendArgs")[1]
+    assert kernel.count("query_velocity<LAYOUT>(") == 1 and kernel.count("query_solve<LAYOUT>(") == 1 and kernel.count("query_each_point(") == 1
+    for word in ("SurfaceTexel", "buf_load", "rmap", ".map"):
+        assert word not in kernel, word

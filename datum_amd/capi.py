@@ -143,6 +143,8 @@ SYMBOLS = {
     "datum_ocean_read_velocity": (I, [P, I, P]),
     "datum_ocean_sample_velocity_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_velocity_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_reduce_body_drag": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_body_drag": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
 }
 
 
@@ -188,6 +190,24 @@ class Body(ctypes.Structure):
 
 # the same layout for numpy: an array of this dtype is an array of Body
 BODY_DTYPE = np.dtype([("rotation", np.float32, 9), ("position", np.float32, 3), ("first", np.int32), ("count", np.int32), ("cap", np.float32), ("pad", np.int32)])
+
+# body drag (datum_ocean_reduce_body_drag, added at ABI 9): floats per body record
+DRAG_RECORD_FLOATS = 8
+
+
+class BodyMotion(ctypes.Structure):
+    """datum_ocean_body_motion of include/datum_ocean_hip.h: 32 bytes"""
+
+    _fields_ = [
+        ("linear", F * 3),
+        ("angular", F * 3),
+        ("cl", F),
+        ("cq", F),
+    ]
+
+
+# the same layout for numpy: an array of this dtype is an array of BodyMotion
+BODY_MOTION_DTYPE = np.dtype([("linear", np.float32, 3), ("angular", np.float32, 3), ("cl", np.float32), ("cq", np.float32)])
 
 # ray casts (datum_ocean_cast_rays, added at ABI 9): floats per ray (ox, oy, oz, tmin, dx, dy, dz, tmax) and per record (hi, lo, g(hi), status,
 # the query's record at hi), the ranges of steps and refine, and the status values
@@ -674,6 +694,29 @@ class Ocean:
         pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
         out = np.empty((b.shape[0], BODY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
+        return out
+
+    # -- body drag (datum_ocean_reduce_body_drag): per-body force and torque from the water's velocity relative to the hull ----------------
+
+    def reduce_body_drag(self, cascades, oceanset, bodies_ptr, motions_ptr, nbodies, probes_ptr, nprobes, records_ptr, iterations=4):
+        """Enqueue the reduction of `nbodies` bodies (device pointer, 64 bytes each) with their motions (device pointer, 32 bytes each) over
+        `nprobes` probes (device pointer, 16 bytes each) into `nbodies` records of 8 floats (device pointer): Fx, Fy, Fz, tau x, tau y,
+        tau z, sum m, max residual.  Needs velocity on and a displace since."""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_reduce_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
+                                                          P(motions_ptr) if motions_ptr else None, nbodies, P(probes_ptr) if probes_ptr else None, nprobes,
+                                                          P(records_ptr) if records_ptr else None))
+
+    def read_body_drag(self, cascades, oceanset, bodies, motions, probes, iterations=4):
+        """the same from host arrays, blocking: `bodies` an array of BODY_DTYPE, `motions` one of BODY_MOTION_DTYPE of the same length,
+        `probes` (n, 4) float32; returns (nbodies, 8)"""
+        arr, n = self._list(cascades)
+        b = np.ascontiguousarray(bodies)
+        mo = np.ascontiguousarray(motions)
+        assert b.dtype.itemsize == ctypes.sizeof(Body) and mo.dtype.itemsize == ctypes.sizeof(BodyMotion) and mo.shape[0] == b.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
+        out = np.empty((b.shape[0], DRAG_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), _ptr(mo), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

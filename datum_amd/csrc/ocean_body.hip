@@ -12,6 +12,8 @@
 //     32 and 16, DPP row shifts below -- every lane alive to the end; lane 0 stores the record, two 16-byte stores;
 //   * a bad probe fetches nothing; its body's record is eight quiet NaNs.
 // No LDS, no barrier, no atomics, no scratch (make resource-usage).
+// The walk (body_each_probe) takes the per-probe terms as a callable, as query_each_point does for points: body drag (ocean_drag.hip) is
+// the same walk with other terms.
 
 #pragma once
 
@@ -74,19 +76,26 @@ namespace ocean
     }
   };
 
-  template<int LAYOUT>
-  __global__ void __launch_bounds__(BODY_THREADS) ocean_body_kernel(BodyArgs a)
+  // The walk over a body's probes, stated once for the kernels that reduce per body (this file's, ocean_drag.hip's): wave `body` reads its
+  // body (wave-uniform index: scalar loads) and asks `begin(body, B, bad)` for the per-probe terms -- a callable (w, a) -> BodyPartial;
+  // begin may set `bad` for a reason of its own, and a bad body walks no probe.  Every lane walks the passes, loads its probe through a
+  // resource over that pass's probes, transforms it, and adds the terms of a probe that is its own and not bad; then the ballot, the
+  // tree and lane 0's store of the record or of eight NaNs
+  template<class Begin>
+  __device__ __forceinline__ void body_each_probe(datum_ocean_body const *bodies, BodyProbe const *probes, float4 *records, int nbodies, int nprobes, Begin &&begin)
   {
     int const lane = (int)threadIdx.x & (BODY_LANES - 1);
     int const body = __builtin_amdgcn_readfirstlane((int)blockIdx.x * BODY_WAVES + ((int)threadIdx.x >> 6));
 
     // (the whole wave: the last workgroup's waves without a body)
-    if (body >= a.nbodies)
+    if (body >= nbodies)
       return;
 
-    datum_ocean_body const B = a.bodies[body];
+    datum_ocean_body const B = bodies[body];
 
-    bool bad = body_range_bad(B, a.nprobes);
+    bool bad = body_range_bad(B, nprobes);
+
+    auto const terms = begin(body, B, bad);
 
     int const n = bad ? 0 : B.count;
 
@@ -101,7 +110,7 @@ namespace ocean
       // this pass's probes and nothing else: lanes beyond the body's last probe load zeros
       int const left = n - k * BODY_LANES;
 
-      __amdgpu_buffer_rsrc_t const rprobes = make_rsrc(a.probes + (size_t)body_lane_probe(B.first, 0, k), (size_t)(left < BODY_LANES ? left : BODY_LANES) * sizeof(BodyProbe));
+      __amdgpu_buffer_rsrc_t const rprobes = make_rsrc(probes + (size_t)body_lane_probe(B.first, 0, k), (size_t)(left < BODY_LANES ? left : BODY_LANES) * sizeof(BodyProbe));
 
       float4 const raw = buf_load_f32x4_aux<0>(rprobes, lane * (int)sizeof(BodyProbe), 0);
 
@@ -115,15 +124,7 @@ namespace ocean
       badprobe = badprobe || (have && probebad);
 
       if (have && !probebad)
-      {
-        float2 const q = make_float2(w.x, w.y);
-
-        QueryRecord const r = query_record<LAYOUT>(a.q, query_solve<LAYOUT>(a.q, q), q);
-
-        float const rec[DATUM_OCEAN_SURFACE_SAMPLE_FLOATS] = { r.v.x, r.v.y, r.v.z, r.v.w, r.m.x, r.m.y, r.m.z, r.m.w };
-
-        body_add(wave.p, body_terms(B, w, probe.a, rec));
-      }
+        body_add(wave.p, terms(w, probe.a));
     }
 
     bad = bad || __builtin_amdgcn_ballot_w64(badprobe) != 0;
@@ -136,11 +137,29 @@ namespace ocean
 
       float const *r = wave.p.f;
 
-      __amdgpu_buffer_rsrc_t const rrecord = make_rsrc(a.records + 2 * (size_t)body, 2 * sizeof(float4));
+      __amdgpu_buffer_rsrc_t const rrecord = make_rsrc(records + 2 * (size_t)body, 2 * sizeof(float4));
 
       buf_store_f32x4_aux<0>(bad ? make_float4(nan, nan, nan, nan) : make_float4(r[0], r[1], r[2], r[3]), rrecord, 0, 0);
       buf_store_f32x4_aux<0>(bad ? make_float4(nan, nan, nan, nan) : make_float4(r[4], r[5], r[6], r[7]), rrecord, 16, 0);
     }
+  }
+
+  template<int LAYOUT>
+  __global__ void __launch_bounds__(BODY_THREADS) ocean_body_kernel(BodyArgs a)
+  {
+    body_each_probe(a.bodies, a.probes, a.records, a.nbodies, a.nprobes, [&](int, datum_ocean_body const &B, bool &)
+    {
+      return [&a, &B](BodyWorld const &w, float weight)
+      {
+        float2 const q = make_float2(w.x, w.y);
+
+        QueryRecord const r = query_record<LAYOUT>(a.q, query_solve<LAYOUT>(a.q, q), q);
+
+        float const rec[DATUM_OCEAN_SURFACE_SAMPLE_FLOATS] = { r.v.x, r.v.y, r.v.z, r.v.w, r.m.x, r.m.y, r.m.z, r.m.w };
+
+        return body_terms(B, w, weight, rec);
+      };
+    });
   }
 
   inline void const *body_kernel_for(int N)

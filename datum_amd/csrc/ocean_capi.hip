@@ -28,6 +28,7 @@
 #include "ocean_ray.hip"
 #include "ocean_bounds.hip"
 #include "ocean_velocity.hip"
+#include "ocean_drag.hip"
 
 using namespace ocean;
 
@@ -68,7 +69,7 @@ struct Staging
 };
 
 // one per array a read_* query stages, kept apart per family: a family's growth frees nothing another family's launch may still read
-enum { STAGE_POINTS, STAGE_SAMPLES, STAGE_BODIES, STAGE_BODY_RECORDS, STAGE_PROBES, STAGE_RAYS, STAGE_RAY_RECORDS, STAGE_COUNT };
+enum { STAGE_POINTS, STAGE_SAMPLES, STAGE_BODIES, STAGE_BODY_RECORDS, STAGE_PROBES, STAGE_MOTIONS, STAGE_RAYS, STAGE_RAY_RECORDS, STAGE_COUNT };
 
 // the host's record of one cascade (what the kernels read of it is CascadeConst)
 struct CascadeState
@@ -2691,6 +2692,98 @@ int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, d
 
   return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
                      [&](void const *in, void *out) { return run_bodies(ctx, cascades, count, set, iterations, in, nbodies, dprobes.ptr, nprobes, out); });
+}
+
+}   // extern "C"
+
+/* -- body drag (ocean_drag.hip) --------------------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // the body calls' checks with the motions beside the bodies, then the state the velocity queries need; `name` goes into the error text
+  int check_body_drag_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
+                           size_t nbodies, void const *probes, size_t nprobes, void const *records, char const *name)
+  {
+    int rc = check_body_args(ctx, cascades, count, set, iterations, bodies, nbodies, probes, nprobes, records, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (nbodies > 0 && !motions)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null motions").c_str());
+
+    if ((uintptr_t)motions & 15)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": motions must be 16-byte aligned").c_str());
+
+    return check_velocity_state(ctx, name);
+  }
+
+  // device arrays, nbodies > 0
+  int run_body_drag(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
+                    size_t nbodies, void const *probes, size_t nprobes, void *records)
+  {
+    DragArgs a = {};
+    a.b.q = query_args(ctx, cascades, count, set, iterations);
+    a.b.bodies = static_cast<datum_ocean_body const*>(bodies);
+    a.b.probes = static_cast<BodyProbe const*>(probes);
+    a.b.records = static_cast<float4*>(records);
+    a.b.nbodies = (int)nbodies;
+    a.b.nprobes = (int)nprobes;
+    a.motions = static_cast<datum_ocean_body_motion const*>(motions);
+
+    for(int i = 0; i < count; ++i)
+      a.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+
+    HIPCHECK(ctx, launch_body_drag(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_reduce_body_drag(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                 void const *bodies_device, void const *motions_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                 void *records_device)
+{
+  int rc = check_body_drag_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, records_device, "datum_ocean_reduce_body_drag");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_body_drag(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, records_device);
+}
+
+int datum_ocean_read_body_drag(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                               datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
+                               float *records)
+{
+  int rc = check_body_drag_args(ctx, cascades, count, set, iterations, bodies, motions, nbodies, probes, nprobes, records, "datum_ocean_read_body_drag");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // the probes and the motions beside the bodies: the body calls' staging, and one for the motions, each grown on its own
+  Staging &dprobes = ctx->staging[STAGE_PROBES];
+  Staging &dmotions = ctx->staging[STAGE_MOTIONS];
+
+  rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
+  if (rc == DATUM_OCEAN_OK)
+    rc = dmotions.reserve(ctx, nbodies * sizeof(datum_ocean_body_motion));
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (nprobes > 0)
+    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
+
+  HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, nbodies * sizeof(datum_ocean_body_motion), hipMemcpyHostToDevice, ctx->stream));
+
+  return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
+                     [&](void const *in, void *out) { return run_body_drag(ctx, cascades, count, set, iterations, in, dmotions.ptr, nbodies, dprobes.ptr, nprobes, out); });
 }
 
 }   // extern "C"

@@ -369,6 +369,16 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_reduce_ocean_body_drag(void *c, void *p, void const *bodies, void const *motions, size_t nbodies, float const *probes, size_t nprobes, float *records, int iterations)
+  {
+    try
+    {
+      reduce_ocean_body_drag(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), static_cast<datum_ocean_body const*>(bodies), static_cast<datum_ocean_body_motion const*>(motions), nbodies, reinterpret_cast<OceanBodyProbe const*>(probes), nprobes, reinterpret_cast<OceanDragRecord*>(records), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_cast_ocean_rays(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
     try

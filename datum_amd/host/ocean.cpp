@@ -933,6 +933,20 @@ void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum
 }
 
 
+///////////////////////// reduce_ocean_body_drag ////////////////////////////
+void reduce_ocean_body_drag(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, OceanBodyProbe const *probes, size_t nprobes, OceanDragRecord *records, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("reduce_ocean_body_drag: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_body_drag(context.hip, &cascade, 1, &set, iterations, bodies, motions, nbodies, reinterpret_cast<float const*>(probes), nprobes, reinterpret_cast<float*>(records)), "datum_ocean_read_body_drag");
+}
+
+
 ///////////////////////// cast_ocean_rays ///////////////////////////////////
 void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
 {

@@ -397,6 +397,21 @@ static_assert(sizeof(OceanBodyRecord) == 32, "OceanBodyRecord must be the C ABI'
 
 void reduce_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, OceanBodyRecord *records, int iterations = 4);
 
+// body drag (include/datum_ocean_hip.h: datum_ocean_read_body_drag, the definition there): per body the force and the torque of the water's
+// motion relative to the hull, from the same bodies and probes as reduce_ocean_bodies and one datum_ocean_body_motion per body.  The same
+// one-cascade list and set.  Needs set_ocean_velocity(ON) and a displace since: throws otherwise, as query_ocean_velocity does
+struct OceanDragRecord
+{
+  lml::Vec3 force;                        // sum of k (water - hull), k = weight * submersion * (cl + cq |water - hull|)
+  lml::Vec3 torque;                       // about the body origin
+  float submerged;                        // sum weight * submersion: reduce_ocean_bodies' force, bit for bit
+  float residual;                         // the largest residual of the probes' velocity records
+};
+
+static_assert(sizeof(OceanDragRecord) == 32, "OceanDragRecord must be the C ABI's record of DATUM_OCEAN_DRAG_RECORD_FLOATS floats");
+
+void reduce_ocean_body_drag(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, OceanDragRecord *records, int iterations = 4);
+
 // ray casts (include/datum_ocean_hip.h: datum_ocean_read_rays, the definition there): per ray a fixed march of `steps` samples to the first
 // change of side, `refine` bisections of that bracket, and the surface sample at the bracket's far end.  One cascade, as
 // query_ocean_surface; the maps the context last displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before

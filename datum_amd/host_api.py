@@ -102,6 +102,7 @@ def load():
             "datum_host_read_ocean_velocity": (I, [P, P]),
             "datum_host_query_ocean_velocity": (I, [P, P, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
+            "datum_host_reduce_ocean_body_drag": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
             "datum_host_ocean_surface_slab": (I, [P, P, P]),
@@ -344,6 +345,18 @@ class OceanContext:
         pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
         out = np.empty((b.shape[0], capi.BODY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_reduce_ocean_bodies(self.c, params.p, b.ctypes.data_as(P), b.shape[0], pr.ctypes.data_as(P), pr.shape[0], out.ctypes.data_as(P), iterations))
+        return out
+
+    def reduce_ocean_body_drag(self, params, bodies, motions, probes, iterations=4):
+        """reduce_ocean_body_drag: `bodies` an array of capi.BODY_DTYPE, `motions` one of capi.BODY_MOTION_DTYPE of the same length, `probes`
+        (n, 4) float32; returns (nbodies, 8) float32 records (OceanDragRecord: force, torque, submerged, largest residual)"""
+        b = np.ascontiguousarray(bodies)
+        mo = np.ascontiguousarray(motions)
+        assert b.dtype.itemsize == ctypes.sizeof(capi.Body) and mo.dtype.itemsize == ctypes.sizeof(capi.BodyMotion) and mo.shape[0] == b.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
+        out = np.empty((b.shape[0], capi.DRAG_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_reduce_ocean_body_drag(self.c, params.p, b.ctypes.data_as(P), mo.ctypes.data_as(P), b.shape[0], pr.ctypes.data_as(P), pr.shape[0],
+                                                               out.ctypes.data_as(P), iterations))
         return out
 
     def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):

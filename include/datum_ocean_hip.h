@@ -52,7 +52,7 @@ extern "C" {
  *      surface bounds, datum_ocean_reduce_bounds, datum_ocean_bounds_device, datum_ocean_read_bounds and datum_ocean_surface_slab, with the
  *      bounded casts datum_ocean_cast_rays_bounded and datum_ocean_read_rays_bounded; then the surface velocity, datum_ocean_set_velocity,
  *      datum_ocean_bind_velocity, datum_ocean_velocity_device, datum_ocean_read_velocity, datum_ocean_sample_velocity_blend and
- *      datum_ocean_read_velocity_blend.
+ *      datum_ocean_read_velocity_blend; then body drag, datum_ocean_reduce_body_drag and datum_ocean_read_body_drag.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -600,6 +600,8 @@ int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
  *                             7    0
  *                           A non-finite q gives a record of quiet NaNs and fetches nothing
  *   read_velocity_blend     the same from HOST arrays, blocking, through the staging buffers datum_ocean_read_surface uses
+ * Inside the module the plane has one consumer so far: body drag (datum_ocean_reduce_body_drag, below) turns these records into a force
+ * and a torque per body on the device.
  * DATUM_OCEAN_ESTATE from read_velocity and the two queries while velocity is OFF, and while no datum_ocean_displace has run since velocity
  * was switched on (the plane holds nothing yet); otherwise the foam calls' and the several-cascade query's errors. */
 #define DATUM_OCEAN_VELOCITY_OFF 0
@@ -613,6 +615,65 @@ int datum_ocean_sample_velocity_blend(datum_ocean_t ctx, int const *cascades, in
                                       void const *points_device, size_t n, void *out_device);
 int datum_ocean_read_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                     float const *points, size_t n, float *out);
+
+/* -- body drag (added at ABI 9; nothing in the reference) ------------------------------------------------------------------------------
+ * The other half of body buoyancy: per body the force and the torque about the body origin that the water's motion relative to the hull
+ * exerts, reduced on the device from the same hull probes.  Buoyancy alone makes a body bob for ever; with this it settles, and the waves
+ * push it along.  (With the velocity query alone a caller transforms every probe, uploads 8 bytes and reads back 32 bytes per probe, and
+ * forms and sums k · (water − hull) on the host; here 32 bytes per BODY come back.)
+ *
+ * A call takes datum_ocean_reduce_bodies' arguments -- list, set, iterations, bodies, probes; their rules and layouts are those of "body
+ * buoyancy" above -- and one more DEVICE array, motions, one datum_ocean_body_motion per body, 32 bytes, below: the velocity v = linear
+ * of the body origin and the angular velocity ω = angular, both in world space, and two drag coefficients cl, cq.
+ *
+ * For probe i of body B, with R = rotation, T = position, every line one fp32 operation per operator as written (no contraction):
+ *
+ *     w   = body buoyancy's w (R, T and the probe's x, y, z), bit for bit
+ *     rec = the record of datum_ocean_sample_velocity_blend for q = (w.x, w.y) with this list, set and iterations, bit for bit
+ *     d   = min(max(rec[2] − w.z, 0), cap)         m = a · d                 body buoyancy's d and m
+ *     r   = (w.x − T.x, w.y − T.y, w.z − T.z)                                lever arm about the body origin
+ *     u.x = v.x + (ω.y·r.z − ω.z·r.y)   u.y = v.y + (ω.z·r.x − ω.x·r.z)   u.z = v.z + (ω.x·r.y − ω.y·r.x)      the hull's velocity at the probe
+ *     e   = (rec[4] − u.x, rec[5] − u.y, rec[6] − u.z)                       the water relative to the hull
+ *     s   = sqrt((e.x·e.x + e.y·e.y) + e.z·e.z)                              correctly rounded (IEEE)
+ *     k   = m · (cl + cq · s)
+ *     f   = (k·e.x, k·e.y, k·e.z)
+ *     τx  = r.y·f.z − r.z·f.y     τy = r.z·f.x − r.x·f.z     τz = r.x·f.y − r.y·f.x
+ *
+ * Each body gets a record of DATUM_OCEAN_DRAG_RECORD_FLOATS = 8 floats (32 bytes):
+ *     Fx, Fy, Fz, τx, τy, τz, Σ m, max residual
+ * summed in body buoyancy's order by the same functions: lane l adds the terms of probes first + l, first + l + 64, … to partials started
+ * at +0.0f, then the tree s = 32 … 1; field 7 is the maximum (fmaxf) of rec[3].  field 6 is datum_ocean_reduce_bodies' field 0 for the
+ * same arguments, bit for bit: fold ρ (and the drag's own constants) into a or into cl, cq exactly as ρ·g for buoyancy -- the result is
+ * linear in a, cl and cq together -- and check the wiring of a new caller with that field.  The weight of a probe is m, its submerged
+ * volume, not a wet / dry switch: the force is continuous where a probe crosses the water line and grows with the draught, as the
+ * buoyancy does.  count == 0 gives eight zeros.  A body's record is eight quiet NaNs, and nothing is fetched for its bad probes, where
+ * datum_ocean_reduce_bodies says so (range, cap, a non-finite w or a) and where any of the motion's eight floats is not finite.  Huge
+ * finite inputs follow the arithmetic as written: an s that overflows gives what fp32 gives.
+ * THE SWELL IS NOT INCLUDED ("surface velocity" above: the velocity plane does not hold the swell's motion, so neither does e); a caller
+ * who moves the swell adds its orbital velocity to `linear` with the opposite sign, or accepts the difference.
+ *
+ *   reduce_body_drag   enqueue and return: one kernel on the handle's stream behind the last displace; it applies no pending update and
+ *                      reads maps and velocity planes as they lie (own or bound).  motions_device: nbodies × 32 bytes, a DEVICE pointer,
+ *                      16-byte aligned; the other arrays as for reduce_bodies; records_device: nbodies × 32 bytes
+ *   read_body_drag     the same from HOST arrays, blocking, through device staging buffers (those of read_bodies and one for the motions,
+ *                      grown on demand, freed by datum_ocean_destroy), all on the handle's stream
+ * DATUM_OCEAN_ESTATE exactly where datum_ocean_sample_velocity_blend returns it: while velocity is OFF, and while no datum_ocean_displace
+ * has run since velocity was switched on or a plane was bound.  DATUM_OCEAN_EINVAL for everything datum_ocean_reduce_bodies refuses, and
+ * for a null or misaligned motions array with nbodies > 0.  nbodies == 0 enqueues nothing.  A call writes only the records. */
+#define DATUM_OCEAN_DRAG_RECORD_FLOATS 8
+typedef struct datum_ocean_body_motion
+{
+  float linear[3];         /*   0  velocity of the body origin, world space, m/s */
+  float angular[3];        /*  12  angular velocity, world space, rad/s          */
+  float cl;                /*  24  linear drag coefficient                       */
+  float cq;                /*  28  quadratic drag coefficient                    */
+} datum_ocean_body_motion;
+int datum_ocean_reduce_body_drag(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                 void const *bodies_device, void const *motions_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                 void *records_device);
+int datum_ocean_read_body_drag(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                               datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
+                               float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -1228,6 +1228,13 @@ int datum_ocean_rebuild_height(datum_ocean_t ctx, int cascade, float wavescale, 
   if (!(wavescale > 0))
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_rebuild_height: wavescale must be positive");
 
+  // refused before anything is installed: such arguments make every h0 a NaN (include/datum_ocean_hip.h)
+  if (!(waveamplitude >= 0) || !std::isfinite(waveamplitude))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_rebuild_height: waveamplitude must be finite and not negative");
+
+  if (!std::isfinite(windspeed) || !std::isfinite(windx) || !std::isfinite(windy))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_rebuild_height: windspeed and the wind direction must be finite");
+
   // queued updates belong to the old wave scale
   int rc = datum_ocean_set_cascade(ctx, cascade, wavescale, ctx->casc[cascade].choppiness);
   if (rc != DATUM_OCEAN_OK)

@@ -218,7 +218,13 @@ int datum_ocean_resume_state(datum_ocean_t ctx, int cascade, void const *device_
  * keep OceanParams::seed (N*N*2 floats, ocean.cpp:140-141) resident and recompute
  * h0 = seed * dk * sqrt(phillips(k, waveamplitude, windspeed, winddirection) / 2), dk = 2 pi / wavescale,
  * on the device when the wind changes, instead of an O(N^2) host loop plus an 8*N*N-byte upload.
- * rebuild_height also installs `wavescale` as the cascade's wave scale (choppiness is kept). */
+ * rebuild_height also installs `wavescale` as the cascade's wave scale (choppiness is kept).
+ * Arguments: a cascade out of range, a wavescale that is not positive, a waveamplitude that is negative or not finite, and a windspeed,
+ * windx or windy that is not finite are DATUM_OCEAN_EINVAL (the error text names datum_ocean_rebuild_height); no seed on the device is
+ * DATUM_OCEAN_ESTATE.  Every check comes before anything is installed: after a refused call the wave scale, h0, the phase and the launch
+ * plan are as if it had not been made.  windspeed = 0 and waveamplitude = 0 are valid and give h0 = 0.  A seed never uploaded for this
+ * cascade (while another's was) is zero.  What the kernel may compute at each point is stated by tests/h064.py (an interval walk of the
+ * expression) and held to it by tests/test_gpu_h0.py. */
 int datum_ocean_upload_seed(datum_ocean_t ctx, int cascade, float const *seed);
 int datum_ocean_rebuild_height(datum_ocean_t ctx, int cascade, float wavescale, float waveamplitude, float windspeed, float windx, float windy);
 int datum_ocean_read_height(datum_ocean_t ctx, int cascade, float *h0);

@@ -145,6 +145,8 @@ SYMBOLS = {
     "datum_ocean_read_velocity_blend": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_reduce_body_drag": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
     "datum_ocean_read_body_drag": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
+    "datum_ocean_step_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
+    "datum_ocean_step_bodies_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
 }
 
 
@@ -208,6 +210,26 @@ class BodyMotion(ctypes.Structure):
 
 # the same layout for numpy: an array of this dtype is an array of BodyMotion
 BODY_MOTION_DTYPE = np.dtype([("linear", np.float32, 3), ("angular", np.float32, 3), ("cl", np.float32), ("cq", np.float32)])
+
+# body stepping (datum_ocean_step_bodies, added at ABI 9): floats per body record and the largest number of sub-steps of a call
+STEP_RECORD_FLOATS = 8
+STEP_MAX_SUBSTEPS = 16
+
+
+class BodyProps(ctypes.Structure):
+    """datum_ocean_body_props of include/datum_ocean_hip.h: 32 bytes"""
+
+    _fields_ = [
+        ("invmass", F),
+        ("invinertia", F * 3),
+        ("gravity", F),
+        ("buoyancy", F),
+        ("pad", F * 2),
+    ]
+
+
+# the same layout for numpy: an array of this dtype is an array of BodyProps
+BODY_PROPS_DTYPE = np.dtype([("invmass", np.float32), ("invinertia", np.float32, 3), ("gravity", np.float32), ("buoyancy", np.float32), ("pad", np.float32, 2)])
 
 # ray casts (datum_ocean_cast_rays, added at ABI 9): floats per ray (ox, oy, oz, tmin, dx, dy, dz, tmax) and per record (hi, lo, g(hi), status,
 # the query's record at hi), the ranges of steps and refine, and the status values
@@ -717,6 +739,32 @@ class Ocean:
         pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
         out = np.empty((b.shape[0], DRAG_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), _ptr(mo), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
+        return out
+
+    # -- body stepping (datum_ocean_step_bodies): buoyancy, drag and a semi-implicit Euler integrator per body, on the device -------------
+
+    def step_bodies(self, cascades, oceanset, bodies_ptr, motions_ptr, props_ptr, nbodies, probes_ptr, nprobes, dt, substeps, records_ptr, iterations=4):
+        """Enqueue `substeps` sub-steps of dt / substeps for `nbodies` bodies (device pointers: 64 bytes each, read and written), their motions
+        (32 bytes each, read and written) and props (32 bytes each) over `nprobes` probes (16 bytes each) into `nbodies` records of 8 floats:
+        Fx, Fy, Fz, tau x, tau y, tau z, sum m of the last sub-step, max residual.  Needs velocity on and a displace since."""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_step_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
+                                                     P(motions_ptr) if motions_ptr else None, P(props_ptr) if props_ptr else None, nbodies,
+                                                     P(probes_ptr) if probes_ptr else None, nprobes, dt, substeps, P(records_ptr) if records_ptr else None))
+
+    def step_bodies_host(self, cascades, oceanset, bodies, motions, props, probes, dt, substeps=1, iterations=4):
+        """the same from host arrays, blocking: `bodies` an array of BODY_DTYPE and `motions` one of BODY_MOTION_DTYPE, both contiguous and
+        advanced IN PLACE, `props` one of BODY_PROPS_DTYPE of the same length, `probes` (n, 4) float32; returns the (nbodies, 8) records"""
+        arr, n = self._list(cascades)
+        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
+        assert bodies.flags.writeable and motions.flags.writeable
+        pp = np.ascontiguousarray(props)
+        assert bodies.dtype.itemsize == ctypes.sizeof(Body) and motions.dtype.itemsize == ctypes.sizeof(BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(BodyProps)
+        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
+        out = np.empty((bodies.shape[0], STEP_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_step_bodies_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(bodies), _ptr(motions), _ptr(pp), bodies.shape[0],
+                                                          _ptr(pr), pr.shape[0], dt, substeps, _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

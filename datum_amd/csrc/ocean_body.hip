@@ -76,32 +76,13 @@ namespace ocean
     }
   };
 
-  // The walk over a body's probes, stated once for the kernels that reduce per body (this file's, ocean_drag.hip's): wave `body` reads its
-  // body (wave-uniform index: scalar loads) and asks `begin(body, B, bad)` for the per-probe terms -- a callable (w, a) -> BodyPartial;
-  // begin may set `bad` for a reason of its own, and a bad body walks no probe.  Every lane walks the passes, loads its probe through a
-  // resource over that pass's probes, transforms it, and adds the terms of a probe that is its own and not bad; then the ballot, the
-  // tree and lane 0's store of the record or of eight NaNs
-  template<class Begin>
-  __device__ __forceinline__ void body_each_probe(datum_ocean_body const *bodies, BodyProbe const *probes, float4 *records, int nbodies, int nprobes, Begin &&begin)
+  // The passes over the first n probes of body B's range (n = 0: none), stated once for every kernel that sums per body: every lane walks
+  // the passes, loads its probe through a resource over that pass's probes, transforms it, and adds to its partial p the terms -- a
+  // callable (w, a) -> Partial, added with body_add -- of a probe that is its own and not bad.  True in a lane that met a bad probe.
+  // (ocean_step.hip loops over this, one walk per sub-step, with a pose that moves)
+  template<class Partial, class Terms>
+  __device__ __forceinline__ bool body_walk(datum_ocean_body const &B, BodyProbe const *probes, int n, int lane, Partial &p, Terms &&terms)
   {
-    int const lane = (int)threadIdx.x & (BODY_LANES - 1);
-    int const body = __builtin_amdgcn_readfirstlane((int)blockIdx.x * BODY_WAVES + ((int)threadIdx.x >> 6));
-
-    // (the whole wave: the last workgroup's waves without a body)
-    if (body >= nbodies)
-      return;
-
-    datum_ocean_body const B = bodies[body];
-
-    bool bad = body_range_bad(B, nprobes);
-
-    auto const terms = begin(body, B, bad);
-
-    int const n = bad ? 0 : B.count;
-
-    BodyWave wave;
-    wave.p = body_zero();
-
     bool badprobe = false;
 
     // lane 0 has the most probes: every lane walks its passes (wave-uniform), `have` says whether a pass holds a probe for this lane
@@ -124,8 +105,38 @@ namespace ocean
       badprobe = badprobe || (have && probebad);
 
       if (have && !probebad)
-        body_add(wave.p, terms(w, probe.a));
+        body_add(p, terms(w, probe.a));
     }
+
+    return badprobe;
+  }
+
+  // The walk over a body's probes, stated once for the kernels that reduce per body (this file's, ocean_drag.hip's): wave `body` reads its
+  // body (wave-uniform index: scalar loads) and asks `begin(body, B, bad)` for the per-probe terms -- a callable (w, a) -> BodyPartial;
+  // begin may set `bad` for a reason of its own, and a bad body walks no probe.  Then the passes (body_walk), the ballot, the tree and
+  // lane 0's store of the record or of eight NaNs
+  template<class Begin>
+  __device__ __forceinline__ void body_each_probe(datum_ocean_body const *bodies, BodyProbe const *probes, float4 *records, int nbodies, int nprobes, Begin &&begin)
+  {
+    int const lane = (int)threadIdx.x & (BODY_LANES - 1);
+    int const body = __builtin_amdgcn_readfirstlane((int)blockIdx.x * BODY_WAVES + ((int)threadIdx.x >> 6));
+
+    // (the whole wave: the last workgroup's waves without a body)
+    if (body >= nbodies)
+      return;
+
+    datum_ocean_body const B = bodies[body];
+
+    bool bad = body_range_bad(B, nprobes);
+
+    auto const terms = begin(body, B, bad);
+
+    int const n = bad ? 0 : B.count;
+
+    BodyWave wave;
+    wave.p = body_zero();
+
+    bool const badprobe = body_walk(B, probes, n, lane, wave.p, terms);
 
     bad = bad || __builtin_amdgcn_ballot_w64(badprobe) != 0;
 

@@ -29,6 +29,7 @@
 #include "ocean_bounds.hip"
 #include "ocean_velocity.hip"
 #include "ocean_drag.hip"
+#include "ocean_step.hip"
 
 using namespace ocean;
 
@@ -69,7 +70,7 @@ struct Staging
 };
 
 // one per array a read_* query stages, kept apart per family: a family's growth frees nothing another family's launch may still read
-enum { STAGE_POINTS, STAGE_SAMPLES, STAGE_BODIES, STAGE_BODY_RECORDS, STAGE_PROBES, STAGE_MOTIONS, STAGE_RAYS, STAGE_RAY_RECORDS, STAGE_COUNT };
+enum { STAGE_POINTS, STAGE_SAMPLES, STAGE_BODIES, STAGE_BODY_RECORDS, STAGE_PROBES, STAGE_MOTIONS, STAGE_PROPS, STAGE_RAYS, STAGE_RAY_RECORDS, STAGE_COUNT };
 
 // the host's record of one cascade (what the kernels read of it is CascadeConst)
 struct CascadeState
@@ -2791,6 +2792,131 @@ int datum_ocean_read_body_drag(datum_ocean_t ctx, int const *cascades, int count
 
   return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
                      [&](void const *in, void *out) { return run_body_drag(ctx, cascades, count, set, iterations, in, dmotions.ptr, nbodies, dprobes.ptr, nprobes, out); });
+}
+
+}   // extern "C"
+
+/* -- body stepping (ocean_step.hip) ----------------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // body drag's checks with the props beside the motions, then the step's own two numbers; `name` goes into the error text
+  int check_step_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
+                      void const *props, size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void const *records, char const *name)
+  {
+    // (the state last: ESTATE exactly where body drag returns it, EINVAL first as there)
+    int rc = check_body_args(ctx, cascades, count, set, iterations, bodies, nbodies, probes, nprobes, records, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (nbodies > 0 && (!motions || !props))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null motions or props").c_str());
+
+    if (((uintptr_t)motions & 15) || ((uintptr_t)props & 15))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": motions and props must be 16-byte aligned").c_str());
+
+    if (substeps < 1 || substeps > DATUM_OCEAN_STEP_MAX_SUBSTEPS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": substeps outside [1, DATUM_OCEAN_STEP_MAX_SUBSTEPS]").c_str());
+
+    if (!std::isfinite(dt))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt is not finite").c_str());
+
+    return check_velocity_state(ctx, name);
+  }
+
+  // device arrays, nbodies > 0
+  int run_step_bodies(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void *bodies, void *motions, void const *props,
+                      size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void *records)
+  {
+    BodyStepArgs a = {};
+    a.d.b.q = query_args(ctx, cascades, count, set, iterations);
+    a.d.b.bodies = a.bodies = static_cast<datum_ocean_body*>(bodies);
+    a.d.b.probes = static_cast<BodyProbe const*>(probes);
+    a.d.b.records = static_cast<float4*>(records);
+    a.d.b.nbodies = (int)nbodies;
+    a.d.b.nprobes = (int)nprobes;
+    a.d.motions = a.motions = static_cast<datum_ocean_body_motion*>(motions);
+    a.props = static_cast<datum_ocean_body_props const*>(props);
+
+    for(int i = 0; i < count; ++i)
+      a.d.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+
+    // the sub-step's length, rounded once here (two fp32 operations: the reciprocal, the product), as the ray cast's inv
+    float const inv = 1.0f / (float)substeps;
+
+    a.h = dt * inv;
+    a.substeps = substeps;
+
+    HIPCHECK(ctx, launch_step_bodies(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_step_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                            void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                            float dt, int substeps, void *records_device)
+{
+  int rc = check_step_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device, "datum_ocean_step_bodies");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_step_bodies(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device);
+}
+
+int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                 datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
+                                 float const *probes, size_t nprobes, float dt, int substeps, float *records)
+{
+  int rc = check_step_args(ctx, cascades, count, set, iterations, bodies, motions, props, nbodies, probes, nprobes, dt, substeps, records, "datum_ocean_step_bodies_host");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // read_body_drag's staging and one more for the props, each grown on its own; bodies and motions come back beside the records
+  Staging &dbodies = ctx->staging[STAGE_BODIES], &dmotions = ctx->staging[STAGE_MOTIONS], &dprops = ctx->staging[STAGE_PROPS];
+  Staging &dprobes = ctx->staging[STAGE_PROBES], &drecords = ctx->staging[STAGE_BODY_RECORDS];
+
+  size_t const bodybytes = nbodies * sizeof(datum_ocean_body), motionbytes = nbodies * sizeof(datum_ocean_body_motion);
+  size_t const recordbytes = nbodies * DATUM_OCEAN_STEP_RECORD_FLOATS * sizeof(float);
+
+  rc = dbodies.reserve(ctx, bodybytes);
+  if (rc == DATUM_OCEAN_OK)
+    rc = dmotions.reserve(ctx, motionbytes);
+  if (rc == DATUM_OCEAN_OK)
+    rc = dprops.reserve(ctx, nbodies * sizeof(datum_ocean_body_props));
+  if (rc == DATUM_OCEAN_OK)
+    rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
+  if (rc == DATUM_OCEAN_OK)
+    rc = drecords.reserve(ctx, recordbytes);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipMemcpyAsync(dbodies.ptr, bodies, bodybytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, motionbytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(dprops.ptr, props, nbodies * sizeof(datum_ocean_body_props), hipMemcpyHostToDevice, ctx->stream));
+
+  if (nprobes > 0)
+    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
+
+  rc = run_step_bodies(ctx, cascades, count, set, iterations, dbodies.ptr, dmotions.ptr, dprops.ptr, nbodies, dprobes.ptr, nprobes, dt, substeps, drecords.ptr);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipMemcpyAsync(bodies, dbodies.ptr, bodybytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(motions, dmotions.ptr, motionbytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipMemcpyAsync(records, drecords.ptr, recordbytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
 }
 
 }   // extern "C"

@@ -412,6 +412,21 @@ static_assert(sizeof(OceanDragRecord) == 32, "OceanDragRecord must be the C ABI'
 
 void reduce_ocean_body_drag(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, OceanDragRecord *records, int iterations = 4);
 
+// body stepping (include/datum_ocean_hip.h: datum_ocean_step_bodies_host, the definition there): advances every body's pose and motion IN
+// PLACE by dt, in `substeps` sub-steps against the surface as it lies -- buoyancy, drag and a semi-implicit Euler integrator on the device --
+// with one datum_ocean_body_props per body.  The same one-cascade list, set and state as reduce_ocean_body_drag; throws where it does
+struct OceanStepRecord
+{
+  lml::Vec3 force;                        // of the last sub-step: buoyancy * submerged (vertical) and the drag
+  lml::Vec3 torque;                       // about the body origin
+  float submerged;                        // sum weight * submersion of the last sub-step
+  float residual;                         // the largest residual of the probes' records over all sub-steps
+};
+
+static_assert(sizeof(OceanStepRecord) == 32, "OceanStepRecord must be the C ABI's record of DATUM_OCEAN_STEP_RECORD_FLOATS floats");
+
+void step_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, float dt, int substeps, OceanStepRecord *records, int iterations = 4);
+
 // ray casts (include/datum_ocean_hip.h: datum_ocean_read_rays, the definition there): per ray a fixed march of `steps` samples to the first
 // change of side, `refine` bisections of that bracket, and the surface sample at the bracket's far end.  One cascade, as
 // query_ocean_surface; the maps the context last displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before

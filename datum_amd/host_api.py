@@ -103,6 +103,7 @@ def load():
             "datum_host_query_ocean_velocity": (I, [P, P, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_body_drag": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
+            "datum_host_step_ocean_bodies": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
             "datum_host_ocean_surface_slab": (I, [P, P, P]),
@@ -357,6 +358,21 @@ class OceanContext:
         out = np.empty((b.shape[0], capi.DRAG_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_reduce_ocean_body_drag(self.c, params.p, b.ctypes.data_as(P), mo.ctypes.data_as(P), b.shape[0], pr.ctypes.data_as(P), pr.shape[0],
                                                                out.ctypes.data_as(P), iterations))
+        return out
+
+    def step_ocean_bodies(self, params, bodies, motions, props, probes, dt, substeps=1, iterations=4):
+        """step_ocean_bodies: `bodies` (capi.BODY_DTYPE) and `motions` (capi.BODY_MOTION_DTYPE), contiguous, are advanced IN PLACE by dt in
+        `substeps` sub-steps; `props` an array of capi.BODY_PROPS_DTYPE of the same length, `probes` (n, 4) float32; returns (nbodies, 8)
+        float32 records (OceanStepRecord: force, torque, submerged of the last sub-step, largest residual)"""
+        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
+        assert bodies.flags.writeable and motions.flags.writeable
+        pp = np.ascontiguousarray(props)
+        assert bodies.dtype.itemsize == ctypes.sizeof(capi.Body) and motions.dtype.itemsize == ctypes.sizeof(capi.BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(capi.BodyProps)
+        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
+        out = np.empty((bodies.shape[0], capi.STEP_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_step_ocean_bodies(self.c, params.p, bodies.ctypes.data_as(P), motions.ctypes.data_as(P), pp.ctypes.data_as(P), bodies.shape[0],
+                                                          pr.ctypes.data_as(P), pr.shape[0], dt, substeps, out.ctypes.data_as(P), iterations))
         return out
 
     def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):

@@ -52,7 +52,8 @@ extern "C" {
  *      surface bounds, datum_ocean_reduce_bounds, datum_ocean_bounds_device, datum_ocean_read_bounds and datum_ocean_surface_slab, with the
  *      bounded casts datum_ocean_cast_rays_bounded and datum_ocean_read_rays_bounded; then the surface velocity, datum_ocean_set_velocity,
  *      datum_ocean_bind_velocity, datum_ocean_velocity_device, datum_ocean_read_velocity, datum_ocean_sample_velocity_blend and
- *      datum_ocean_read_velocity_blend; then body drag, datum_ocean_reduce_body_drag and datum_ocean_read_body_drag.
+ *      datum_ocean_read_velocity_blend; then body drag, datum_ocean_reduce_body_drag and datum_ocean_read_body_drag; then body stepping,
+ *      datum_ocean_step_bodies and datum_ocean_step_bodies_host.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -606,8 +607,8 @@ int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
  *                             7    0
  *                           A non-finite q gives a record of quiet NaNs and fetches nothing
  *   read_velocity_blend     the same from HOST arrays, blocking, through the staging buffers datum_ocean_read_surface uses
- * Inside the module the plane has one consumer so far: body drag (datum_ocean_reduce_body_drag, below) turns these records into a force
- * and a torque per body on the device.
+ * Inside the module the plane has two consumers: body drag (datum_ocean_reduce_body_drag, below) turns these records into a force and a
+ * torque per body on the device, and body stepping (datum_ocean_step_bodies, below it) moves the bodies with them.
  * DATUM_OCEAN_ESTATE from read_velocity and the two queries while velocity is OFF, and while no datum_ocean_displace has run since velocity
  * was switched on (the plane holds nothing yet); otherwise the foam calls' and the several-cascade query's errors. */
 #define DATUM_OCEAN_VELOCITY_OFF 0
@@ -680,6 +681,83 @@ int datum_ocean_reduce_body_drag(datum_ocean_t ctx, int const *cascades, int cou
 int datum_ocean_read_body_drag(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
                                float *records);
+
+/* -- body stepping (added at ABI 9; nothing in the reference) --------------------------------------------------------------------------
+ * What body buoyancy and body drag are for: one call advances every body's pose and motion by dt on the device, in `substeps` sub-steps
+ * against the surface as it lies (a stiff buoyancy spring needs sub-steps; the water does not move between them).  Without it a caller
+ * launches datum_ocean_reduce_bodies and datum_ocean_reduce_body_drag -- which solve the same query for every probe twice -- reads 2 × 32
+ * bytes per body back, integrates on the host and uploads 64 + 32 bytes per body, per sub-step.  Here pose and motion stay in registers
+ * from sub-step to sub-step, a sub-step makes one query per probe, and memory is written once at the end.
+ *
+ * A call takes datum_ocean_reduce_body_drag's arguments -- list, set, iterations, bodies, motions, probes; their rules and layouts are those
+ * of "body buoyancy" and "body drag" above; bodies and motions are read AND written -- one more DEVICE array, props, one
+ * datum_ocean_body_props per body, 32 bytes, below, and dt and substeps.  The body origin is the centre of mass: torques are about it, as in
+ * both calls above.
+ *
+ *     inv = 1.0f / (float)substeps        h = dt · inv        both rounded once, on the host; every sub-step has the length h
+ *
+ * One sub-step, with R, T the body's pose, v, ω, cl, cq its motion; every operator one fp32 operation as written (no contraction), division
+ * and sqrt the correctly rounded ones (IEEE):
+ *
+ *   1 the probe walk is body buoyancy's: the same lanes, probe order, partials started at +0.0f and tree s = 32 … 1.  Per probe ONE record
+ *     rec of datum_ocean_sample_velocity_blend (its fields 0-3 are the surface record's, bit for bit); from it body buoyancy's terms 0-2 and
+ *     body drag's terms 0-5 and 7: ten sums
+ *         M = Σ m     bx = Σ r.y·m     by = Σ −(r.x·m)     D = (Fx, Fy, Fz, τx, τy, τz) of the drag     res = max rec[3]
+ *     each of them, bit for bit, the field of datum_ocean_reduce_bodies (0-2) or datum_ocean_reduce_body_drag (0-5, 7) for the same pose,
+ *     motion and arguments (the drag's field 6 is M)
+ *   2 totals     F = (D.Fx, D.Fy, buoyancy·M + D.Fz)          τ = (buoyancy·bx + D.τx, buoyancy·by + D.τy, D.τz)
+ *   3 linear     v'.x = v.x + h·(F.x·invmass)     v'.y likewise     v'.z = v.z + h·(F.z·invmass − gravity)
+ *                T' = T + h·v'  per component                 semi-implicit Euler: the pose moves with the NEW velocity
+ *   4 angular    τb_j = (R[j]·τ.x + R[3+j]·τ.y) + R[6+j]·τ.z          the torque in the body frame, j = 0, 1, 2
+ *                αb_j = τb_j · invinertia[j]
+ *                α.x = (R[0]·αb_0 + R[1]·αb_1) + R[2]·αb_2          α.y, α.z with rows 1, 2 (body buoyancy's w without T)
+ *                ω' = ω + h·α  per component
+ *                THE GYROSCOPIC TERM ω × Iω IS LEFT OUT: exact for a body whose three moments are equal, and for any body turning about
+ *                one principal axis; a small error at the spin rates floating bodies reach
+ *   5 rotation   c_j = (R[j], R[3+j], R[6+j]) the columns of R;  for j = 0, 1:
+ *                c_j'.x = c_j.x + h·(ω'.y·c_j.z − ω'.z·c_j.y)   c_j'.y = c_j.y + h·(ω'.z·c_j.x − ω'.x·c_j.z)   c_j'.z = c_j.z + h·(ω'.x·c_j.y − ω'.y·c_j.x)
+ *                |a| = sqrt((a.x·a.x + a.y·a.y) + a.z·a.z)
+ *                x = c_0' / |c_0'|  per component
+ *                y0 = c_1' − (x·c_1')·x  per component, x·c = (x.x·c.x + x.y·c.y) + x.z·c.z
+ *                y = y0 / |y0|
+ *                z = x × y:  z.x = x.y·y.z − x.z·y.y    z.y = x.z·y.x − x.x·y.z    z.z = x.x·y.y − x.y·y.x
+ *                R' has the columns x, y, z
+ *
+ * Each body gets a record of DATUM_OCEAN_STEP_RECORD_FLOATS = 8 floats (32 bytes):
+ *     F.x, F.y, F.z, τ.x, τ.y, τ.z, M -- of the LAST sub-step -- and the largest res over all sub-steps
+ * A body is bad if datum_ocean_reduce_body_drag would call it bad for the pose and motion of any sub-step (range, cap, a non-finite w or a,
+ * the motion), if one of the props' six fields is not finite, or if any float of the integrated pose or motion of any sub-step is not
+ * finite (a column that the rotation step shrinks to length zero ends there).  A bad body's pose and motion in memory are left exactly as
+ * they were, its record is eight quiet NaNs, and it walks no further sub-step.  Bodies and motions are written only after the last sub-step.
+ * No index can fault, by body buoyancy's means; probe ranges may be shared between bodies, body and motion slots are a body's own.
+ * Huge finite inputs and a negative dt follow the arithmetic as written.
+ * THE SWELL IS NOT INCLUDED, as in body drag.  Added mass, wave radiation and collisions between bodies are not modelled.
+ *
+ *   step_bodies        enqueue and return: one kernel on the handle's stream behind the last displace; it applies no pending update and
+ *                      reads maps and velocity planes as they lie (own or bound).  bodies_device: nbodies × 64 bytes, motions_device and
+ *                      props_device: nbodies × 32 bytes, records_device: nbodies × 32 bytes; DEVICE pointers, 16-byte aligned.  It writes
+ *                      only bodies (their rotation and position), motions and records
+ *   step_bodies_host   the same from HOST arrays, blocking, through device staging buffers (those of read_body_drag and one for the
+ *                      props, grown on demand, freed by datum_ocean_destroy), all on the handle's stream; bodies and motions are copied back
+ * DATUM_OCEAN_ESTATE exactly where datum_ocean_reduce_body_drag returns it.  DATUM_OCEAN_EINVAL for everything that call refuses, for a
+ * null or misaligned props array with nbodies > 0, for substeps outside [1, DATUM_OCEAN_STEP_MAX_SUBSTEPS] and for a non-finite dt.
+ * nbodies == 0 enqueues nothing. */
+#define DATUM_OCEAN_STEP_RECORD_FLOATS 8
+#define DATUM_OCEAN_STEP_MAX_SUBSTEPS 16
+typedef struct datum_ocean_body_props
+{
+  float invmass;           /*   0  1 / mass; 0: the body is not accelerated linearly                   */
+  float invinertia[3];     /*   4  1 / principal moments, BODY frame (diagonal); 0: no spin-up         */
+  float gravity;           /*  16  m/s², subtracted from the vertical acceleration as written          */
+  float buoyancy;          /*  20  ρ·g: multiplies the Archimedes sums (the drag's ρ goes into cl, cq) */
+  float pad[2];            /*  24                                                                      */
+} datum_ocean_body_props;
+int datum_ocean_step_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                            void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                            float dt, int substeps, void *records_device);
+int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                 datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
+                                 float const *probes, size_t nprobes, float dt, int substeps, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -147,6 +147,19 @@ SYMBOLS = {
     "datum_ocean_read_body_drag": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
     "datum_ocean_step_bodies": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
     "datum_ocean_step_bodies_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
+    "datum_ocean_set_ripples": (I, [P, I, F]),
+    "datum_ocean_set_ripple_params": (I, [P, F, F, I, F]),
+    "datum_ocean_center_ripples": (I, [P, F, F]),
+    "datum_ocean_reset_ripples": (I, [P]),
+    "datum_ocean_ripples_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(I), ctypes.POINTER(I)]),
+    "datum_ocean_read_ripples": (I, [P, P]),
+    "datum_ocean_step_ripples": (I, [P, F, I]),
+    "datum_ocean_deposit_ripples": (I, [P, P, ctypes.c_size_t]),
+    "datum_ocean_deposit_body_ripples": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P]),
+    "datum_ocean_deposit_ripples_host": (I, [P, P, ctypes.c_size_t]),
+    "datum_ocean_deposit_body_ripples_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P]),
+    "datum_ocean_sample_ripples": (I, [P, P, ctypes.c_size_t, P]),
+    "datum_ocean_query_ripples": (I, [P, P, ctypes.c_size_t, P]),
 }
 
 
@@ -171,6 +184,12 @@ FOAM_MODES = {"off": FOAM_OFF, "jacobian": FOAM_JACOBIAN, "accumulate": FOAM_ACC
 # surface queries (datum_ocean_sample_surface, added at ABI 9): floats per record and the largest iteration count
 SURFACE_SAMPLE_FLOATS = 8
 SURFACE_MAX_ITERATIONS = 16
+
+# the ripple layer (datum_ocean_set_ripples, added at ABI 9): the sizes a layer can have, floats per wake record, the limits of a step
+RIPPLE_SIZES = (64, 128, 256, 512, 1024)
+RIPPLE_RECORD_FLOATS = 8
+RIPPLE_MAX_SUBSTEPS = 16
+RIPPLE_MAX_SPONGE = 64
 
 # body buoyancy (datum_ocean_reduce_bodies, added at ABI 9): floats per body record and per probe
 BODY_RECORD_FLOATS = 8
@@ -765,6 +784,81 @@ class Ocean:
         out = np.empty((bodies.shape[0], STEP_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_step_bodies_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(bodies), _ptr(motions), _ptr(pp), bodies.shape[0],
                                                           _ptr(pr), pr.shape[0], dt, substeps, _ptr(out)))
+        return out
+
+    # -- the ripple layer (datum_ocean_set_ripples): a local, scrolling wave grid fed by impulses and by the bodies' wakes ---------------
+
+    def set_ripples(self, R, s=1.0):
+        """Switch the layer on with R x R cells of side `s` metres (R one of RIPPLE_SIZES), at rest, origin (-R/2, -R/2); R = 0 frees it."""
+        self._check(self.lib.datum_ocean_set_ripples(self.h, R, s))
+
+    def set_ripple_params(self, c=2.0, gamma=0.05, sponge_cells=8, sponge_gamma=4.0):
+        """wave speed (m/s), damping (1/s), width of the absorbing border in cells (0: none) and its extra damping at the edge (1/s)"""
+        self._check(self.lib.datum_ocean_set_ripple_params(self.h, c, gamma, sponge_cells, sponge_gamma))
+
+    def center_ripples(self, x, y):
+        """Move the window so that the cell of (x, y) is its middle; the cells that entered are zeroed, none is copied."""
+        self._check(self.lib.datum_ocean_center_ripples(self.h, x, y))
+
+    def reset_ripples(self):
+        self._check(self.lib.datum_ocean_reset_ripples(self.h))
+
+    def ripples_device(self):
+        """(device pointer of the CURRENT state buffer, bytes, ox, oy); the pointer alternates between two buffers with every sub-step"""
+        ptr, nbytes, ox, oy = P(), ctypes.c_size_t(), I(), I()
+        self._check(self.lib.datum_ocean_ripples_device(self.h, ctypes.byref(ptr), ctypes.byref(nbytes), ctypes.byref(ox), ctypes.byref(oy)))
+        return ptr.value, nbytes.value, ox.value, oy.value
+
+    def read_ripples(self):
+        """the current state in window order, (R, R, 2) float32: [j][i] is cell (ox + i, oy + j), (height, rate); blocking"""
+        _, nbytes, _, _ = self.ripples_device()
+        R = int(round((nbytes // 8) ** 0.5))
+        out = np.empty((R, R, 2), np.float32)
+        self._check(self.lib.datum_ocean_read_ripples(self.h, _ptr(out)))
+        return out
+
+    def step_ripples(self, dt, substeps=1):
+        """Enqueue `substeps` sub-steps of dt / substeps, one launch each; the first takes the pending deposits in."""
+        self._check(self.lib.datum_ocean_step_ripples(self.h, dt, substeps))
+
+    def deposit_ripples(self, impulses_ptr, n):
+        """Enqueue `n` deposits (device pointer, 16 bytes each: x, y, volume in m^3, 0)."""
+        self._check(self.lib.datum_ocean_deposit_ripples(self.h, P(impulses_ptr) if impulses_ptr else None, n))
+
+    def deposit_body_ripples(self, cascades, oceanset, bodies_ptr, motions_ptr, nbodies, probes_ptr, nprobes, dt, records_ptr, iterations=4):
+        """Enqueue the wake of `nbodies` bodies over dt: reduce_body_drag's arguments; records of 8 floats: sum Vh, sum m sx, sum m sy,
+        dropped quanta, 0, 0, sum m, max residual.  Needs velocity on and a displace since."""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_deposit_body_ripples(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
+                                                              P(motions_ptr) if motions_ptr else None, nbodies, P(probes_ptr) if probes_ptr else None, nprobes,
+                                                              dt, P(records_ptr) if records_ptr else None))
+
+    def deposit_ripples_host(self, impulses):
+        """the same from a host array, blocking: `impulses` (n, 4) float32"""
+        imp = np.ascontiguousarray(impulses, np.float32).reshape(-1, 4)
+        self._check(self.lib.datum_ocean_deposit_ripples_host(self.h, _ptr(imp), imp.shape[0]))
+
+    def deposit_body_ripples_host(self, cascades, oceanset, bodies, motions, probes, dt, iterations=4):
+        """the wake from host arrays, blocking: `bodies` an array of BODY_DTYPE, `motions` one of BODY_MOTION_DTYPE of the same length,
+        `probes` (n, 4) float32; returns (nbodies, 8)"""
+        arr, n = self._list(cascades)
+        b = np.ascontiguousarray(bodies)
+        mo = np.ascontiguousarray(motions)
+        assert b.dtype.itemsize == ctypes.sizeof(Body) and mo.dtype.itemsize == ctypes.sizeof(BodyMotion) and mo.shape[0] == b.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
+        out = np.empty((b.shape[0], RIPPLE_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_deposit_body_ripples_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), _ptr(mo), b.shape[0], _ptr(pr), pr.shape[0], dt, _ptr(out)))
+        return out
+
+    def sample_ripples(self, points_ptr, n, out_ptr):
+        """Enqueue the sample of `n` points (device pointer, 8 bytes each) into `n` float4 (device pointer): height, d/dx, d/dy, rate."""
+        self._check(self.lib.datum_ocean_sample_ripples(self.h, P(points_ptr) if points_ptr else None, n, P(out_ptr) if out_ptr else None))
+
+    def query_ripples(self, points):
+        """the same from a host array, blocking: `points` (n, 2) float32; returns (n, 4) float32"""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty((p.shape[0], 4), np.float32)
+        self._check(self.lib.datum_ocean_query_ripples(self.h, _ptr(p), p.shape[0], _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

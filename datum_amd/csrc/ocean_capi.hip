@@ -30,6 +30,7 @@
 #include "ocean_velocity.hip"
 #include "ocean_drag.hip"
 #include "ocean_step.hip"
+#include "ocean_ripple.hip"
 
 using namespace ocean;
 
@@ -149,6 +150,16 @@ struct datum_ocean_ctx
   float4 *boundspartials = nullptr;
   int boundsgroups = 0;               // workgroups per cascade the partials were sized for
   bool boundscurrent = false;         // the records are those of the maps as they lie: set by reduce_bounds, cleared by displace, bind_maps and a release_memory that unbinds the maps
+
+  // the ripple layer (datum_ocean_set_ripples): nothing is allocated while rippleR == 0
+  int rippleR = 0;                    // cells per side, 0 = off
+  double ripples = 0.0;               // cell side, metres
+  int rippleox = 0, rippleoy = 0;     // the window's origin, cells
+  float2 *ripplestate[2] = { nullptr, nullptr };
+  int ripplecurrent = 0;              // the state buffer the next sub-step reads
+  int *ripplesrc = nullptr;           // pending deposits
+  double ripplec = 2.0, ripplegamma = 0.05, ripplespongegamma = 4.0;   // datum_ocean_set_ripple_params
+  int ripplesponge = 8;
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -985,6 +996,9 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->foam.own);
   (void)hipFree(ctx->velocity.own);
   (void)hipFree(ctx->velocitywork);
+  (void)hipFree(ctx->ripplestate[0]);
+  (void)hipFree(ctx->ripplestate[1]);
+  (void)hipFree(ctx->ripplesrc);
 
   for(Staging &st : ctx->staging)
     (void)hipFree(st.ptr);
@@ -2917,6 +2931,506 @@ int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int cou
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
+/* -- the ripple layer (ocean_ripple.hip) ------------------------------------------------------------------------------------------ */
+
+namespace
+{
+  size_t ripple_cells(datum_ocean_ctx const *ctx) { return (size_t)ctx->rippleR * ctx->rippleR; }
+
+  // what every call that needs the layer refuses; `name` goes into the error text
+  int check_ripples(datum_ocean_ctx *ctx, char const *name)
+  {
+    std::string const what = name;
+
+    if (!ctx)
+      return fail(nullptr, DATUM_OCEAN_EINVAL, (what + ": null handle").c_str());
+
+    if (ctx->rippleR == 0)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": the ripple layer is off (datum_ocean_set_ripples)").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  RippleGrid ripple_grid(datum_ocean_ctx const *ctx)
+  {
+    RippleGrid g;
+    g.R = ctx->rippleR;
+    g.ox = ctx->rippleox;
+    g.oy = ctx->rippleoy;
+    g.invs = (float)(1.0 / ctx->ripples);
+    return g;
+  }
+
+  int free_ripples(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, hipFree(ctx->ripplestate[0]));
+    ctx->ripplestate[0] = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->ripplestate[1]));
+    ctx->ripplestate[1] = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->ripplesrc));
+    ctx->ripplesrc = nullptr;
+    ctx->rippleR = 0;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // water at rest: both state buffers and the pending deposits, on the handle's stream
+  int clear_ripples(datum_ocean_ctx *ctx)
+  {
+    size_t const cells = ripple_cells(ctx);
+
+    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[0], 0, cells * sizeof(float2), ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[1], 0, cells * sizeof(float2), ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplesrc, 0, cells * sizeof(int), ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // device arrays, n > 0
+  int run_ripple_samples(datum_ocean_ctx *ctx, void const *points, size_t n, void *out)
+  {
+    RippleSampleArgs a;
+    a.state = ctx->ripplestate[ctx->ripplecurrent];
+    a.points = static_cast<float2 const*>(points);
+    a.samples = static_cast<float4*>(out);
+    a.g = ripple_grid(ctx);
+    a.count = (int)n;
+
+    HIPCHECK(ctx, launch_ripple_samples(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // what both impulse deposits refuse; `name` goes into the error text
+  int check_ripple_impulses(datum_ocean_ctx *ctx, void const *impulses, size_t n, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (n > 0 && !impulses)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null impulses").c_str());
+
+    if ((uintptr_t)impulses & 15)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": impulses must be 16-byte aligned").c_str());
+
+    if (n > (size_t)INT32_MAX / 16)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX / 16").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // a device array, n > 0
+  int run_ripple_impulses(datum_ocean_ctx *ctx, void const *impulses, size_t n)
+  {
+    RippleImpulseArgs a;
+    a.impulses = static_cast<float4 const*>(impulses);
+    a.src = ctx->ripplesrc;
+    a.g = ripple_grid(ctx);
+    a.count = (int)n;
+
+    HIPCHECK(ctx, launch_ripple_impulses(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the layer, dt, then body drag's checks: ESTATE exactly where that call returns it once the layer is on
+  int check_ripple_wake_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
+                             size_t nbodies, void const *probes, size_t nprobes, float dt, void const *records, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    if (!std::isfinite(dt))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (std::string(name) + ": dt is not finite").c_str());
+
+    return check_body_drag_args(ctx, cascades, count, set, iterations, bodies, motions, nbodies, probes, nprobes, records, name);
+  }
+
+  // device arrays, nbodies > 0
+  int run_ripple_wake(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
+                      size_t nbodies, void const *probes, size_t nprobes, float dt, void *records)
+  {
+    RippleWakeArgs a = {};
+    a.d.b.q = query_args(ctx, cascades, count, set, iterations);
+    a.d.b.bodies = static_cast<datum_ocean_body const*>(bodies);
+    a.d.b.probes = static_cast<BodyProbe const*>(probes);
+    a.d.b.records = static_cast<float4*>(records);
+    a.d.b.nbodies = (int)nbodies;
+    a.d.b.nprobes = (int)nprobes;
+    a.d.motions = static_cast<datum_ocean_body_motion const*>(motions);
+
+    for(int i = 0; i < count; ++i)
+      a.d.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+
+    a.src = ctx->ripplesrc;
+    a.g = ripple_grid(ctx);
+    a.dt = dt;
+
+    HIPCHECK(ctx, launch_ripple_wake(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  int check_ripple_points(datum_ocean_ctx *ctx, void const *points, size_t n, void const *out, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (n > 0 && (!points || !out))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or out").c_str());
+
+    if (((uintptr_t)points & 7) || ((uintptr_t)out & 15))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and out 16-byte aligned").c_str());
+
+    if (n > (size_t)INT32_MAX / 16)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX / 16").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_set_ripples(datum_ocean_t ctx, int R, float s)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripples: null handle");
+
+  if (R != 0 && R != 64 && R != 128 && R != 256 && R != 512 && R != 1024)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripples: R must be 0, 64, 128, 256, 512 or 1024");
+
+  if (R != 0 && !(std::isfinite(s) && s > 0.0f))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripples: s must be finite and positive");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  int rc = free_ripples(ctx);
+  if (rc != DATUM_OCEAN_OK || R == 0)
+    return rc;
+
+  size_t const cells = (size_t)R * R;
+
+  hipError_t e = hipMalloc(&ctx->ripplestate[0], cells * sizeof(float2));
+  if (e == hipSuccess)
+    e = hipMalloc(&ctx->ripplestate[1], cells * sizeof(float2));
+  if (e == hipSuccess)
+    e = hipMalloc(&ctx->ripplesrc, cells * sizeof(int));
+
+  if (e != hipSuccess)
+  {
+    (void)free_ripples(ctx);
+    return fail(ctx, (int)e, "datum_ocean_set_ripples: hipMalloc");
+  }
+
+  ctx->rippleR = R;
+  ctx->ripples = (double)s;
+  ctx->rippleox = ctx->rippleoy = -R / 2;
+  ctx->ripplecurrent = 0;
+
+  rc = clear_ripples(ctx);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_set_ripple_params(datum_ocean_t ctx, float c, float gamma, int sponge_cells, float sponge_gamma)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_params: null handle");
+
+  if (!(std::isfinite(c) && c > 0.0f))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_params: c must be finite and positive");
+
+  if (!std::isfinite(gamma) || gamma < 0.0f)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_params: gamma must be finite and not negative");
+
+  if (sponge_cells < 0 || sponge_cells > DATUM_OCEAN_RIPPLE_MAX_SPONGE)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_params: sponge_cells outside [0, DATUM_OCEAN_RIPPLE_MAX_SPONGE]");
+
+  if (!std::isfinite(sponge_gamma) || sponge_gamma < 0.0f)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_params: sponge_gamma must be finite and not negative");
+
+  ctx->ripplec = (double)c;
+  ctx->ripplegamma = (double)gamma;
+  ctx->ripplesponge = sponge_cells;
+  ctx->ripplespongegamma = (double)sponge_gamma;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
+{
+  int rc = check_ripples(ctx, "datum_ocean_center_ripples");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  RippleGrid g = ripple_grid(ctx);
+
+  if (!(ripple_coord_ok(x, g.invs) && ripple_coord_ok(y, g.invs)))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_center_ripples: x and y must be finite and within 2^30 cells");
+
+  // the cell of (x, y) as a deposit at it would take it: one fp32 product, floor
+  int const ox = (int)floorf(x * g.invs) - g.R / 2, oy = (int)floorf(y * g.invs) - g.R / 2;
+
+  if (ox == g.ox && oy == g.oy)
+    return DATUM_OCEAN_OK;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  RippleScrollArgs a;
+  a.state[0] = ctx->ripplestate[0];
+  a.state[1] = ctx->ripplestate[1];
+  a.src = ctx->ripplesrc;
+  a.oldx = g.ox;
+  a.oldy = g.oy;
+  g.ox = ox;
+  g.oy = oy;
+  a.g = g;
+
+  HIPCHECK(ctx, launch_ripple_scroll(a, ctx->stream));
+
+  ctx->rippleox = ox;
+  ctx->rippleoy = oy;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_reset_ripples(datum_ocean_t ctx)
+{
+  int rc = check_ripples(ctx, "datum_ocean_reset_ripples");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return clear_ripples(ctx);
+}
+
+int datum_ocean_ripples_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes, int *ox, int *oy)
+{
+  int rc = check_ripples(ctx, "datum_ocean_ripples_device");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!device_ptr)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripples_device: null argument");
+
+  *device_ptr = ctx->ripplestate[ctx->ripplecurrent];
+
+  if (bytes)
+    *bytes = ripple_cells(ctx) * sizeof(float2);
+  if (ox)
+    *ox = ctx->rippleox;
+  if (oy)
+    *oy = ctx->rippleoy;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_ripples(datum_ocean_t ctx, float *state)
+{
+  int rc = check_ripples(ctx, "datum_ocean_read_ripples");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!state)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_ripples: null argument");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // window order from the torus: up to four rectangles, split where the window wraps in memory
+  int const R = ctx->rippleR;
+  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
+
+  float2 const *src = ctx->ripplestate[ctx->ripplecurrent];
+  float2 *dst = reinterpret_cast<float2*>(state);
+
+  size_t const pitch = (size_t)R * sizeof(float2);
+
+  // (window columns [0, R - mx) are memory columns [mx, R), the rest memory columns [0, mx); rows likewise)
+  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
+  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
+
+  for(int j = 0; j < 2; ++j)
+    for(int i = 0; i < 2; ++i)
+      if (w[i] > 0 && h[j] > 0)
+        HIPCHECK(ctx, hipMemcpy2DAsync(dst + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i] * sizeof(float2), (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps)
+{
+  int rc = check_ripples(ctx, "datum_ocean_step_ripples");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (substeps < 1 || substeps > DATUM_OCEAN_RIPPLE_MAX_SUBSTEPS)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripples: substeps outside [1, DATUM_OCEAN_RIPPLE_MAX_SUBSTEPS]");
+
+  // (a negative dt would turn the damping into growth: f[k] above 1, unbounded where h (gamma + gamma_e) = -1)
+  if (!std::isfinite(dt) || dt < 0.0f)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripples: dt is not finite or is negative");
+
+  // the sub-step's length, rounded once here (two fp32 operations: the reciprocal, the product), as datum_ocean_step_bodies has it
+  float const inv = 1.0f / (float)substeps;
+  float const h = dt * inv;
+
+  // the scheme's stability bound is c h / s <= 1 / sqrt 2
+  if (ctx->ripplec * (double)h / ctx->ripples > 0.7)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripples: c * dt / (substeps * s) above 0.7, the scheme's stability bound with a margin");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  RippleStepArgs a = {};
+  a.src = ctx->ripplesrc;
+  a.g = ripple_grid(ctx);
+  a.B = ctx->ripplesponge;
+  a.h = h;
+  a.c2s2 = (float)(ctx->ripplec * ctx->ripplec / (ctx->ripples * ctx->ripples));
+
+  for(int k = 0; k <= a.B; ++k)
+  {
+    double const u = a.B > 0 ? (double)k / a.B : 0.0;
+
+    a.f[k] = (float)(1.0 / (1.0 + (double)h * (ctx->ripplegamma + ctx->ripplespongegamma * (u * u))));
+  }
+
+  for(int i = 0; i < substeps; ++i)
+  {
+    a.in = ctx->ripplestate[ctx->ripplecurrent];
+    a.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
+
+    HIPCHECK(ctx, launch_ripple_step(a, i == 0, ctx->stream));
+
+    ctx->ripplecurrent ^= 1;
+
+    // the first sub-step's neighbours read src too: no kernel clears it
+    if (i == 0)
+      HIPCHECK(ctx, hipMemsetAsync(ctx->ripplesrc, 0, ripple_cells(ctx) * sizeof(int), ctx->stream));
+  }
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_deposit_ripples(datum_ocean_t ctx, void const *impulses_device, size_t n)
+{
+  int rc = check_ripple_impulses(ctx, impulses_device, n, "datum_ocean_deposit_ripples");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_ripple_impulses(ctx, impulses_device, n);
+}
+
+int datum_ocean_deposit_ripples_host(datum_ocean_t ctx, float const *impulses, size_t n)
+{
+  int rc = check_ripple_impulses(ctx, impulses, n, "datum_ocean_deposit_ripples_host");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // the surface queries' point staging; the call waits, so the caller's array is free when it returns
+  Staging &in = ctx->staging[STAGE_POINTS];
+
+  rc = in.reserve(ctx, n * sizeof(float4));
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipMemcpyAsync(in.ptr, impulses, n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+
+  rc = run_ripple_impulses(ctx, in.ptr, n);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_deposit_body_ripples(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                     void const *bodies_device, void const *motions_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                     float dt, void *records_device)
+{
+  int rc = check_ripple_wake_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, dt, records_device, "datum_ocean_deposit_body_ripples");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_ripple_wake(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, dt, records_device);
+}
+
+int datum_ocean_deposit_body_ripples_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                          datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
+                                          float dt, float *records)
+{
+  int rc = check_ripple_wake_args(ctx, cascades, count, set, iterations, bodies, motions, nbodies, probes, nprobes, dt, records, "datum_ocean_deposit_body_ripples_host");
+  if (rc != DATUM_OCEAN_OK || nbodies == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // read_body_drag's staging: the probes and the motions beside the bodies, each grown on its own
+  Staging &dprobes = ctx->staging[STAGE_PROBES];
+  Staging &dmotions = ctx->staging[STAGE_MOTIONS];
+
+  rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
+  if (rc == DATUM_OCEAN_OK)
+    rc = dmotions.reserve(ctx, nbodies * sizeof(datum_ocean_body_motion));
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (nprobes > 0)
+    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
+
+  HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, nbodies * sizeof(datum_ocean_body_motion), hipMemcpyHostToDevice, ctx->stream));
+
+  return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
+                     [&](void const *in, void *out) { return run_ripple_wake(ctx, cascades, count, set, iterations, in, dmotions.ptr, nbodies, dprobes.ptr, nprobes, dt, out); });
+}
+
+int datum_ocean_sample_ripples(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device)
+{
+  int rc = check_ripple_points(ctx, points_device, n, out_device, "datum_ocean_sample_ripples");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_ripple_samples(ctx, points_device, n, out_device);
+}
+
+int datum_ocean_query_ripples(datum_ocean_t ctx, float const *points, size_t n, float *out)
+{
+  int rc = check_ripple_points(ctx, points, n, out, "datum_ocean_query_ripples");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return read_staged(ctx, ctx->staging[STAGE_POINTS], points, n * sizeof(float2), ctx->staging[STAGE_SAMPLES], out, n * sizeof(float4),
+                     [&](void const *in, void *dev) { return run_ripple_samples(ctx, in, n, dev); });
 }
 
 }   // extern "C"

@@ -389,6 +389,66 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_ripples(void *c, int R, float cellsize)
+  {
+    try
+    {
+      set_ocean_ripples(static_cast<HostContext*>(c)->context, R, cellsize);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_center_ocean_ripples(void *c, float x, float y)
+  {
+    try
+    {
+      center_ocean_ripples(static_cast<HostContext*>(c)->context, Vec2(x, y));
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_deposit_ocean_ripples(void *c, float const *impulses, size_t count)
+  {
+    try
+    {
+      deposit_ocean_ripples(static_cast<HostContext*>(c)->context, reinterpret_cast<OceanRippleImpulse const*>(impulses), count);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_deposit_ocean_body_ripples(void *c, void *p, void const *bodies, void const *motions, size_t nbodies, float const *probes, size_t nprobes, float dt, float *records, int iterations)
+  {
+    try
+    {
+      deposit_ocean_body_ripples(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), static_cast<datum_ocean_body const*>(bodies), static_cast<datum_ocean_body_motion const*>(motions), nbodies, reinterpret_cast<OceanBodyProbe const*>(probes), nprobes, dt, reinterpret_cast<OceanWakeRecord*>(records), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_step_ocean_ripples(void *c, float dt, int substeps)
+  {
+    try
+    {
+      step_ocean_ripples(static_cast<HostContext*>(c)->context, dt, substeps);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_query_ocean_ripples(void *c, float const *xy, size_t count, float *samples)
+  {
+    try
+    {
+      query_ocean_ripples(static_cast<HostContext*>(c)->context, reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanRippleSample*>(samples));
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_cast_ocean_rays(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
     try

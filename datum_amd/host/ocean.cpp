@@ -961,6 +961,60 @@ void step_ocean_bodies(OceanContext &context, OceanParams const &params, datum_o
 }
 
 
+///////////////////////// the ripple layer //////////////////////////////////
+void set_ocean_ripples(OceanContext &context, int R, float cellsize)
+{
+  if (!context.ready)
+    throw runtime_error("set_ocean_ripples: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_set_ripples(context.hip, R, cellsize), "datum_ocean_set_ripples");
+}
+
+void center_ocean_ripples(OceanContext &context, Vec2 const &centre)
+{
+  if (!context.ready)
+    throw runtime_error("center_ocean_ripples: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_center_ripples(context.hip, centre.x, centre.y), "datum_ocean_center_ripples");
+}
+
+void deposit_ocean_ripples(OceanContext &context, OceanRippleImpulse const *impulses, size_t count)
+{
+  if (!context.ready)
+    throw runtime_error("deposit_ocean_ripples: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_deposit_ripples_host(context.hip, reinterpret_cast<float const*>(impulses), count), "datum_ocean_deposit_ripples_host");
+}
+
+void deposit_ocean_body_ripples(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, OceanBodyProbe const *probes, size_t nprobes, float dt, OceanWakeRecord *records, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("deposit_ocean_body_ripples: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_deposit_body_ripples_host(context.hip, &cascade, 1, &set, iterations, bodies, motions, nbodies, reinterpret_cast<float const*>(probes), nprobes, dt, reinterpret_cast<float*>(records)), "datum_ocean_deposit_body_ripples_host");
+}
+
+void step_ocean_ripples(OceanContext &context, float dt, int substeps)
+{
+  if (!context.ready)
+    throw runtime_error("step_ocean_ripples: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_step_ripples(context.hip, dt, substeps), "datum_ocean_step_ripples");
+}
+
+void query_ocean_ripples(OceanContext &context, Vec2 const *positions, size_t count, OceanRippleSample *samples)
+{
+  if (!context.ready)
+    throw runtime_error("query_ocean_ripples: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_query_ripples(context.hip, reinterpret_cast<float const*>(positions), count, reinterpret_cast<float*>(samples)), "datum_ocean_query_ripples");
+}
+
+
 ///////////////////////// cast_ocean_rays ///////////////////////////////////
 void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
 {

@@ -427,6 +427,44 @@ static_assert(sizeof(OceanStepRecord) == 32, "OceanStepRecord must be the C ABI'
 
 void step_ocean_bodies(OceanContext &context, OceanParams const &params, datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, float dt, int substeps, OceanStepRecord *records, int iterations = 4);
 
+// the ripple layer (include/datum_ocean_hip.h: "ripple layer", the definition there): a local R x R wave grid of `cellsize`-metre cells that
+// carries what bodies and impacts do to the water; off until set_ocean_ripples, R = 0 frees it.  Host arrays, blocking, as every call
+// here; the same one-cascade list, set and state as reduce_ocean_body_drag for the wake, which throws where that call does.  Every call
+// but set_ocean_ripples throws while the layer is off
+struct OceanRippleImpulse
+{
+  lml::Vec2 position;                     // world x, y, metres
+  float volume;                           // m^3 of water added (negative: taken away)
+  float pad;                              // 0
+};
+
+struct OceanRippleSample
+{
+  float height;                           // eta, metres
+  float dx, dy;                           // its slopes
+  float rate;                             // d eta / dt, m/s
+};
+
+struct OceanWakeRecord
+{
+  float heave;                            // sum of the heave volumes deposited, m^3
+  lml::Vec2 surge;                        // sum of displaced volume times the hull's shift through the water
+  float dropped;                          // non-zero quanta that fell outside the window
+  float pad[2];                           // 0
+  float submerged;                        // sum weight * submersion: reduce_ocean_bodies' force, bit for bit
+  float residual;                         // the largest residual of the probes' velocity records
+};
+
+static_assert(sizeof(OceanRippleImpulse) == 16 && sizeof(OceanRippleSample) == 16, "the C ABI's 16-byte impulse and sample");
+static_assert(sizeof(OceanWakeRecord) == 32, "OceanWakeRecord must be the C ABI's record of DATUM_OCEAN_RIPPLE_RECORD_FLOATS floats");
+
+void set_ocean_ripples(OceanContext &context, int R, float cellsize);
+void center_ocean_ripples(OceanContext &context, lml::Vec2 const &centre);
+void deposit_ocean_ripples(OceanContext &context, OceanRippleImpulse const *impulses, std::size_t count);
+void deposit_ocean_body_ripples(OceanContext &context, OceanParams const &params, datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, float dt, OceanWakeRecord *records, int iterations = 4);
+void step_ocean_ripples(OceanContext &context, float dt, int substeps = 1);
+void query_ocean_ripples(OceanContext &context, lml::Vec2 const *positions, std::size_t count, OceanRippleSample *samples);
+
 // ray casts (include/datum_ocean_hip.h: datum_ocean_read_rays, the definition there): per ray a fixed march of `steps` samples to the first
 // change of side, `refine` bisections of that bracket, and the surface sample at the bracket's far end.  One cascade, as
 // query_ocean_surface; the maps the context last displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before

@@ -104,6 +104,12 @@ def load():
             "datum_host_reduce_ocean_bodies": (I, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_reduce_ocean_body_drag": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_step_ocean_bodies": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
+            "datum_host_set_ocean_ripples": (I, [P, I, F]),
+            "datum_host_center_ocean_ripples": (I, [P, F, F]),
+            "datum_host_deposit_ocean_ripples": (I, [P, P, ctypes.c_size_t]),
+            "datum_host_deposit_ocean_body_ripples": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P, I]),
+            "datum_host_step_ocean_ripples": (I, [P, F, I]),
+            "datum_host_query_ocean_ripples": (I, [P, P, ctypes.c_size_t, P]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
             "datum_host_ocean_surface_slab": (I, [P, P, P]),
@@ -373,6 +379,42 @@ class OceanContext:
         out = np.empty((bodies.shape[0], capi.STEP_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_step_ocean_bodies(self.c, params.p, bodies.ctypes.data_as(P), motions.ctypes.data_as(P), pp.ctypes.data_as(P), bodies.shape[0],
                                                           pr.ctypes.data_as(P), pr.shape[0], dt, substeps, out.ctypes.data_as(P), iterations))
+        return out
+
+    def set_ocean_ripples(self, R, cellsize=1.0):
+        """set_ocean_ripples: the ripple layer with R x R cells of `cellsize` metres (R one of capi.RIPPLE_SIZES), at rest; R = 0 frees it"""
+        self._check(self.lib.datum_host_set_ocean_ripples(self.c, R, cellsize))
+
+    def center_ocean_ripples(self, x, y):
+        """center_ocean_ripples: the window's middle becomes the cell of (x, y); entered cells are zeroed"""
+        self._check(self.lib.datum_host_center_ocean_ripples(self.c, x, y))
+
+    def deposit_ocean_ripples(self, impulses):
+        """deposit_ocean_ripples: `impulses` (n, 4) float32 (OceanRippleImpulse: x, y, volume in m^3, 0)"""
+        imp = np.ascontiguousarray(impulses, np.float32).reshape(-1, 4)
+        self._check(self.lib.datum_host_deposit_ocean_ripples(self.c, imp.ctypes.data_as(P), imp.shape[0]))
+
+    def deposit_ocean_body_ripples(self, params, bodies, motions, probes, dt, iterations=4):
+        """deposit_ocean_body_ripples: the wake of the bodies over dt, reduce_ocean_body_drag's arrays; returns (nbodies, 8) float32 records
+        (OceanWakeRecord: heave, surge x, surge y, dropped quanta, 0, 0, submerged, largest residual)"""
+        b = np.ascontiguousarray(bodies)
+        mo = np.ascontiguousarray(motions)
+        assert b.dtype.itemsize == ctypes.sizeof(capi.Body) and mo.dtype.itemsize == ctypes.sizeof(capi.BodyMotion) and mo.shape[0] == b.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
+        out = np.empty((b.shape[0], capi.RIPPLE_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_deposit_ocean_body_ripples(self.c, params.p, b.ctypes.data_as(P), mo.ctypes.data_as(P), b.shape[0], pr.ctypes.data_as(P), pr.shape[0],
+                                                                   dt, out.ctypes.data_as(P), iterations))
+        return out
+
+    def step_ocean_ripples(self, dt, substeps=1):
+        """step_ocean_ripples: `substeps` sub-steps of dt / substeps; the first takes the pending deposits in"""
+        self._check(self.lib.datum_host_step_ocean_ripples(self.c, dt, substeps))
+
+    def query_ocean_ripples(self, xy):
+        """query_ocean_ripples: (M, 4) float32 samples (OceanRippleSample: height, d/dx, d/dy, rate)"""
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], 4), np.float32)
+        self._check(self.lib.datum_host_query_ocean_ripples(self.c, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P)))
         return out
 
     def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):

@@ -53,7 +53,10 @@ extern "C" {
  *      bounded casts datum_ocean_cast_rays_bounded and datum_ocean_read_rays_bounded; then the surface velocity, datum_ocean_set_velocity,
  *      datum_ocean_bind_velocity, datum_ocean_velocity_device, datum_ocean_read_velocity, datum_ocean_sample_velocity_blend and
  *      datum_ocean_read_velocity_blend; then body drag, datum_ocean_reduce_body_drag and datum_ocean_read_body_drag; then body stepping,
- *      datum_ocean_step_bodies and datum_ocean_step_bodies_host.
+ *      datum_ocean_step_bodies and datum_ocean_step_bodies_host; then the ripple layer, datum_ocean_set_ripples,
+ *      datum_ocean_set_ripple_params, datum_ocean_center_ripples, datum_ocean_reset_ripples, datum_ocean_ripples_device,
+ *      datum_ocean_read_ripples, datum_ocean_step_ripples, datum_ocean_deposit_ripples, datum_ocean_deposit_ripples_host,
+ *      datum_ocean_deposit_body_ripples, datum_ocean_deposit_body_ripples_host, datum_ocean_sample_ripples and datum_ocean_query_ripples.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -758,6 +761,101 @@ int datum_ocean_step_bodies(datum_ocean_t ctx, int const *cascades, int count, d
 int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                  datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
                                  float const *probes, size_t nprobes, float dt, int substeps, float *records);
+
+/* -- ripple layer (added at ABI 9; nothing in the reference) ----------------------------------------------------------------------------
+ * Everything above couples one way: the water moves the bodies.  The FFT surface is periodic and statistical and cannot carry a local
+ * disturbance, so a wake, the rings round a bobbing crate or an impact live in a second, LOCAL layer: a small height field centred on the
+ * camera or the action that obeys a damped wave equation, takes sources from bodies and impulses, scrolls with its centre, and is added to
+ * the FFT surface by the renderer's shader, the way the foam plane is.  Off by default: while it is off nothing is
+ * allocated or launched, and on or off no other call's result changes by a bit.
+ *
+ * The layer is R x R cells of side s metres, R one of 64, 128, 256, 512, 1024.  It holds
+ *     state   two buffers of R·R float2 (η, η_t): the height in metres and its rate.  A sub-step reads one and writes the other
+ *     src     one plane of R·R int32: pending deposits, in units of 2^-20 m of height
+ * World cell (I, J) = (floor(x·invs), floor(y·invs)) lives at memory index (J mod R)·R + (I mod R), mod the floor one: a torus in memory.
+ * invs = 1/s is rounded once from double.  The window is the cells ox <= I < ox + R, oy <= J < oy + R for an integer origin (ox, oy).  Moving
+ * the window changes the origin and zeroes the cells that entered (both state buffers and src); no cell is copied.  Everything outside the
+ * window is water at rest, η = 0.
+ *
+ * THE STEP.  step_ripples(dt, substeps) runs `substeps` sub-steps (1 .. DATUM_OCEAN_RIPPLE_MAX_SUBSTEPS) of
+ *     inv = 1.0f / (float)substeps        h = dt · inv        both rounded once, on the host
+ * Per window cell and sub-step, every operator one fp32 operation as written (no contraction):
+ *     e   = η                       in the step's FIRST sub-step   e = η + (float)src · 2^-20   -- for the cell and for every neighbour it reads
+ *     lap = ((eL + eR) + (eD + eU)) − 4·e         L, R the cells I − 1, I + 1; D, U the cells J − 1, J + 1; a neighbour outside the window is 0
+ *     v1  = (η_t + h · (c2s2 · lap)) · f[k]       c2s2 = c²/s², rounded once on the host from double
+ *     e1  = e + h · v1                            the new cell is (e1, v1)
+ * the project's semi-implicit Euler: the rate first, the height with the new rate.  k = max(0, B − min(distance of the cell to the window's four
+ * edges, in cells)) is the sponge index (the outermost ring has k = B) and f[k] = 1 / (1 + h (γ + γe (k/B)²)) for k = 0 .. B, built on the host
+ * in double and rounded once; B = sponge_cells <= DATUM_OCEAN_RIPPLE_MAX_SPONGE, and with B = 0 there is no sponge and f[0] serves every cell.
+ * dt = 0 is legal (the pending deposits become heights and nothing else moves); dt < 0 or not finite is DATUM_OCEAN_EINVAL: the damping would
+ * grow.  After the first sub-step src is zero again.  The scheme is stable for c·h/s <= 1/√2; the call refuses c·h/s > 0.7 (that bound with a
+ * margin) with DATUM_OCEAN_EINVAL, computed in double from c, s, dt and substeps.  Defaults: c = 2 m/s, γ = 0.05 1/s, B = 8, γe = 4 1/s.
+ *
+ * DEPOSITS are integers, so that a plane repeats bit for bit whatever the order of the atomics.  For a volume V m³ at (x, y):
+ *     Q   = rint((V · (invs·invs)) · 2^20) clamped to ±2^30        rint to nearest, ties to even; Q = 0 deposits nothing
+ *     u   = x·invs − 0.5     I0 = floor(u)     wx = u − I0         cell centres stand at (I + ½)·s; y, J0, wy likewise
+ *     w00 = (1 − wx)·(1 − wy)     w10 = wx·(1 − wy)     w01 = (1 − wx)·wy
+ *     q00 = rint((float)Q·w00)   q10 = rint((float)Q·w10)   q01 = rint((float)Q·w01)   q11 = Q − ((q00 + q10) + q01)
+ * quantum q_ab goes to cell (I0 + a, J0 + b) with an atomic add on src: the plane's sum changes by Q exactly.  A quantum whose cell lies
+ * outside the window is dropped.  A non-finite x, y or V, or |x·invs| or |y·invs| >= 2^30, deposits nothing.
+ *   deposit_ripples        n records of 16 bytes (x, y, V, 0) in a DEVICE array, 16-byte aligned, one thread per record: impacts, rain,
+ *                          explosions.
+ *   deposit_body_ripples   THE WAKE.  datum_ocean_reduce_body_drag's arguments and rules, DATUM_OCEAN_ESTATE exactly where that call
+ *                          returns it, and dt.  With body drag's w, rec, d, m, u, e for a probe, bit for bit:
+ *                              heave   if 0 < d and d < cap:  splat Vh = (a · (−e.z)) · dt at (w.x, w.y)
+ *                                      a column that sinks relative to the water pushes water out; a dry or a fully submerged one displaces
+ *                                      nothing more
+ *                              surge   if d > 0:  splat −m at (w.x, w.y) and +m at (w.x + sx, w.y + sy),  sx = −(e.x·dt), sy = −(e.y·dt)
+ *                                      the column's displaced volume moves with the hull relative to the water; the two splats cancel
+ *                                      exactly where their weights agree
+ *                          Each body gets a record of DATUM_OCEAN_RIPPLE_RECORD_FLOATS = 8 floats, summed in body buoyancy's order by the
+ *                          same tree:  Σ Vh,  Σ m·sx,  Σ m·sy,  the count of non-zero quanta dropped,  0,  0,  Σ m,  max residual.
+ *                          Field 6 is datum_ocean_reduce_bodies' field 0 bit for bit.  A bad body or motion: eight quiet NaNs and no
+ *                          deposit (a body that is bad only through one bad PROBE has deposited its other probes).  THE SWELL IS NOT INCLUDED, as in body drag.  This is a KINEMATIC SOURCE, NOT A RADIATION SOLUTION: no
+ *                          boundary condition is solved on the hull, whose shape enters only through its probes.
+ *
+ *   set_ripples          R = 0 switches the layer off and frees everything.  Otherwise R must be one of the five sizes and s finite and
+ *                        positive; the new layer is at rest, its origin (−R/2, −R/2), its parameters kept.  Waits for the stream.
+ *   set_ripple_params    c finite and > 0; gamma and sponge_gamma finite and >= 0; sponge_cells 0 .. DATUM_OCEAN_RIPPLE_MAX_SPONGE.  Works
+ *                        while the layer is off.
+ *   center_ripples       the new origin is (floor(x·invs) − R/2, floor(y·invs) − R/2); one kernel zeroes the cells that entered; a jump of R
+ *                        cells or more clears the layer.  x, y finite with |x·invs|, |y·invs| < 2^30, else DATUM_OCEAN_EINVAL.
+ *   reset_ripples        water at rest, no pending deposit; the origin stays.
+ *   ripples_device       the CURRENT state buffer (the one the next sub-step reads), its bytes and the origin, for a renderer that binds
+ *                        it.  THE POINTER ALTERNATES between the layer's two buffers with every sub-step: ask again after each step.
+ *   read_ripples         the current state to the HOST in window order, [j][i][2] for cell (ox + i, oy + j); blocking.
+ *   sample_ripples       per DEVICE point (8 bytes, x y) a float4 (η, ∂xη, ∂yη, η_t), 16-byte aligned: the bilinear patch between the four
+ *                        cell centres around the point, in the deposit's u, I0, wx:
+ *                            a0 = η10 − η00   a1 = η11 − η01   e0 = η00 + wx·a0   e1 = η01 + wx·a1
+ *                            η = e0 + wy·(e1 − e0)     ∂xη = (a0 + wy·(a1 − a0))·invs     ∂yη = (e1 − e0)·invs      η_t as η
+ *                        Cells outside the window read 0.  A non-finite point gives four NaNs and fetches nothing; a finite one beyond
+ *                        2^30 cells gives zeros.  Pending deposits are not seen before the next step.
+ *   query_ripples        the same from HOST arrays, blocking, through the surface queries' staging.
+ *   deposit_ripples_host, deposit_body_ripples_host   the two deposits from HOST arrays, through device staging buffers (the surface
+ *                        queries' and read_body_drag's, grown on demand), all on the handle's stream; blocking: the arrays are free and, for
+ *                        the wake, the records are written when the call returns.  The same checks, kernels and bits.
+ * Every call but set_ripples and set_ripple_params returns DATUM_OCEAN_ESTATE while the layer is off.  All launches and memsets go on
+ * the handle's stream.  The layer is not added into the surface queries, gen_blend, the ray casts or step_bodies. */
+#define DATUM_OCEAN_RIPPLE_RECORD_FLOATS 8
+#define DATUM_OCEAN_RIPPLE_MAX_SUBSTEPS 16
+#define DATUM_OCEAN_RIPPLE_MAX_SPONGE 64
+int datum_ocean_set_ripples(datum_ocean_t ctx, int R, float s);
+int datum_ocean_set_ripple_params(datum_ocean_t ctx, float c, float gamma, int sponge_cells, float sponge_gamma);
+int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y);
+int datum_ocean_reset_ripples(datum_ocean_t ctx);
+int datum_ocean_ripples_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes, int *ox, int *oy);
+int datum_ocean_read_ripples(datum_ocean_t ctx, float *state);
+int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps);
+int datum_ocean_deposit_ripples(datum_ocean_t ctx, void const *impulses_device, size_t n);
+int datum_ocean_deposit_body_ripples(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                     void const *bodies_device, void const *motions_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                     float dt, void *records_device);
+int datum_ocean_deposit_ripples_host(datum_ocean_t ctx, float const *impulses, size_t n);
+int datum_ocean_deposit_body_ripples_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                          datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
+                                          float dt, float *records);
+int datum_ocean_sample_ripples(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device);
+int datum_ocean_query_ripples(datum_ocean_t ctx, float const *points, size_t n, float *out);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

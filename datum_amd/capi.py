@@ -160,6 +160,8 @@ SYMBOLS = {
     "datum_ocean_deposit_body_ripples_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P]),
     "datum_ocean_sample_ripples": (I, [P, P, ctypes.c_size_t, P]),
     "datum_ocean_query_ripples": (I, [P, P, ctypes.c_size_t, P]),
+    "datum_ocean_step_bodies_coupled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
+    "datum_ocean_step_bodies_coupled_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
 }
 
 
@@ -190,6 +192,9 @@ RIPPLE_SIZES = (64, 128, 256, 512, 1024)
 RIPPLE_RECORD_FLOATS = 8
 RIPPLE_MAX_SUBSTEPS = 16
 RIPPLE_MAX_SPONGE = 64
+
+# coupled stepping (datum_ocean_step_bodies_coupled, added at ABI 9): floats per body record
+COUPLED_RECORD_FLOATS = 12
 
 # body buoyancy (datum_ocean_reduce_bodies, added at ABI 9): floats per body record and per probe
 BODY_RECORD_FLOATS = 8
@@ -859,6 +864,33 @@ class Ocean:
         p = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
         out = np.empty((p.shape[0], 4), np.float32)
         self._check(self.lib.datum_ocean_query_ripples(self.h, _ptr(p), p.shape[0], _ptr(out)))
+        return out
+
+    # -- coupled stepping (datum_ocean_step_bodies_coupled): bodies and the ripple layer advance together, the wake pushes back ----------
+
+    def step_bodies_coupled(self, cascades, oceanset, bodies_ptr, motions_ptr, props_ptr, nbodies, probes_ptr, nprobes, dt, substeps, records_ptr, iterations=4):
+        """Enqueue `substeps` coupled sub-steps of dt / substeps: step_bodies' arguments (device pointers), with records of 12 floats per body:
+        Fx, Fy, Fz, tau x, tau y, tau z, sum m of the last sub-step, max residual, the wake's sum Vh, sum m sx, sum m sy of the last sub-step,
+        dropped quanta of all sub-steps.  Each sub-step the bodies feel the layer's height and rate and deposit their wake, then the layer
+        steps.  Needs velocity on, a displace since, and the layer on."""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_step_bodies_coupled(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
+                                                             P(motions_ptr) if motions_ptr else None, P(props_ptr) if props_ptr else None, nbodies,
+                                                             P(probes_ptr) if probes_ptr else None, nprobes, dt, substeps, P(records_ptr) if records_ptr else None))
+
+    def step_bodies_coupled_host(self, cascades, oceanset, bodies, motions, props, probes, dt, substeps=1, iterations=4):
+        """the same from host arrays, blocking: `bodies` and `motions` as step_bodies_host takes them, advanced IN PLACE; returns the
+        (nbodies, 12) records"""
+        arr, n = self._list(cascades)
+        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
+        assert bodies.flags.writeable and motions.flags.writeable
+        pp = np.ascontiguousarray(props)
+        assert bodies.dtype.itemsize == ctypes.sizeof(Body) and motions.dtype.itemsize == ctypes.sizeof(BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(BodyProps)
+        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
+        out = np.empty((bodies.shape[0], COUPLED_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_step_bodies_coupled_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(bodies), _ptr(motions), _ptr(pp), bodies.shape[0],
+                                                                  _ptr(pr), pr.shape[0], dt, substeps, _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

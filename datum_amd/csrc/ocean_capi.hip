@@ -31,6 +31,7 @@
 #include "ocean_drag.hip"
 #include "ocean_step.hip"
 #include "ocean_ripple.hip"
+#include "ocean_couple.hip"
 
 using namespace ocean;
 
@@ -3079,6 +3080,33 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
+  // c h / s in double, which a step holds against the scheme's stability bound
+  double ripple_courant(datum_ocean_ctx const *ctx, float h)
+  {
+    return ctx->ripplec * (double)h / ctx->ripples;
+  }
+
+  // what a sub-step of length h takes but its two state buffers: src, the grid, c2s2 and the sponge table, rounded once from double
+  // (datum_ocean_step_ripples, and datum_ocean_step_bodies_coupled for the layer's share of a coupled sub-step)
+  RippleStepArgs ripple_step_args(datum_ocean_ctx const *ctx, float h)
+  {
+    RippleStepArgs a = {};
+    a.src = ctx->ripplesrc;
+    a.g = ripple_grid(ctx);
+    a.B = ctx->ripplesponge;
+    a.h = h;
+    a.c2s2 = (float)(ctx->ripplec * ctx->ripplec / (ctx->ripples * ctx->ripples));
+
+    for(int k = 0; k <= a.B; ++k)
+    {
+      double const u = a.B > 0 ? (double)k / a.B : 0.0;
+
+      a.f[k] = (float)(1.0 / (1.0 + (double)h * (ctx->ripplegamma + ctx->ripplespongegamma * (u * u))));
+    }
+
+    return a;
+  }
+
   int check_ripple_points(datum_ocean_ctx *ctx, void const *points, size_t n, void const *out, char const *name)
   {
     int rc = check_ripples(ctx, name);
@@ -3295,24 +3323,12 @@ int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps)
   float const h = dt * inv;
 
   // the scheme's stability bound is c h / s <= 1 / sqrt 2
-  if (ctx->ripplec * (double)h / ctx->ripples > 0.7)
+  if (ripple_courant(ctx, h) > 0.7)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripples: c * dt / (substeps * s) above 0.7, the scheme's stability bound with a margin");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  RippleStepArgs a = {};
-  a.src = ctx->ripplesrc;
-  a.g = ripple_grid(ctx);
-  a.B = ctx->ripplesponge;
-  a.h = h;
-  a.c2s2 = (float)(ctx->ripplec * ctx->ripplec / (ctx->ripples * ctx->ripples));
-
-  for(int k = 0; k <= a.B; ++k)
-  {
-    double const u = a.B > 0 ? (double)k / a.B : 0.0;
-
-    a.f[k] = (float)(1.0 / (1.0 + (double)h * (ctx->ripplegamma + ctx->ripplespongegamma * (u * u))));
-  }
+  RippleStepArgs a = ripple_step_args(ctx, h);
 
   for(int i = 0; i < substeps; ++i)
   {
@@ -3696,6 +3712,161 @@ int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_bounded(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
+}
+
+}   // extern "C"
+
+/* -- coupled stepping (ocean_couple.hip) -------------------------------------------------------------------------------------------- */
+
+namespace
+{
+  // the layer and the ripple step's rule for dt, then body stepping's checks (ESTATE exactly where body drag returns it once the layer is
+  // on), then the ripple step's stability bound for the sub-step; `name` goes into the error text
+  int check_coupled_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
+                         void const *props, size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void const *records, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (!std::isfinite(dt) || dt < 0.0f)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt is not finite or is negative").c_str());
+
+    rc = check_step_args(ctx, cascades, count, set, iterations, bodies, motions, props, nbodies, probes, nprobes, dt, substeps, records, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    float const inv = 1.0f / (float)substeps;
+
+    if (ripple_courant(ctx, dt * inv) > 0.7)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": c * dt / (substeps * s) above 0.7, the ripple step's stability bound with a margin").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // device arrays; `substeps` rounds of: the bodies' coupled sub-step (nbodies > 0), then the layer's sub-step in its first form
+  int run_step_bodies_coupled(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void *bodies, void *motions,
+                              void const *props, size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void *records)
+  {
+    // the sub-step's length, rounded once here (two fp32 operations: the reciprocal, the product), as both parent calls have it
+    float const inv = 1.0f / (float)substeps;
+    float const h = dt * inv;
+
+    CoupleArgs a = {};
+    a.d.b.q = query_args(ctx, cascades, count, set, iterations);
+    a.d.b.bodies = a.bodies = static_cast<datum_ocean_body*>(bodies);
+    a.d.b.probes = static_cast<BodyProbe const*>(probes);
+    a.d.b.records = static_cast<float4*>(records);
+    a.d.b.nbodies = (int)nbodies;
+    a.d.b.nprobes = (int)nprobes;
+    a.d.motions = a.motions = static_cast<datum_ocean_body_motion*>(motions);
+    a.props = static_cast<datum_ocean_body_props const*>(props);
+
+    for(int i = 0; i < count; ++i)
+      a.d.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+
+    a.src = ctx->ripplesrc;
+    a.g = ripple_grid(ctx);
+    a.h = h;
+
+    RippleStepArgs r = ripple_step_args(ctx, h);
+
+    for(int i = 0; i < substeps; ++i)
+    {
+      if (nbodies > 0)
+      {
+        a.state = ctx->ripplestate[ctx->ripplecurrent];
+        a.first = i == 0;
+
+        HIPCHECK(ctx, launch_couple(a, ctx->stream));
+      }
+
+      // datum_ocean_step_ripples(h, 1): the first form takes the deposits in, and no kernel clears src
+      r.in = ctx->ripplestate[ctx->ripplecurrent];
+      r.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
+
+      HIPCHECK(ctx, launch_ripple_step(r, true, ctx->stream));
+
+      ctx->ripplecurrent ^= 1;
+
+      HIPCHECK(ctx, hipMemsetAsync(ctx->ripplesrc, 0, ripple_cells(ctx) * sizeof(int), ctx->stream));
+    }
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_step_bodies_coupled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                    void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                    float dt, int substeps, void *records_device)
+{
+  int rc = check_coupled_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device, "datum_ocean_step_bodies_coupled");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_step_bodies_coupled(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device);
+}
+
+int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                         datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
+                                         float const *probes, size_t nprobes, float dt, int substeps, float *records)
+{
+  int rc = check_coupled_args(ctx, cascades, count, set, iterations, bodies, motions, props, nbodies, probes, nprobes, dt, substeps, records, "datum_ocean_step_bodies_coupled_host");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // step_bodies_host's staging, the records' grown to 48 bytes per body; bodies and motions come back beside the records
+  Staging &dbodies = ctx->staging[STAGE_BODIES], &dmotions = ctx->staging[STAGE_MOTIONS], &dprops = ctx->staging[STAGE_PROPS];
+  Staging &dprobes = ctx->staging[STAGE_PROBES], &drecords = ctx->staging[STAGE_BODY_RECORDS];
+
+  size_t const bodybytes = nbodies * sizeof(datum_ocean_body), motionbytes = nbodies * sizeof(datum_ocean_body_motion);
+  size_t const recordbytes = nbodies * DATUM_OCEAN_COUPLED_RECORD_FLOATS * sizeof(float);
+
+  rc = dbodies.reserve(ctx, bodybytes);
+  if (rc == DATUM_OCEAN_OK)
+    rc = dmotions.reserve(ctx, motionbytes);
+  if (rc == DATUM_OCEAN_OK)
+    rc = dprops.reserve(ctx, nbodies * sizeof(datum_ocean_body_props));
+  if (rc == DATUM_OCEAN_OK)
+    rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
+  if (rc == DATUM_OCEAN_OK)
+    rc = drecords.reserve(ctx, recordbytes);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (nbodies > 0)
+  {
+    HIPCHECK(ctx, hipMemcpyAsync(dbodies.ptr, bodies, bodybytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, motionbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(dprops.ptr, props, nbodies * sizeof(datum_ocean_body_props), hipMemcpyHostToDevice, ctx->stream));
+  }
+
+  if (nprobes > 0)
+    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
+
+  rc = run_step_bodies_coupled(ctx, cascades, count, set, iterations, dbodies.ptr, dmotions.ptr, dprops.ptr, nbodies, dprobes.ptr, nprobes, dt, substeps, drecords.ptr);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (nbodies > 0)
+  {
+    HIPCHECK(ctx, hipMemcpyAsync(bodies, dbodies.ptr, bodybytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(motions, dmotions.ptr, motionbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(records, drecords.ptr, recordbytes, hipMemcpyDeviceToHost, ctx->stream));
+  }
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
 }
 
 }   // extern "C"

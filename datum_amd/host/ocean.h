@@ -465,6 +465,24 @@ void deposit_ocean_body_ripples(OceanContext &context, OceanParams const &params
 void step_ocean_ripples(OceanContext &context, float dt, int substeps = 1);
 void query_ocean_ripples(OceanContext &context, lml::Vec2 const *positions, std::size_t count, OceanRippleSample *samples);
 
+// coupled stepping (include/datum_ocean_hip.h: datum_ocean_step_bodies_coupled_host, the definition there): step_ocean_bodies' arguments;
+// bodies and the ripple layer advance together by dt in `substeps` coupled sub-steps -- each sub-step the bodies feel the layer's height
+// and rate and deposit their wake, then the layer steps.  Throws where step_ocean_bodies does, and while the layer is off
+struct OceanCoupledRecord
+{
+  lml::Vec3 force;                        // of the last sub-step
+  lml::Vec3 torque;                       // about the body origin
+  float submerged;                        // sum weight * submersion of the last sub-step
+  float residual;                         // the largest residual of the probes' records over all sub-steps
+  float heave;                            // the wake of the last sub-step: sum of the heave volumes deposited, m^3
+  lml::Vec2 surge;                        // ... and of displaced volume times the hull's shift through the water
+  float dropped;                          // non-zero quanta that fell outside the window, all sub-steps
+};
+
+static_assert(sizeof(OceanCoupledRecord) == 48, "OceanCoupledRecord must be the C ABI's record of DATUM_OCEAN_COUPLED_RECORD_FLOATS floats");
+
+void step_ocean_bodies_coupled(OceanContext &context, OceanParams const &params, datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, float dt, int substeps, OceanCoupledRecord *records, int iterations = 4);
+
 // ray casts (include/datum_ocean_hip.h: datum_ocean_read_rays, the definition there): per ray a fixed march of `steps` samples to the first
 // change of side, `refine` bisections of that bracket, and the surface sample at the bracket's far end.  One cascade, as
 // query_ocean_surface; the maps the context last displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before

@@ -110,6 +110,7 @@ def load():
             "datum_host_deposit_ocean_body_ripples": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P, I]),
             "datum_host_step_ocean_ripples": (I, [P, F, I]),
             "datum_host_query_ocean_ripples": (I, [P, P, ctypes.c_size_t, P]),
+            "datum_host_step_ocean_bodies_coupled": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
             "datum_host_ocean_surface_slab": (I, [P, P, P]),
@@ -415,6 +416,21 @@ class OceanContext:
         pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         out = np.empty((pts.shape[0], 4), np.float32)
         self._check(self.lib.datum_host_query_ocean_ripples(self.c, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P)))
+        return out
+
+    def step_ocean_bodies_coupled(self, params, bodies, motions, props, probes, dt, substeps=1, iterations=4):
+        """step_ocean_bodies_coupled: step_ocean_bodies' arguments; bodies and the ripple layer advance together, the bodies feeling the
+        layer; returns (nbodies, 12) float32 records (OceanCoupledRecord: force, torque, submerged, largest residual, the wake's heave,
+        surge x, surge y of the last sub-step, dropped quanta)"""
+        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
+        assert bodies.flags.writeable and motions.flags.writeable
+        pp = np.ascontiguousarray(props)
+        assert bodies.dtype.itemsize == ctypes.sizeof(capi.Body) and motions.dtype.itemsize == ctypes.sizeof(capi.BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(capi.BodyProps)
+        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
+        out = np.empty((bodies.shape[0], capi.COUPLED_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_step_ocean_bodies_coupled(self.c, params.p, bodies.ctypes.data_as(P), motions.ctypes.data_as(P), pp.ctypes.data_as(P), bodies.shape[0],
+                                                                  pr.ctypes.data_as(P), pr.shape[0], dt, substeps, out.ctypes.data_as(P), iterations))
         return out
 
     def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):

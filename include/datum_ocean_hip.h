@@ -56,7 +56,8 @@ extern "C" {
  *      datum_ocean_step_bodies and datum_ocean_step_bodies_host; then the ripple layer, datum_ocean_set_ripples,
  *      datum_ocean_set_ripple_params, datum_ocean_center_ripples, datum_ocean_reset_ripples, datum_ocean_ripples_device,
  *      datum_ocean_read_ripples, datum_ocean_step_ripples, datum_ocean_deposit_ripples, datum_ocean_deposit_ripples_host,
- *      datum_ocean_deposit_body_ripples, datum_ocean_deposit_body_ripples_host, datum_ocean_sample_ripples and datum_ocean_query_ripples.
+ *      datum_ocean_deposit_body_ripples, datum_ocean_deposit_body_ripples_host, datum_ocean_sample_ripples and datum_ocean_query_ripples;
+ *      then coupled stepping, datum_ocean_step_bodies_coupled and datum_ocean_step_bodies_coupled_host.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -835,7 +836,8 @@ int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int cou
  *                        queries' and read_body_drag's, grown on demand), all on the handle's stream; blocking: the arrays are free and, for
  *                        the wake, the records are written when the call returns.  The same checks, kernels and bits.
  * Every call but set_ripples and set_ripple_params returns DATUM_OCEAN_ESTATE while the layer is off.  All launches and memsets go on
- * the handle's stream.  The layer is not added into the surface queries, gen_blend, the ray casts or step_bodies. */
+ * the handle's stream.  The layer is not added into the surface queries, gen_blend, the ray casts or step_bodies; the one call that
+ * feels it is datum_ocean_step_bodies_coupled ("coupled stepping", below). */
 #define DATUM_OCEAN_RIPPLE_RECORD_FLOATS 8
 #define DATUM_OCEAN_RIPPLE_MAX_SUBSTEPS 16
 #define DATUM_OCEAN_RIPPLE_MAX_SPONGE 64
@@ -856,6 +858,77 @@ int datum_ocean_deposit_body_ripples_host(datum_ocean_t ctx, int const *cascades
                                           float dt, float *records);
 int datum_ocean_sample_ripples(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device);
 int datum_ocean_query_ripples(datum_ocean_t ctx, float const *points, size_t n, float *out);
+
+/* -- coupled stepping (added at ABI 9; nothing in the reference) ------------------------------------------------------------------------
+ * The link the chain above lacks: a body that FEELS the ripple layer.  datum_ocean_step_bodies keeps pose and motion in registers over its
+ * sub-steps and reads nothing back, so a caller has no place to add sample_ripples' height; here the bodies and the layer advance together
+ * by dt in `substeps` coupled sub-steps (1 .. DATUM_OCEAN_STEP_MAX_SUBSTEPS), and a boat rocks in another boat's wake.
+ *
+ * A call takes datum_ocean_step_bodies' arguments, with their rules and layouts.
+ *
+ *     inv = 1.0f / (float)substeps        h = dt · inv        both rounded once, on the host, as in both parent calls
+ *
+ * Per coupled sub-step, in this order:
+ *   1 BODIES.  One kernel walks every body's probes exactly as datum_ocean_step_bodies does: the same lanes, probe order and tree.  Per
+ *     probe at w it makes ONE velocity record rec above (w.x, w.y) (datum_ocean_sample_velocity_blend's) and ONE sample
+ *     s = (η, ∂xη, ∂yη, η_t) of the layer's CURRENT state buffer at (w.x, w.y) (datum_ocean_sample_ripples'; pending deposits are not
+ *     seen, cells outside the window read 0).  THE RIPPLED RECORD is
+ *         rec'[2] = rec[2] + s.η          rec'[6] = rec[6] + s.η_t          one fp32 addition each; every other field is rec's
+ *     From rec' it forms datum_ocean_step_bodies' ten sums and datum_ocean_deposit_body_ripples' wake with dt = h -- the deposits go onto
+ *     src, and the wake's Σ Vh, Σ m·sx, Σ m·sy and dropped count are summed beside the ten: fourteen fields in the body tree's order, the
+ *     tenth the maximum.  Then datum_ocean_step_bodies' steps 2-5 with h, and pose, motion and record are stored.  The wake is that of the
+ *     pose and motion at the START of the sub-step, as datum_ocean_deposit_body_ripples has it.
+ *   2 WATER.  One sub-step of the layer of length h in the step's FIRST form (it takes src in), src zeroed behind it, the current buffer
+ *     swapped: datum_ocean_step_ripples(h, 1), with f[k] and c2s2 built from h as that call builds them.
+ * The result is therefore: K rounds of the two reductions and the wake from rippled records, through the integrator, then
+ * datum_ocean_step_ripples(h, 1) -- bit for bit.  Every sub-step is a launch of its own: the layer's step between two of them needs
+ * the whole device.
+ *
+ * Each body gets a record of DATUM_OCEAN_COUPLED_RECORD_FLOATS = 12 floats (48 bytes):
+ *     0-6   F.x, F.y, F.z, τ.x, τ.y, τ.z, M of the LAST sub-step          7   the largest res over all sub-steps
+ *     8-10  the wake's Σ Vh, Σ m·sx, Σ m·sy of the LAST sub-step          11  the dropped quanta summed over all sub-steps
+ * Fields 7 and 11 fold from launch to launch through the record in memory: fmaxf and one fp32 addition with the old record's fields.
+ *
+ * Bad bodies follow datum_ocean_step_bodies' rules, with two differences that the launch per sub-step brings:
+ *   - a bad body's pose and motion in memory are what its LAST GOOD SUB-STEP wrote, not those from before the call;
+ *   - a body that turns bad through one bad probe has deposited its other probes of that sub-step (the wake's rule), and one that
+ *     turns bad only behind the integrator -- a pose or motion that is not finite -- has deposited ALL its probes of that sub-step.
+ * Its record is twelve quiet NaNs; a NaN in field 0 tells the next sub-step's launch that the body went bad, and it walks nothing and
+ * deposits nothing from then on.
+ *
+ * STABILITY OF A BODY'S OWN WAKE: IT NEEDS DRAG.  The wake is a kinematic source, and a body that feels it closes a loop the source was
+ * not made for: the heave splat lowers the cell under a sinking column by (a/s²)·(sink rate relative to the water)·h, the wave
+ * equation fills the hollow, and the filling flow -- water rising relative to the hull, rec'[6] -- is read by the next sub-step as the
+ * hull sinking further.  tests/test_couple64.py walks a box dropped from rest through 2000 sub-steps in float64 at the layer's default
+ * parameters over the grid a/s² = 0.01, 0.05, 0.25, 1: with cl = cq = 0 the heave and the total of body and layer energy GROW at every
+ * ratio of the grid (by a tenth of the drop at 0.01, without bound at 1), so no ratio is stable without damping and none is promised.
+ * What bounds the loop is the body's linear drag: with cl·D >= buoyancy·(a/s²) (SI numbers; D the draught, buoyancy = ρ·g) the heave
+ * never exceeds the drop, decays, and the total energy never exceeds its start -- measured at 0.01, 0.05 and 0.25; at a/s² = 1 that drag
+ * keeps the heave below the drop but not the energy below its start.  Give floating bodies that drag AND probes that stand for a quarter
+ * of a cell or less (a/s² <= 0.25): a small ratio alone does not bound it.  Another body's wake is no loop and needs none of this.
+ *
+ * THE FFT SURFACE IS FROZEN within a call; the layer is not.  THE SWELL IS NOT INCLUDED, as in body drag.  The ripple layer's other
+ * calls, datum_ocean_step_bodies and every other call keep their bits.
+ *
+ *   step_bodies_coupled        enqueue and return: 2 kernels and a memset per sub-step on the handle's stream.  records_device: nbodies ×
+ *                              48 bytes; every array a DEVICE pointer, 16-byte aligned.  It writes bodies, motions, records and the layer
+ *   step_bodies_coupled_host   the same from HOST arrays, blocking, through datum_ocean_step_bodies_host's staging; bodies and motions
+ *                              are copied back
+ * DATUM_OCEAN_ESTATE exactly where datum_ocean_reduce_body_drag returns it, and while the layer is off.  DATUM_OCEAN_EINVAL for everything
+ * datum_ocean_step_bodies refuses, for records that are not 16-byte aligned, for dt < 0 or not finite (the ripple step's rule) and for
+ * c·h/s > 0.7, computed in double as in datum_ocean_step_ripples.  The layer is looked at first: while it is off the call returns
+ * DATUM_OCEAN_ESTATE whatever its other arguments are (a null handle is DATUM_OCEAN_EINVAL).  A refused call enqueues nothing and
+ * changes nothing.
+ * nbodies == 0 still steps the water: it is datum_ocean_step_ripples(h, 1) × substeps.
+ * LEFT OUT: a flag to feel the layer without depositing into it; the layer in the surface queries, gen_blend and the ray casts; temporal
+ * blocking of the ripple step; a several-sub-steps-per-launch form. */
+#define DATUM_OCEAN_COUPLED_RECORD_FLOATS 12
+int datum_ocean_step_bodies_coupled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                    void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                    float dt, int substeps, void *records_device);
+int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                         datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
+                                         float const *probes, size_t nprobes, float dt, int substeps, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

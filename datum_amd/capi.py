@@ -162,6 +162,11 @@ SYMBOLS = {
     "datum_ocean_query_ripples": (I, [P, P, ctypes.c_size_t, P]),
     "datum_ocean_step_bodies_coupled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
     "datum_ocean_step_bodies_coupled_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
+    "datum_ocean_gen_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, P]),
+    "datum_ocean_sample_surface_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_surface_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
+    "datum_ocean_cast_rays_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_rays_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -891,6 +896,41 @@ class Ocean:
         out = np.empty((bodies.shape[0], COUPLED_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_step_bodies_coupled_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(bodies), _ptr(motions), _ptr(pp), bodies.shape[0],
                                                                   _ptr(pr), pr.shape[0], dt, substeps, _ptr(out)))
+        return out
+
+    # -- rippled reads (datum_ocean_gen_blend_rippled): the mesh, the query and the cast with the ripple layer's height and slopes on top -----
+
+    def gen_blend_rippled(self, cascades, oceanset, sizex, sizey, vertices_device_ptr):
+        """gen_blend() with the layer sampled at each vertex's stored (x, y): z lifted by its height, its slopes in the shaded normal"""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_gen_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), sizex, sizey, P(vertices_device_ptr)))
+
+    def sample_surface_blend_rippled(self, cascades, oceanset, points_ptr, count, samples_ptr, iterations=4):
+        """sample_surface_blend() with the layer sampled at the asked point: device pointers, enqueued on the handle's stream"""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_sample_surface_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
+                                                                      count, P(samples_ptr) if samples_ptr else None))
+
+    def read_surface_blend_rippled(self, cascades, oceanset, points, iterations=4):
+        """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
+        arr, n = self._list(cascades)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_surface_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
+
+    def cast_rays_rippled(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
+        """cast_rays() on the rippled water: every height of the search and the record at hi carry the layer"""
+        arr, c = self._list(cascades)
+        self._check(self.lib.datum_ocean_cast_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, P(rays_ptr) if rays_ptr else None, n,
+                                                           P(records_ptr) if records_ptr else None))
+
+    def read_rays_rippled(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
+        """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
+        arr, c = self._list(cascades)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
+        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

@@ -32,6 +32,7 @@
 #include "ocean_step.hip"
 #include "ocean_ripple.hip"
 #include "ocean_couple.hip"
+#include "ocean_rippled.hip"
 
 using namespace ocean;
 
@@ -2383,14 +2384,52 @@ namespace
     return rc != DATUM_OCEAN_OK ? rc : check_points(ctx, points, n, samples, name);
   }
 
-  // device arrays, n > 0
-  int run_surface_blend(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  // what the several-cascade mesh calls check; `name` goes into the error text
+  int check_gen_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void const *vertices, char const *name)
+  {
+    std::string const what = name;
+
+    if (!ctx || !set || !vertices)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null argument").c_str());
+
+    int rc = check_blend_list(ctx, cascades, count, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    if (sizex < 2 || sizey < 2)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": mesh must be at least 2 x 2").c_str());
+
+    if ((uintptr_t)vertices & 15)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": vertex buffer must be 16-byte aligned").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // (the shape is the launch's: gen_shape)
+  GenBlendArgs gen_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, void *vertices)
+  {
+    GenBlendArgs b;
+    b.g.set = *set;
+    b.g.map = nullptr;
+    b.g.vertices = (float*)vertices;
+    b.list = blend_list(ctx, cascades, count);
+    return b;
+  }
+
+  SurfaceBlendArgs surface_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
   {
     SurfaceBlendArgs b;
     b.q = query_args(ctx, cascades, count, set, iterations);
     b.points = static_cast<float2 const*>(points);
     b.samples = static_cast<float4*>(samples);
     b.count = (int)n;
+    return b;
+  }
+
+  // device arrays, n > 0
+  int run_surface_blend(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  {
+    SurfaceBlendArgs b = surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples);
 
     HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
 
@@ -2403,26 +2442,13 @@ extern "C"
 
 int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
 {
-  if (!ctx || !set || !vertices_device)
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_gen_blend: null argument");
-
-  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_gen_blend");
+  int rc = check_gen_blend_args(ctx, cascades, count, set, sizex, sizey, vertices_device, "datum_ocean_gen_blend");
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  if (sizex < 2 || sizey < 2)
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_gen_blend: mesh must be at least 2 x 2");
-
-  if ((uintptr_t)vertices_device & 15)
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_gen_blend: vertex buffer must be 16-byte aligned");
-
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  GenBlendArgs b;
-  b.g.set = *set;
-  b.g.map = nullptr;
-  b.g.vertices = (float*)vertices_device;
-  b.list = blend_list(ctx, cascades, count);
+  GenBlendArgs b = gen_blend_args(ctx, cascades, count, set, vertices_device);
 
   HIPCHECK(ctx, launch_gen_blend(b, ctx->N, sizex, sizey, ctx->stream));
 
@@ -3867,6 +3893,126 @@ int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades,
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;
+}
+
+}   // extern "C"
+
+/* -- rippled reads: the layer in the mesh, the surface query and the ray cast (ocean_rippled.hip) ---------------------------------------- */
+
+namespace
+{
+  // the layer's current state as a read sees it (the buffer datum_ocean_ripples_device returns)
+  RippledLayer rippled_layer(datum_ocean_ctx const *ctx)
+  {
+    RippledLayer l;
+    l.state = ctx->ripplestate[ctx->ripplecurrent];
+    l.g = ripple_grid(ctx);
+    return l;
+  }
+
+  // device arrays, n > 0
+  int run_surface_blend_rippled(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  {
+    SurfaceBlendRippledArgs r;
+    r.b = surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples);
+    r.layer = rippled_layer(ctx);
+
+    HIPCHECK(ctx, launch_surface_blend_rippled(r, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // device arrays, n > 0
+  int run_rays_rippled(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                       void const *rays, size_t n, void *records)
+  {
+    RayRippledArgs r;
+    r.a.q = query_args(ctx, cascades, count, set, iterations);
+    r.a.r = ray_batch(steps, refine, rays, n, records);
+    r.layer = rippled_layer(ctx);
+
+    HIPCHECK(ctx, launch_rays_rippled(r, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+// (each: the layer first -- a null handle EINVAL, the layer off ESTATE -- then the parent call's own checks under this call's name)
+
+int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
+{
+  int rc = check_ripples(ctx, "datum_ocean_gen_blend_rippled");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_gen_blend_args(ctx, cascades, count, set, sizex, sizey, vertices_device, "datum_ocean_gen_blend_rippled");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  GenBlendRippledArgs r;
+  r.b = gen_blend_args(ctx, cascades, count, set, vertices_device);
+  r.layer = rippled_layer(ctx);
+
+  HIPCHECK(ctx, launch_gen_blend_rippled(r, ctx->N, sizex, sizey, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_sample_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
+{
+  int rc = check_ripples(ctx, "datum_ocean_sample_surface_blend_rippled");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points_device, n, samples_device, "datum_ocean_sample_surface_blend_rippled");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_surface_blend_rippled(ctx, cascades, count, set, iterations, points_device, n, samples_device);
+}
+
+int datum_ocean_read_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
+{
+  int rc = check_ripples(ctx, "datum_ocean_read_surface_blend_rippled");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples, "datum_ocean_read_surface_blend_rippled");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend_rippled(ctx, cascades, count, set, iterations, in, n, out); });
+}
+
+int datum_ocean_cast_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  void const *rays_device, size_t n, void *records_device)
+{
+  int rc = check_ripples(ctx, "datum_ocean_cast_rays_rippled");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_rippled");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_rays_rippled(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
+}
+
+int datum_ocean_read_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  float const *rays, size_t n, float *records)
+{
+  int rc = check_ripples(ctx, "datum_ocean_read_rays_rippled");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, "datum_ocean_read_rays_rippled");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_rippled(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
 }
 
 }   // extern "C"

@@ -1,5 +1,5 @@
-// ocean_gen_store.inc -- the tail of a mesh kernel (ocean_gen.hip), included as text by ocean_gen_kernel and ocean_gen_blend_kernel
-// (ocean_blend.hip): the tangent, the vertex and its way through LDS into the mesh.
+// ocean_gen_store.inc -- the tail of a mesh kernel (ocean_gen.hip), included as text by ocean_gen_kernel, ocean_gen_blend_kernel
+// (ocean_blend.hip) and ocean_gen_blend_rippled_kernel (ocean_rippled.hip): the tangent, the vertex and its way through LDS into the mesh.
 // In scope before: ocean_gen_tile.inc's names; ph; position[ph]; p3 displacement, tbn2; float4 *mine (the wave's 6 KB of LDS).
 
       // tbn[0] = normalize((1, 0, 0) - tbn[2].x * tbn[2])
@@ -11,7 +11,12 @@
       // The wave's 4 rows x 32 vertices = 4 x 96 float4 go through its 6 KB of LDS: lane i then stores float4 number
       // i, 64 + i, ... 320 + i of the wave's 384 (three 16-byte stores per vertex at a 48-byte stride touch every line three times).
 
+      // (OCEAN_GEN_STORE_LIFT, where the including kernel defines it: a v2 added to the finished height, one more fp32 addition)
+#ifdef OCEAN_GEN_STORE_LIFT
+      v2 const px = position[ph].x - displacement.x, py = position[ph].y - displacement.y, pz = (position[ph].z + displacement.z) + OCEAN_GEN_STORE_LIFT;
+#else
       v2 const px = position[ph].x - displacement.x, py = position[ph].y - displacement.y, pz = position[ph].z + displacement.z;
+#endif
       v2 const tu = 0.1f * position[ph].x, tv = 0.1f * position[ph].y;
 
       #pragma unroll

@@ -8,7 +8,8 @@
 //   * QueryCorners: one cascade at one position -- the resource over its map, gen's REPEAT bilinear fetch (SurfaceTexel) and part A of
 //     the four corners.  Nothing else in the five kernels makes a SurfaceTexel or loads from a map;
 //   * three final evaluations over it: query_height (part A alone: what a ray's search needs), query_record (parts A and B and the foam
-//     planes: the record's eight fields) and query_velocity (part A and the velocity planes).  Each is the same operations in the same
+//     planes: the record's eight fields; query_sums is its loop and query_finish what follows it, so that the rippled record of
+//     ocean_rippled.hip puts the layer's slopes between the two) and query_velocity (part A and the velocity planes).  Each is the same operations in the same
 //     order on what it shares with the others, so a height has the record's bits;
 //   * query_each_point: the prologue of the one-point-per-thread kernels.
 // Every fetch goes through a buffer resource sized to what it reads; a zero bilinear weight pushes its corner out of range (-256).
@@ -196,9 +197,15 @@ namespace ocean
     return (a.frame.basez + a.set.swellamplitude * b.st) + dz;
   }
 
-  // the record: parts A and B and the foam plane of every listed cascade
+  // the record's sums over the list: the displacement, the slopes (m.x / m.z, m.y / m.z) and the foam as the record stores it
+  struct QuerySums
+  {
+    float dx, dy, dz, sx, sy, foam;
+  };
+
+  // parts A and B and the foam plane of every listed cascade: the one loop behind every record
   template<int LAYOUT>
-  __device__ __forceinline__ QueryRecord query_record(QueryArgs const &a, QueryBase const &b, float2 q)
+  __device__ __forceinline__ QuerySums query_sums(QueryArgs const &a, QueryBase const &b)
   {
     float dx = 0.0f, dy = 0.0f, dz = 0.0f, sx = 0.0f, sy = 0.0f, foam = 0.0f;
 
@@ -258,15 +265,28 @@ namespace ocean
     if (a.list.foammode == DATUM_OCEAN_FOAM_JACOBIAN)
       foam = 1.0f + foam;
 
+    return QuerySums{ dx, dy, dz, sx, sy, foam };
+  }
+
+  // the record of the sums: V(b) and the residual, the shading normal of the summed slopes, the foam
+  __device__ __forceinline__ QueryRecord query_finish(QueryArgs const &a, QueryBase const &b, float2 q, QuerySums const &s)
+  {
     QueryRecord r;
 
-    r.v = query_position(a, b, q, dx, dy, dz);
+    r.v = query_position(a, b, q, s.dx, s.dy, s.dz);
 
-    blend_surface_normal(a.frame, b.st, b.ct, sx, sy, r.m.x, r.m.y, r.m.z);
+    blend_surface_normal(a.frame, b.st, b.ct, s.sx, s.sy, r.m.x, r.m.y, r.m.z);
 
-    r.m.w = foam;
+    r.m.w = s.foam;
 
     return r;
+  }
+
+  // the record: parts A and B and the foam plane of every listed cascade
+  template<int LAYOUT>
+  __device__ __forceinline__ QueryRecord query_record(QueryArgs const &a, QueryBase const &b, float2 q)
+  {
+    return query_finish(a, b, q, query_sums<LAYOUT>(a, b));
   }
 
   // the record's first half, and the listed cascades' velocity planes (`vel`, in list order) sampled with the same fetch and summed in

@@ -469,6 +469,36 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_query_ocean_surface_rippled(void *c, void *p, float const *xy, size_t count, float *samples, int iterations)
+  {
+    try
+    {
+      query_ocean_surface_rippled(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanSurfaceSample*>(samples), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_cast_ocean_rays_rippled(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
+  {
+    try
+    {
+      cast_ocean_rays_rippled(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_gen_ocean_surface_rippled(void *c, void *ocean, datum_host_camera const *camera, void *p)
+  {
+    try
+    {
+      gen_ocean_surface_rippled(static_cast<HostContext*>(c)->context, static_cast<Ocean const*>(ocean), make_camera(*camera), *static_cast<OceanParams*>(p));
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_reduce_ocean_bounds(void *c)
   {
     try

@@ -1043,6 +1043,47 @@ void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay 
 }
 
 
+///////////////////////// rippled reads /////////////////////////////////////
+void query_ocean_surface_rippled(OceanContext &context, OceanParams const &params, Vec2 const *positions, size_t count, OceanSurfaceSample *samples, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("query_ocean_surface_rippled: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_surface_blend_rippled(context.hip, &cascade, 1, &set, iterations, reinterpret_cast<float const*>(positions), count, reinterpret_cast<float*>(samples)), "datum_ocean_read_surface_blend_rippled");
+}
+
+void cast_ocean_rays_rippled(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
+{
+  if (!context.ready)
+    throw runtime_error("cast_ocean_rays_rippled: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_rays_rippled(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays_rippled");
+}
+
+void gen_ocean_surface_rippled(OceanContext &context, Ocean const *target, Camera const &camera, OceanParams const &params)
+{
+  if (!context.ready)
+    throw runtime_error("gen_ocean_surface_rippled: the context is not prepared (prepare_ocean_context)");
+
+  assert(target->ready());
+
+  datum_ocean_set set = make_oceanset(camera, params);
+
+  int const cascade = 0;
+
+  // the mesh alone, from the maps the context last displaced: nothing is displaced here
+  check(context.hip, datum_ocean_gen_blend_rippled(context.hip, &cascade, 1, &set, target->sizex, target->sizey, target->vertexbuffer.vertices), "datum_ocean_gen_blend_rippled");
+}
+
+
 ///////////////////////// reduce_ocean_bounds ///////////////////////////////
 void reduce_ocean_bounds(OceanContext &context)
 {

@@ -509,6 +509,15 @@ static_assert(sizeof(OceanRayRecord) == 48, "OceanRayRecord must be the C ABI's 
 
 void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
 
+// rippled reads (include/datum_ocean_hip.h: "rippled reads", the definition there): query_ocean_surface, cast_ocean_rays and the mesh WITH
+// the ripple layer's current state on top -- the water step_ocean_bodies_coupled floats its bodies on.  Cascade 0 and host arrays, as their
+// parents; gen_ocean_surface_rippled writes the rippled mesh of cascade 0 into `target`'s vertex buffer from the maps the context last
+// displaced (after a render_ocean_surface / displace_ocean_surface) and displaces nothing itself.  All three throw before
+// prepare_ocean_context, and while the layer is off (set_ocean_ripples)
+void query_ocean_surface_rippled(OceanContext &context, OceanParams const &params, lml::Vec2 const *positions, std::size_t count, OceanSurfaceSample *samples, int iterations = 4);
+void cast_ocean_rays_rippled(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
+void gen_ocean_surface_rippled(OceanContext &context, Ocean const *target, Camera const &camera, OceanParams const &params);
+
 // surface bounds (include/datum_ocean_hip.h: datum_ocean_reduce_bounds, the definition there): the extrema of the displacement the context
 // last displaced, reduced on the device, and what they say about the surface under `params`: every height lies strictly between zlo and
 // zhi, every vertex within `reach` of its undisplaced position along x and y.  One cascade, as query_ocean_surface.  reduce_ocean_bounds

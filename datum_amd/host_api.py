@@ -112,6 +112,9 @@ def load():
             "datum_host_query_ocean_ripples": (I, [P, P, ctypes.c_size_t, P]),
             "datum_host_step_ocean_bodies_coupled": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
+            "datum_host_query_ocean_surface_rippled": (I, [P, P, P, ctypes.c_size_t, P, I]),
+            "datum_host_cast_ocean_rays_rippled": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
+            "datum_host_gen_ocean_surface_rippled": (I, [P, P, ctypes.POINTER(CameraDesc), P]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
             "datum_host_ocean_surface_slab": (I, [P, P, P]),
             "datum_host_cast_ocean_rays_bounded": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
@@ -440,6 +443,25 @@ class OceanContext:
         out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_cast_ocean_rays(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
         return out
+
+    def query_ocean_surface_rippled(self, params, xy, iterations=4):
+        """query_ocean_surface_rippled: query_ocean_surface with the ripple layer's height and slopes on top; (M, 8) float32"""
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], capi.SURFACE_SAMPLE_FLOATS), np.float32)
+        self._check(self.lib.datum_host_query_ocean_surface_rippled(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
+        return out
+
+    def cast_ocean_rays_rippled(self, params, rays, iterations=4, steps=32, refine=8):
+        """cast_ocean_rays_rippled: cast_ocean_rays' arguments and records, on the water with the ripple layer on top"""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
+        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_cast_ocean_rays_rippled(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
+        return out
+
+    def gen_ocean_surface_rippled(self, mesh, params, camera=None):
+        """gen_ocean_surface_rippled: the rippled mesh of cascade 0 into the mesh's vertex buffer, from the maps last displaced"""
+        cam = camera or example_camera()
+        self._check(self.lib.datum_host_gen_ocean_surface_rippled(self.c, mesh[0], ctypes.byref(cam), params.p))
 
     def reduce_ocean_bounds(self):
         """reduce_ocean_bounds: enqueue the reduction of the displacement last computed; current until the next render / displace"""

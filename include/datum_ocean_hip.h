@@ -57,7 +57,9 @@ extern "C" {
  *      datum_ocean_set_ripple_params, datum_ocean_center_ripples, datum_ocean_reset_ripples, datum_ocean_ripples_device,
  *      datum_ocean_read_ripples, datum_ocean_step_ripples, datum_ocean_deposit_ripples, datum_ocean_deposit_ripples_host,
  *      datum_ocean_deposit_body_ripples, datum_ocean_deposit_body_ripples_host, datum_ocean_sample_ripples and datum_ocean_query_ripples;
- *      then coupled stepping, datum_ocean_step_bodies_coupled and datum_ocean_step_bodies_coupled_host.
+ *      then coupled stepping, datum_ocean_step_bodies_coupled and datum_ocean_step_bodies_coupled_host; then the rippled reads,
+ *      datum_ocean_gen_blend_rippled, datum_ocean_sample_surface_blend_rippled, datum_ocean_read_surface_blend_rippled,
+ *      datum_ocean_cast_rays_rippled and datum_ocean_read_rays_rippled.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -836,8 +838,9 @@ int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int cou
  *                        queries' and read_body_drag's, grown on demand), all on the handle's stream; blocking: the arrays are free and, for
  *                        the wake, the records are written when the call returns.  The same checks, kernels and bits.
  * Every call but set_ripples and set_ripple_params returns DATUM_OCEAN_ESTATE while the layer is off.  All launches and memsets go on
- * the handle's stream.  The layer is not added into the surface queries, gen_blend, the ray casts or step_bodies; the one call that
- * feels it is datum_ocean_step_bodies_coupled ("coupled stepping", below). */
+ * the handle's stream.  The layer is not added into the surface queries, gen_blend, the ray casts or step_bodies themselves, which keep
+ * their bits; the one call that feels it is datum_ocean_step_bodies_coupled ("coupled stepping", below), and the calls that SHOW it are
+ * the mesh, the query and the cast of "rippled reads" (below, behind coupled stepping). */
 #define DATUM_OCEAN_RIPPLE_RECORD_FLOATS 8
 #define DATUM_OCEAN_RIPPLE_MAX_SUBSTEPS 16
 #define DATUM_OCEAN_RIPPLE_MAX_SPONGE 64
@@ -920,8 +923,8 @@ int datum_ocean_query_ripples(datum_ocean_t ctx, float const *points, size_t n, 
  * DATUM_OCEAN_ESTATE whatever its other arguments are (a null handle is DATUM_OCEAN_EINVAL).  A refused call enqueues nothing and
  * changes nothing.
  * nbodies == 0 still steps the water: it is datum_ocean_step_ripples(h, 1) × substeps.
- * LEFT OUT: a flag to feel the layer without depositing into it; the layer in the surface queries, gen_blend and the ray casts; temporal
- * blocking of the ripple step; a several-sub-steps-per-launch form. */
+ * LEFT OUT: a flag to feel the layer without depositing into it; temporal blocking of the ripple step; a several-sub-steps-per-launch
+ * form.  (The layer in the surface query, gen_blend and the ray cast is no longer left out: "rippled reads", below.) */
 #define DATUM_OCEAN_COUPLED_RECORD_FLOATS 12
 int datum_ocean_step_bodies_coupled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                     void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
@@ -929,6 +932,59 @@ int datum_ocean_step_bodies_coupled(datum_ocean_t ctx, int const *cascades, int 
 int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                          datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
                                          float const *probes, size_t nprobes, float dt, int substeps, float *records);
+
+/* -- rippled reads (added at ABI 9; nothing in the reference) ---------------------------------------------------------------------------
+ * The read side of the ripple layer: the mesh, the surface query and the ray cast of the summed FFT surface WITH the layer on top -- the
+ * water coupled stepping floats its bodies on, by coupled stepping's rule rec'[2] = rec[2] + s.η.  Opt-in: the parent calls
+ * (datum_ocean_gen_blend, datum_ocean_sample_surface_blend, datum_ocean_cast_rays and their host twins), the ripple layer's calls and
+ * datum_ocean_step_bodies_coupled keep their bits.
+ *
+ * Every call reads the layer's CURRENT state buffer (the one datum_ocean_ripples_device returns) and writes nothing into the layer.  As
+ * in datum_ocean_sample_ripples and in coupled stepping: pending deposits are not seen; cells outside the window read 0; a coordinate
+ * beyond 2^30 cells gives zeros; s = (η, ∂xη, ∂yη, η_t) is datum_ocean_sample_ripples' sample, unchanged.
+ *
+ * THE RIPPLED RECORD above a world point q.  rec is datum_ocean_sample_surface_blend's record (8 floats), s the layer's sample at
+ * (q.x, q.y) -- the ASKED point, as coupled stepping samples at the probe's (w.x, w.y), not the solved base point b:
+ *     rec'[2] = rec[2] + s.η                              one fp32 addition; fields 0, 1, 3 and 7 are rec's bits
+ *     p' = (p.x + (−0.5f · s.∂xη), p.y + (−0.5f · s.∂yη))   one fp32 product and one addition per component, behind the loop over the list
+ *     fields 4-6: dn = normalize(p'.x, p'.y, 1) through the same frame as the parent's
+ * The layer is one more entry behind the cascade list in the map's own slope convention, m.x / m.z = −½ ∂z/∂x.  The solve
+ * b ← b + (q − V(b).xy) is untouched: the layer displaces nothing horizontally.  A non-finite q gives eight quiet NaNs and fetches
+ * nothing.
+ *
+ * THE RIPPLED HEIGHT is the parent's height + s.η, one fp32 addition: by construction the rippled record's field 2, bit for bit.
+ *
+ * THE RIPPLED MESH VERTEX is datum_ocean_gen_blend's vertex, with the layer sampled at the vertex's OWN horizontal position
+ * (px, py) = position.xy − displacement.xy, the two floats the vertex stores:
+ *     pz' = pz + s.η          in shaded waves slopex, slopey each + (−0.5f · ∂η) before dn is formed
+ * A vertex whose stored x or y is not finite gets the sample's four NaNs: its z and, in a shaded wave, its normal are NaN (no ray of a
+ * finite camera gives one: above the horizon gen puts the vertex 10^6 m away, which is finite).
+ * Unshaded waves keep the plane normal (gen's rule).  Position x, y and the texcoord are gen_blend's bits; the tangent follows from the
+ * new normal as in gen.
+ *
+ * THE RIPPLED CAST is datum_ocean_cast_rays with every height of the march and the bisection the rippled height, the record at hi the
+ * rippled record and g taken from its field 2.
+ *
+ *   gen_blend_rippled                  datum_ocean_gen_blend's arguments, rules and ordering; one kernel
+ *   sample_surface_blend_rippled       datum_ocean_sample_surface_blend's; one kernel
+ *   read_surface_blend_rippled         datum_ocean_read_surface_blend's: HOST arrays, blocking, the queries' staging
+ *   cast_rays_rippled                  datum_ocean_cast_rays'; one kernel
+ *   read_rays_rippled                  datum_ocean_read_rays': HOST arrays, blocking
+ * Each returns what its parent call returns for the same arguments, with its own name in the error text.  The layer is looked at first:
+ * while it is off the call returns DATUM_OCEAN_ESTATE whatever its other arguments are (a null handle is DATUM_OCEAN_EINVAL).  n == 0
+ * enqueues nothing.  A refused call enqueues nothing and changes nothing.
+ * LEFT OUT: the bounded cast (its slab would need a bound on |η|) and a slab for the layer; the layer's rate in
+ * datum_ocean_sample_velocity_blend; the layer in datum_ocean_reduce_bodies, datum_ocean_reduce_body_drag and datum_ocean_step_bodies
+ * (datum_ocean_step_bodies_coupled is the call for that); foam from the layer; anything on the displace path. */
+int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device);
+int datum_ocean_sample_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                             void const *points_device, size_t n, void *samples_device);
+int datum_ocean_read_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                           float const *points, size_t n, float *samples);
+int datum_ocean_cast_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  void const *rays_device, size_t n, void *records_device);
+int datum_ocean_read_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                  float const *rays, size_t n, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -334,6 +334,27 @@ def _ptr(a):
     return a.ctypes.data_as(P)
 
 
+def _dev(ptr):
+    """an optional device pointer given as an integer: None and 0 are the C null"""
+    return P(ptr) if ptr else None
+
+
+def _body_batch(bodies, motions, props, probes, floats, in_place=False):
+    """A body call's host arrays as its C arguments up to the records -- [bodies, (motions, (props,)) nbodies, probes, nprobes] -- and the
+    records' (nbodies, floats) array to pass last.  `motions` and `props` are None where the call takes none; `in_place` (the step twins,
+    which write bodies and motions back): both must be writable contiguous arrays already, and neither is copied."""
+    if in_place:
+        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
+        assert bodies.flags.writeable and motions.flags.writeable
+    arrays = [np.ascontiguousarray(np.frombuffer(bytes(bodies), BODY_DTYPE) if isinstance(bodies, ctypes.Array) else bodies)]
+    arrays += [np.ascontiguousarray(a) for a in (motions, props) if a is not None]
+    for a, struct in zip(arrays, (Body, BodyMotion, BodyProps)):
+        assert a.dtype.itemsize == ctypes.sizeof(struct) and a.shape[0] == arrays[0].shape[0]
+    pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
+    out = np.empty((arrays[0].shape[0], floats), np.float32)
+    return [_ptr(a) for a in arrays] + [arrays[0].shape[0], _ptr(pr), pr.shape[0]], out
+
+
 class Ocean:
     """One handle of the C ABI (a device, a resolution, `cascades` independent grids)."""
 
@@ -377,7 +398,7 @@ class Ocean:
             self._check(self.lib.datum_ocean_set_stream(self.h, P(stream_ptr), 0))
 
     def bind_maps(self, device_ptr, nbytes):
-        self._check(self.lib.datum_ocean_bind_maps(self.h, P(device_ptr) if device_ptr else None, nbytes))
+        self._check(self.lib.datum_ocean_bind_maps(self.h, _dev(device_ptr), nbytes))
 
     def maps_device(self):
         p = P()
@@ -464,11 +485,11 @@ class Ocean:
     def farm_result(self, slot, stream_ptr=None):
         """(device pointer, bytes) of the slot's gathered block; `stream_ptr` (None: the handle's stream) waits for the collective."""
         p, n = P(), ctypes.c_size_t()
-        self._check(self.lib.datum_ocean_farm_result(self.h, slot, P(stream_ptr) if stream_ptr else None, 1 if stream_ptr is None else 0, ctypes.byref(p), ctypes.byref(n)))
+        self._check(self.lib.datum_ocean_farm_result(self.h, slot, _dev(stream_ptr), 1 if stream_ptr is None else 0, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
 
     def farm_release(self, slot, stream_ptr=None):
-        self._check(self.lib.datum_ocean_farm_release(self.h, slot, P(stream_ptr) if stream_ptr else None, 1 if stream_ptr is None else 0))
+        self._check(self.lib.datum_ocean_farm_release(self.h, slot, _dev(stream_ptr), 1 if stream_ptr is None else 0))
 
     def farm_query(self, slot):
         rc = self.lib.datum_ocean_farm_query(self.h, slot)
@@ -634,7 +655,7 @@ class Ocean:
 
     def bind_foam(self, device_ptr, nbytes):
         """caller-owned device memory (cascades * N * N * 4 bytes) becomes the foam plane; None / 0 restores the handle's own"""
-        self._check(self.lib.datum_ocean_bind_foam(self.h, P(device_ptr) if device_ptr else None, nbytes))
+        self._check(self.lib.datum_ocean_bind_foam(self.h, _dev(device_ptr), nbytes))
 
     def foam_device(self):
         """(device pointer, bytes) of the foam plane in use"""
@@ -653,8 +674,7 @@ class Ocean:
     def sample_surface(self, cascade, oceanset, points_ptr, count, samples_ptr, iterations=4):
         """Enqueue the query of `count` float2 world points (device pointer, 8-byte aligned) into `count` records of 8 floats (device
         pointer, 16-byte aligned): surface point (x, y, height), residual, unit normal, foam.  `oceanset` as for gen()."""
-        self._check(self.lib.datum_ocean_sample_surface(self.h, cascade, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
-                                                        count, P(samples_ptr) if samples_ptr else None))
+        self._check(self.lib.datum_ocean_sample_surface(self.h, cascade, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(samples_ptr)))
 
     def read_surface(self, cascade, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
@@ -678,8 +698,7 @@ class Ocean:
     def sample_surface_blend(self, cascades, oceanset, points_ptr, count, samples_ptr, iterations=4):
         """sample_surface() of the sum of the listed cascades: device pointers, enqueued on the handle's stream"""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_sample_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
-                                                              count, P(samples_ptr) if samples_ptr else None))
+        self._check(self.lib.datum_ocean_sample_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(samples_ptr)))
 
     def read_surface_blend(self, cascades, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
@@ -699,7 +718,7 @@ class Ocean:
 
     def bind_velocity(self, device_ptr, nbytes):
         """caller-owned device memory (cascades * N * N * 16 bytes) becomes the velocity plane; None / 0 restores the handle's own"""
-        self._check(self.lib.datum_ocean_bind_velocity(self.h, P(device_ptr) if device_ptr else None, nbytes))
+        self._check(self.lib.datum_ocean_bind_velocity(self.h, _dev(device_ptr), nbytes))
 
     def velocity_device(self):
         """(device pointer, bytes) of the velocity plane in use"""
@@ -717,8 +736,7 @@ class Ocean:
     def sample_velocity_blend(self, cascades, oceanset, points_ptr, count, out_ptr, iterations=4):
         """sample_surface_blend()'s solve, then the listed cascades' velocity planes at the same texels: device pointers, enqueued"""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_sample_velocity_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
-                                                               count, P(out_ptr) if out_ptr else None))
+        self._check(self.lib.datum_ocean_sample_velocity_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(out_ptr)))
 
     def read_velocity_blend(self, cascades, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32: V(b), residual, velocity, 0"""
@@ -734,17 +752,13 @@ class Ocean:
         """Enqueue the reduction of `nbodies` bodies (device pointer, 64 bytes each) over `nprobes` probes (device pointer, 16 bytes each:
         x, y, z, weight) into `nbodies` records of 8 floats (device pointer): Fz, tau x, tau y, wet, sum m n, max residual."""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_reduce_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None, nbodies,
-                                                       P(probes_ptr) if probes_ptr else None, nprobes, P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_reduce_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(bodies_ptr), nbodies, _dev(probes_ptr), nprobes, _dev(records_ptr)))
 
     def read_bodies(self, cascades, oceanset, bodies, probes, iterations=4):
         """the same from host arrays, blocking: `bodies` an array of BODY_DTYPE (or of Body), `probes` (n, 4) float32; returns (nbodies, 8)"""
         arr, n = self._list(cascades)
-        b = np.ascontiguousarray(np.frombuffer(bytes(bodies), BODY_DTYPE) if isinstance(bodies, ctypes.Array) else bodies)
-        assert b.dtype.itemsize == ctypes.sizeof(Body)
-        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
-        out = np.empty((b.shape[0], BODY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
+        args, out = _body_batch(bodies, None, None, probes, BODY_RECORD_FLOATS)
+        self._check(self.lib.datum_ocean_read_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, _ptr(out)))
         return out
 
     # -- body drag (datum_ocean_reduce_body_drag): per-body force and torque from the water's velocity relative to the hull ----------------
@@ -754,20 +768,15 @@ class Ocean:
         `nprobes` probes (device pointer, 16 bytes each) into `nbodies` records of 8 floats (device pointer): Fx, Fy, Fz, tau x, tau y,
         tau z, sum m, max residual.  Needs velocity on and a displace since."""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_reduce_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
-                                                          P(motions_ptr) if motions_ptr else None, nbodies, P(probes_ptr) if probes_ptr else None, nprobes,
-                                                          P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_reduce_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(bodies_ptr), _dev(motions_ptr), nbodies,
+                                                          _dev(probes_ptr), nprobes, _dev(records_ptr)))
 
     def read_body_drag(self, cascades, oceanset, bodies, motions, probes, iterations=4):
         """the same from host arrays, blocking: `bodies` an array of BODY_DTYPE, `motions` one of BODY_MOTION_DTYPE of the same length,
         `probes` (n, 4) float32; returns (nbodies, 8)"""
         arr, n = self._list(cascades)
-        b = np.ascontiguousarray(bodies)
-        mo = np.ascontiguousarray(motions)
-        assert b.dtype.itemsize == ctypes.sizeof(Body) and mo.dtype.itemsize == ctypes.sizeof(BodyMotion) and mo.shape[0] == b.shape[0]
-        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
-        out = np.empty((b.shape[0], DRAG_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), _ptr(mo), b.shape[0], _ptr(pr), pr.shape[0], _ptr(out)))
+        args, out = _body_batch(bodies, motions, None, probes, DRAG_RECORD_FLOATS)
+        self._check(self.lib.datum_ocean_read_body_drag(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, _ptr(out)))
         return out
 
     # -- body stepping (datum_ocean_step_bodies): buoyancy, drag and a semi-implicit Euler integrator per body, on the device -------------
@@ -777,23 +786,15 @@ class Ocean:
         (32 bytes each, read and written) and props (32 bytes each) over `nprobes` probes (16 bytes each) into `nbodies` records of 8 floats:
         Fx, Fy, Fz, tau x, tau y, tau z, sum m of the last sub-step, max residual.  Needs velocity on and a displace since."""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_step_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
-                                                     P(motions_ptr) if motions_ptr else None, P(props_ptr) if props_ptr else None, nbodies,
-                                                     P(probes_ptr) if probes_ptr else None, nprobes, dt, substeps, P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_step_bodies(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(bodies_ptr), _dev(motions_ptr), _dev(props_ptr), nbodies,
+                                                     _dev(probes_ptr), nprobes, dt, substeps, _dev(records_ptr)))
 
     def step_bodies_host(self, cascades, oceanset, bodies, motions, props, probes, dt, substeps=1, iterations=4):
         """the same from host arrays, blocking: `bodies` an array of BODY_DTYPE and `motions` one of BODY_MOTION_DTYPE, both contiguous and
         advanced IN PLACE, `props` one of BODY_PROPS_DTYPE of the same length, `probes` (n, 4) float32; returns the (nbodies, 8) records"""
         arr, n = self._list(cascades)
-        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
-        assert bodies.flags.writeable and motions.flags.writeable
-        pp = np.ascontiguousarray(props)
-        assert bodies.dtype.itemsize == ctypes.sizeof(Body) and motions.dtype.itemsize == ctypes.sizeof(BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(BodyProps)
-        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
-        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
-        out = np.empty((bodies.shape[0], STEP_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_step_bodies_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(bodies), _ptr(motions), _ptr(pp), bodies.shape[0],
-                                                          _ptr(pr), pr.shape[0], dt, substeps, _ptr(out)))
+        args, out = _body_batch(bodies, motions, props, probes, STEP_RECORD_FLOATS, in_place=True)
+        self._check(self.lib.datum_ocean_step_bodies_host(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, dt, substeps, _ptr(out)))
         return out
 
     # -- the ripple layer (datum_ocean_set_ripples): a local, scrolling wave grid fed by impulses and by the bodies' wakes ---------------
@@ -833,15 +834,14 @@ class Ocean:
 
     def deposit_ripples(self, impulses_ptr, n):
         """Enqueue `n` deposits (device pointer, 16 bytes each: x, y, volume in m^3, 0)."""
-        self._check(self.lib.datum_ocean_deposit_ripples(self.h, P(impulses_ptr) if impulses_ptr else None, n))
+        self._check(self.lib.datum_ocean_deposit_ripples(self.h, _dev(impulses_ptr), n))
 
     def deposit_body_ripples(self, cascades, oceanset, bodies_ptr, motions_ptr, nbodies, probes_ptr, nprobes, dt, records_ptr, iterations=4):
         """Enqueue the wake of `nbodies` bodies over dt: reduce_body_drag's arguments; records of 8 floats: sum Vh, sum m sx, sum m sy,
         dropped quanta, 0, 0, sum m, max residual.  Needs velocity on and a displace since."""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_deposit_body_ripples(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
-                                                              P(motions_ptr) if motions_ptr else None, nbodies, P(probes_ptr) if probes_ptr else None, nprobes,
-                                                              dt, P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_deposit_body_ripples(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(bodies_ptr), _dev(motions_ptr), nbodies,
+                                                              _dev(probes_ptr), nprobes, dt, _dev(records_ptr)))
 
     def deposit_ripples_host(self, impulses):
         """the same from a host array, blocking: `impulses` (n, 4) float32"""
@@ -852,17 +852,13 @@ class Ocean:
         """the wake from host arrays, blocking: `bodies` an array of BODY_DTYPE, `motions` one of BODY_MOTION_DTYPE of the same length,
         `probes` (n, 4) float32; returns (nbodies, 8)"""
         arr, n = self._list(cascades)
-        b = np.ascontiguousarray(bodies)
-        mo = np.ascontiguousarray(motions)
-        assert b.dtype.itemsize == ctypes.sizeof(Body) and mo.dtype.itemsize == ctypes.sizeof(BodyMotion) and mo.shape[0] == b.shape[0]
-        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
-        out = np.empty((b.shape[0], RIPPLE_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_deposit_body_ripples_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(b), _ptr(mo), b.shape[0], _ptr(pr), pr.shape[0], dt, _ptr(out)))
+        args, out = _body_batch(bodies, motions, None, probes, RIPPLE_RECORD_FLOATS)
+        self._check(self.lib.datum_ocean_deposit_body_ripples_host(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, dt, _ptr(out)))
         return out
 
     def sample_ripples(self, points_ptr, n, out_ptr):
         """Enqueue the sample of `n` points (device pointer, 8 bytes each) into `n` float4 (device pointer): height, d/dx, d/dy, rate."""
-        self._check(self.lib.datum_ocean_sample_ripples(self.h, P(points_ptr) if points_ptr else None, n, P(out_ptr) if out_ptr else None))
+        self._check(self.lib.datum_ocean_sample_ripples(self.h, _dev(points_ptr), n, _dev(out_ptr)))
 
     def query_ripples(self, points):
         """the same from a host array, blocking: `points` (n, 2) float32; returns (n, 4) float32"""
@@ -879,23 +875,15 @@ class Ocean:
         dropped quanta of all sub-steps.  Each sub-step the bodies feel the layer's height and rate and deposit their wake, then the layer
         steps.  Needs velocity on, a displace since, and the layer on."""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_step_bodies_coupled(self.h, arr, n, ctypes.byref(oceanset), iterations, P(bodies_ptr) if bodies_ptr else None,
-                                                             P(motions_ptr) if motions_ptr else None, P(props_ptr) if props_ptr else None, nbodies,
-                                                             P(probes_ptr) if probes_ptr else None, nprobes, dt, substeps, P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_step_bodies_coupled(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(bodies_ptr), _dev(motions_ptr), _dev(props_ptr),
+                                                             nbodies, _dev(probes_ptr), nprobes, dt, substeps, _dev(records_ptr)))
 
     def step_bodies_coupled_host(self, cascades, oceanset, bodies, motions, props, probes, dt, substeps=1, iterations=4):
         """the same from host arrays, blocking: `bodies` and `motions` as step_bodies_host takes them, advanced IN PLACE; returns the
         (nbodies, 12) records"""
         arr, n = self._list(cascades)
-        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
-        assert bodies.flags.writeable and motions.flags.writeable
-        pp = np.ascontiguousarray(props)
-        assert bodies.dtype.itemsize == ctypes.sizeof(Body) and motions.dtype.itemsize == ctypes.sizeof(BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(BodyProps)
-        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
-        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, BODY_PROBE_FLOATS)
-        out = np.empty((bodies.shape[0], COUPLED_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_step_bodies_coupled_host(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(bodies), _ptr(motions), _ptr(pp), bodies.shape[0],
-                                                                  _ptr(pr), pr.shape[0], dt, substeps, _ptr(out)))
+        args, out = _body_batch(bodies, motions, props, probes, COUPLED_RECORD_FLOATS, in_place=True)
+        self._check(self.lib.datum_ocean_step_bodies_coupled_host(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, dt, substeps, _ptr(out)))
         return out
 
     # -- rippled reads (datum_ocean_gen_blend_rippled): the mesh, the query and the cast with the ripple layer's height and slopes on top -----
@@ -908,8 +896,7 @@ class Ocean:
     def sample_surface_blend_rippled(self, cascades, oceanset, points_ptr, count, samples_ptr, iterations=4):
         """sample_surface_blend() with the layer sampled at the asked point: device pointers, enqueued on the handle's stream"""
         arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_sample_surface_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), iterations, P(points_ptr) if points_ptr else None,
-                                                                      count, P(samples_ptr) if samples_ptr else None))
+        self._check(self.lib.datum_ocean_sample_surface_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(samples_ptr)))
 
     def read_surface_blend_rippled(self, cascades, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
@@ -922,8 +909,7 @@ class Ocean:
     def cast_rays_rippled(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
         """cast_rays() on the rippled water: every height of the search and the record at hi carry the layer"""
         arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, P(rays_ptr) if rays_ptr else None, n,
-                                                           P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_cast_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
 
     def read_rays_rippled(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
@@ -939,8 +925,7 @@ class Ocean:
         """Enqueue the cast of `n` rays (device pointer, 32 bytes each: ox, oy, oz, tmin, dx, dy, dz, tmax) into `n` records of 12 floats
         (device pointer): hi, lo, g(hi), status (0 miss, 1 enter, 2 leave) and the surface record at hi."""
         arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, P(rays_ptr) if rays_ptr else None, n,
-                                                   P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_cast_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
 
     def read_rays(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
@@ -981,8 +966,7 @@ class Ocean:
         """cast_rays with the samples outside the slab decided without a height evaluation: the same records bit for bit.  Needs current
         bounds (reduce_bounds after the last displace or bind_maps), else OceanError(ESTATE)."""
         arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, P(rays_ptr) if rays_ptr else None, n,
-                                                           P(records_ptr) if records_ptr else None))
+        self._check(self.lib.datum_ocean_cast_rays_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
 
     def read_rays_bounded(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""

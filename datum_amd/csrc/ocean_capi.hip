@@ -2309,54 +2309,61 @@ int datum_ocean_read_surface(datum_ocean_t ctx, int cascade, datum_ocean_set con
 
 namespace
 {
+  // a query as the caller gave it: the listed cascades, the set and the solve's iterations (0 where a call has none: the mesh calls and
+  // surface_slab, which check the list alone)
+  struct Query { int const *cascades; int count; datum_ocean_set const *set; int iterations; };
+
+  // a body call's arrays as the caller gave them, device or host alike; motions and props are null where the call takes none
+  struct BodyBatch { void const *bodies, *motions, *props; size_t nbodies; void const *probes; size_t nprobes; void *records; };
+
   // the list's checks, shared by every entry point that takes one; `name` goes into the error text
-  int check_blend_list(datum_ocean_ctx *ctx, int const *cascades, int count, char const *name)
+  int check_blend_list(datum_ocean_ctx *ctx, Query const &q, char const *name)
   {
     std::string const what = name;
 
     if (!ctx)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle").c_str());
 
-    if (!cascades)
+    if (!q.cascades)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null cascade list").c_str());
 
-    if (count < 1 || count > DATUM_OCEAN_MAX_CASCADES)
+    if (q.count < 1 || q.count > DATUM_OCEAN_MAX_CASCADES)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": count outside [1, DATUM_OCEAN_MAX_CASCADES]").c_str());
 
-    for(int i = 0; i < count; ++i)
-      if (cascades[i] < 0 || cascades[i] >= ctx->cascades)
+    for(int i = 0; i < q.count; ++i)
+      if (q.cascades[i] < 0 || q.cascades[i] >= ctx->cascades)
         return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
 
     return DATUM_OCEAN_OK;
   }
 
   // what every query on the summed surface checks first: the handle and the list, the set, the iterations
-  int check_query(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, char const *name)
+  int check_query(datum_ocean_ctx *ctx, Query const &q, char const *name)
   {
-    int rc = check_blend_list(ctx, cascades, count, name);
+    int rc = check_blend_list(ctx, q, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
 
-    if (!set)
+    if (!q.set)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
 
-    if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
+    if (q.iterations < 0 || q.iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
 
     return DATUM_OCEAN_OK;
   }
 
-  BlendList blend_list(datum_ocean_ctx *ctx, int const *cascades, int count)
+  BlendList blend_list(datum_ocean_ctx *ctx, Query const &q)
   {
     BlendList l = {};
-    l.count = count;
+    l.count = q.count;
     l.foammode = ctx->foammode;
 
-    for(int i = 0; i < count; ++i)
+    for(int i = 0; i < q.count; ++i)
     {
-      int const c = cascades[i];
+      int const c = q.cascades[i];
 
       l.casc[i].map = reinterpret_cast<float4 const*>(map_block(ctx, c));
       l.casc[i].foam = (ctx->foammode != DATUM_OCEAN_FOAM_OFF) ? ctx->foam.get() + (size_t)c * plane(ctx) : nullptr;
@@ -2367,32 +2374,32 @@ namespace
   }
 
   // (the frame is the launch's: query_frame)
-  QueryArgs query_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations)
+  QueryArgs query_args(datum_ocean_ctx *ctx, Query const &q)
   {
-    QueryArgs q = {};
-    q.set = *set;
-    q.list = blend_list(ctx, cascades, count);
-    q.N = ctx->N;
-    q.iterations = iterations;
-    return q;
+    QueryArgs a = {};
+    a.set = *q.set;
+    a.list = blend_list(ctx, q);
+    a.N = ctx->N;
+    a.iterations = q.iterations;
+    return a;
   }
 
-  int check_surface_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void const *samples, char const *name)
+  int check_surface_blend_args(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void const *samples, char const *name)
   {
-    int rc = check_query(ctx, cascades, count, set, iterations, name);
+    int rc = check_query(ctx, q, name);
 
     return rc != DATUM_OCEAN_OK ? rc : check_points(ctx, points, n, samples, name);
   }
 
   // what the several-cascade mesh calls check; `name` goes into the error text
-  int check_gen_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void const *vertices, char const *name)
+  int check_gen_blend_args(datum_ocean_ctx *ctx, Query const &q, int sizex, int sizey, void const *vertices, char const *name)
   {
     std::string const what = name;
 
-    if (!ctx || !set || !vertices)
+    if (!ctx || !q.set || !vertices)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null argument").c_str());
 
-    int rc = check_blend_list(ctx, cascades, count, name);
+    int rc = check_blend_list(ctx, q, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
@@ -2406,20 +2413,20 @@ namespace
   }
 
   // (the shape is the launch's: gen_shape)
-  GenBlendArgs gen_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, void *vertices)
+  GenBlendArgs gen_blend_args(datum_ocean_ctx *ctx, Query const &q, void *vertices)
   {
     GenBlendArgs b;
-    b.g.set = *set;
+    b.g.set = *q.set;
     b.g.map = nullptr;
     b.g.vertices = (float*)vertices;
-    b.list = blend_list(ctx, cascades, count);
+    b.list = blend_list(ctx, q);
     return b;
   }
 
-  SurfaceBlendArgs surface_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  SurfaceBlendArgs surface_blend_args(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples)
   {
     SurfaceBlendArgs b;
-    b.q = query_args(ctx, cascades, count, set, iterations);
+    b.q = query_args(ctx, q);
     b.points = static_cast<float2 const*>(points);
     b.samples = static_cast<float4*>(samples);
     b.count = (int)n;
@@ -2427,9 +2434,9 @@ namespace
   }
 
   // device arrays, n > 0
-  int run_surface_blend(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  int run_surface_blend(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples)
   {
-    SurfaceBlendArgs b = surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples);
+    SurfaceBlendArgs b = surface_blend_args(ctx, q, points, n, samples);
 
     HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
 
@@ -2442,13 +2449,14 @@ extern "C"
 
 int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
 {
-  int rc = check_gen_blend_args(ctx, cascades, count, set, sizex, sizey, vertices_device, "datum_ocean_gen_blend");
+  Query const q = { cascades, count, set, 0 };
+  int rc = check_gen_blend_args(ctx, q, sizex, sizey, vertices_device, "datum_ocean_gen_blend");
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  GenBlendArgs b = gen_blend_args(ctx, cascades, count, set, vertices_device);
+  GenBlendArgs b = gen_blend_args(ctx, q, vertices_device);
 
   HIPCHECK(ctx, launch_gen_blend(b, ctx->N, sizex, sizey, ctx->stream));
 
@@ -2457,24 +2465,26 @@ int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, dat
 
 int datum_ocean_sample_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
 {
-  int rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points_device, n, samples_device, "datum_ocean_sample_surface_blend");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_surface_blend_args(ctx, q, points_device, n, samples_device, "datum_ocean_sample_surface_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_surface_blend(ctx, cascades, count, set, iterations, points_device, n, samples_device);
+  return run_surface_blend(ctx, q, points_device, n, samples_device);
 }
 
 int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
 {
-  int rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples, "datum_ocean_read_surface_blend");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_surface_blend_args(ctx, q, points, n, samples, "datum_ocean_read_surface_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend(ctx, cascades, count, set, iterations, in, n, out); });
+  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend(ctx, q, in, n, out); });
 }
 
 }   // extern "C"
@@ -2498,24 +2508,30 @@ namespace
   }
 
   // the several-cascade query's checks, then the state both velocity queries need
-  int check_velocity_blend_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void const *out, char const *name)
+  int check_velocity_blend_args(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void const *out, char const *name)
   {
-    int rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points, n, out, name);
+    int rc = check_surface_blend_args(ctx, q, points, n, out, name);
 
     return rc != DATUM_OCEAN_OK ? rc : check_velocity_state(ctx, name);
   }
 
+  // the velocity planes of a query's list, in list order (the entries past the list stay as the caller zeroed them)
+  void velocity_planes(datum_ocean_ctx *ctx, Query const &q, float4 const **vel)
+  {
+    for(int i = 0; i < q.count; ++i)
+      vel[i] = ctx->velocity.get() + (size_t)q.cascades[i] * plane(ctx);
+  }
+
   // device arrays, n > 0
-  int run_velocity_blend(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *out)
+  int run_velocity_blend(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *out)
   {
     VelocityBlendArgs vb = {};
-    vb.q = query_args(ctx, cascades, count, set, iterations);
+    vb.q = query_args(ctx, q);
     vb.points = static_cast<float2 const*>(points);
     vb.samples = static_cast<float4*>(out);
     vb.count = (int)n;
 
-    for(int i = 0; i < count; ++i)
-      vb.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+    velocity_planes(ctx, q, vb.vel);
 
     HIPCHECK(ctx, launch_velocity_blend(vb, ctx->stream));
 
@@ -2639,24 +2655,26 @@ int datum_ocean_read_velocity(datum_ocean_t ctx, int cascade, float *vel)
 
 int datum_ocean_sample_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *out_device)
 {
-  int rc = check_velocity_blend_args(ctx, cascades, count, set, iterations, points_device, n, out_device, "datum_ocean_sample_velocity_blend");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_velocity_blend_args(ctx, q, points_device, n, out_device, "datum_ocean_sample_velocity_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_velocity_blend(ctx, cascades, count, set, iterations, points_device, n, out_device);
+  return run_velocity_blend(ctx, q, points_device, n, out_device);
 }
 
 int datum_ocean_read_velocity_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *out)
 {
-  int rc = check_velocity_blend_args(ctx, cascades, count, set, iterations, points, n, out, "datum_ocean_read_velocity_blend");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_velocity_blend_args(ctx, q, points, n, out, "datum_ocean_read_velocity_blend");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return read_points(ctx, points, n, out, [&](void const *in, void *dev) { return run_velocity_blend(ctx, cascades, count, set, iterations, in, n, dev); });
+  return read_points(ctx, points, n, out, [&](void const *in, void *dev) { return run_velocity_blend(ctx, q, in, n, dev); });
 }
 
 }   // extern "C"
@@ -2666,40 +2684,100 @@ int datum_ocean_read_velocity_blend(datum_ocean_t ctx, int const *cascades, int 
 namespace
 {
   // the checks both entry points share; `name` goes into the error text
-  int check_body_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
-                      void const *probes, size_t nprobes, void const *records, char const *name)
+  int check_body_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, char const *name)
   {
-    int rc = check_query(ctx, cascades, count, set, iterations, name);
+    int rc = check_query(ctx, q, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
 
-    if ((nbodies > 0 && (!bodies || !records)) || (nprobes > 0 && !probes))
+    if ((b.nbodies > 0 && (!b.bodies || !b.records)) || (b.nprobes > 0 && !b.probes))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null bodies, probes or records").c_str());
 
-    if (((uintptr_t)bodies & 15) || ((uintptr_t)probes & 15) || ((uintptr_t)records & 15))
+    if (((uintptr_t)b.bodies & 15) || ((uintptr_t)b.probes & 15) || ((uintptr_t)b.records & 15))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": bodies, probes and records must be 16-byte aligned").c_str());
 
-    if (nbodies > (size_t)INT32_MAX || nprobes > (size_t)INT32_MAX)
+    if (b.nbodies > (size_t)INT32_MAX || b.nprobes > (size_t)INT32_MAX)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": nbodies or nprobes above INT32_MAX").c_str());
 
     return DATUM_OCEAN_OK;
   }
 
+  // a body kernel's share of its arguments from a query and a device batch, filled in place (the struct is large); the drag, wake, step
+  // and couple fillers add their own fields beside it
+  void fill_body_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, BodyArgs &a)
+  {
+    a.q = query_args(ctx, q);
+    a.bodies = static_cast<datum_ocean_body const*>(b.bodies);
+    a.probes = static_cast<BodyProbe const*>(b.probes);
+    a.records = static_cast<float4*>(b.records);
+    a.nbodies = (int)b.nbodies;
+    a.nprobes = (int)b.nprobes;
+  }
+
   // device arrays, nbodies > 0
-  int run_bodies(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, size_t nbodies,
-                 void const *probes, size_t nprobes, void *records)
+  int run_bodies(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b)
   {
     BodyArgs a;
-    a.q = query_args(ctx, cascades, count, set, iterations);
-    a.bodies = static_cast<datum_ocean_body const*>(bodies);
-    a.probes = static_cast<BodyProbe const*>(probes);
-    a.records = static_cast<float4*>(records);
-    a.nbodies = (int)nbodies;
-    a.nprobes = (int)nprobes;
+    fill_body_args(ctx, q, b, a);
 
     HIPCHECK(ctx, launch_bodies(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // a host twin of a body call behind its checks, first half: the device made current, the staging of each array the batch has (one per
+  // array: STAGE_*) and of its records, `recordfloats` floats per body, each grown on its own, then the arrays copied in on the handle's
+  // stream (an empty one is not); `dev` is the batch as the family's run_* takes it
+  int stage_batch(datum_ocean_ctx *ctx, BodyBatch const &host, size_t recordfloats, BodyBatch &dev)
+  {
+    int const stage[4] = { STAGE_BODIES, STAGE_MOTIONS, STAGE_PROPS, STAGE_PROBES };
+    void const *const src[4] = { host.bodies, host.motions, host.props, host.probes };
+    size_t const bytes[4] = { host.nbodies * sizeof(datum_ocean_body), host.nbodies * sizeof(datum_ocean_body_motion),
+                              host.nbodies * sizeof(datum_ocean_body_props), host.nprobes * sizeof(BodyProbe) };
+    void *ptr[4] = {};
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    int rc = ctx->staging[STAGE_BODY_RECORDS].reserve(ctx, host.nbodies * recordfloats * sizeof(float));
+
+    for(int i = 0; i < 4 && rc == DATUM_OCEAN_OK; ++i)
+      if (src[i])
+        rc = ctx->staging[stage[i]].reserve(ctx, bytes[i]);
+
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    for(int i = 0; i < 4; ++i)
+    {
+      if (src[i])
+        ptr[i] = ctx->staging[stage[i]].ptr;
+
+      if (src[i] && bytes[i] > 0)
+        HIPCHECK(ctx, hipMemcpyAsync(ptr[i], src[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
+    }
+
+    dev = BodyBatch{ ptr[0], ptr[1], ptr[2], host.nbodies, ptr[3], host.nprobes, ctx->staging[STAGE_BODY_RECORDS].ptr };
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // ... second half, after the launches: the records -- and of a step (`stepped`) the bodies and motions it advanced -- copied back to the
+  // caller's arrays and waited for; no body, no copy
+  int fetch_batch(datum_ocean_ctx *ctx, BodyBatch const &host, BodyBatch const &dev, size_t recordfloats, bool stepped)
+  {
+    if (host.nbodies > 0 && stepped)
+    {
+      // (a step's entry points take both arrays writable)
+      HIPCHECK(ctx, hipMemcpyAsync(const_cast<void*>(host.bodies), dev.bodies, host.nbodies * sizeof(datum_ocean_body), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHECK(ctx, hipMemcpyAsync(const_cast<void*>(host.motions), dev.motions, host.nbodies * sizeof(datum_ocean_body_motion), hipMemcpyDeviceToHost, ctx->stream));
+    }
+
+    if (host.nbodies > 0)
+      HIPCHECK(ctx, hipMemcpyAsync(host.records, dev.records, host.nbodies * recordfloats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
     return DATUM_OCEAN_OK;
   }
@@ -2711,36 +2789,34 @@ extern "C"
 int datum_ocean_reduce_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                               void const *bodies_device, size_t nbodies, void const *probes_device, size_t nprobes, void *records_device)
 {
-  int rc = check_body_args(ctx, cascades, count, set, iterations, bodies_device, nbodies, probes_device, nprobes, records_device, "datum_ocean_reduce_bodies");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const b = { bodies_device, nullptr, nullptr, nbodies, probes_device, nprobes, records_device };
+
+  int rc = check_body_args(ctx, q, b, "datum_ocean_reduce_bodies");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_bodies(ctx, cascades, count, set, iterations, bodies_device, nbodies, probes_device, nprobes, records_device);
+  return run_bodies(ctx, q, b);
 }
 
 int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                             datum_ocean_body const *bodies, size_t nbodies, float const *probes, size_t nprobes, float *records)
 {
-  int rc = check_body_args(ctx, cascades, count, set, iterations, bodies, nbodies, probes, nprobes, records, "datum_ocean_read_bodies");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const host = { bodies, nullptr, nullptr, nbodies, probes, nprobes, records };
+  BodyBatch dev;
+
+  int rc = check_body_args(ctx, q, host, "datum_ocean_read_bodies");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  rc = stage_batch(ctx, host, DATUM_OCEAN_BODY_RECORD_FLOATS, dev);
+  if (rc == DATUM_OCEAN_OK)
+    rc = run_bodies(ctx, q, dev);
 
-  // the probes beside the bodies: a staging of their own, grown on its own
-  Staging &dprobes = ctx->staging[STAGE_PROBES];
-
-  rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  if (nprobes > 0)
-    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
-
-  return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
-                     [&](void const *in, void *out) { return run_bodies(ctx, cascades, count, set, iterations, in, nbodies, dprobes.ptr, nprobes, out); });
+  return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_BODY_RECORD_FLOATS, false);
 }
 
 }   // extern "C"
@@ -2750,39 +2826,36 @@ int datum_ocean_read_bodies(datum_ocean_t ctx, int const *cascades, int count, d
 namespace
 {
   // the body calls' checks with the motions beside the bodies, then the state the velocity queries need; `name` goes into the error text
-  int check_body_drag_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
-                           size_t nbodies, void const *probes, size_t nprobes, void const *records, char const *name)
+  int check_body_drag_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, char const *name)
   {
-    int rc = check_body_args(ctx, cascades, count, set, iterations, bodies, nbodies, probes, nprobes, records, name);
+    int rc = check_body_args(ctx, q, b, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
 
-    if (nbodies > 0 && !motions)
+    if (b.nbodies > 0 && !b.motions)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null motions").c_str());
 
-    if ((uintptr_t)motions & 15)
+    if ((uintptr_t)b.motions & 15)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": motions must be 16-byte aligned").c_str());
 
     return check_velocity_state(ctx, name);
   }
 
+  // body buoyancy's share, the motions and the list's velocity planes: what the drag, wake, step and couple kernels all read
+  void fill_drag_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, DragArgs &d)
+  {
+    fill_body_args(ctx, q, b, d.b);
+    d.motions = static_cast<datum_ocean_body_motion const*>(b.motions);
+    velocity_planes(ctx, q, d.vel);
+  }
+
   // device arrays, nbodies > 0
-  int run_body_drag(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
-                    size_t nbodies, void const *probes, size_t nprobes, void *records)
+  int run_body_drag(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b)
   {
     DragArgs a = {};
-    a.b.q = query_args(ctx, cascades, count, set, iterations);
-    a.b.bodies = static_cast<datum_ocean_body const*>(bodies);
-    a.b.probes = static_cast<BodyProbe const*>(probes);
-    a.b.records = static_cast<float4*>(records);
-    a.b.nbodies = (int)nbodies;
-    a.b.nprobes = (int)nprobes;
-    a.motions = static_cast<datum_ocean_body_motion const*>(motions);
-
-    for(int i = 0; i < count; ++i)
-      a.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
+    fill_drag_args(ctx, q, b, a);
 
     HIPCHECK(ctx, launch_body_drag(a, ctx->stream));
 
@@ -2797,42 +2870,35 @@ int datum_ocean_reduce_body_drag(datum_ocean_t ctx, int const *cascades, int cou
                                  void const *bodies_device, void const *motions_device, size_t nbodies, void const *probes_device, size_t nprobes,
                                  void *records_device)
 {
-  int rc = check_body_drag_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, records_device, "datum_ocean_reduce_body_drag");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const b = { bodies_device, motions_device, nullptr, nbodies, probes_device, nprobes, records_device };
+
+  int rc = check_body_drag_args(ctx, q, b, "datum_ocean_reduce_body_drag");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_body_drag(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, records_device);
+  return run_body_drag(ctx, q, b);
 }
 
 int datum_ocean_read_body_drag(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
                                float *records)
 {
-  int rc = check_body_drag_args(ctx, cascades, count, set, iterations, bodies, motions, nbodies, probes, nprobes, records, "datum_ocean_read_body_drag");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const host = { bodies, motions, nullptr, nbodies, probes, nprobes, records };
+  BodyBatch dev;
+
+  int rc = check_body_drag_args(ctx, q, host, "datum_ocean_read_body_drag");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  // the probes and the motions beside the bodies: the body calls' staging, and one for the motions, each grown on its own
-  Staging &dprobes = ctx->staging[STAGE_PROBES];
-  Staging &dmotions = ctx->staging[STAGE_MOTIONS];
-
-  rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
+  rc = stage_batch(ctx, host, DATUM_OCEAN_DRAG_RECORD_FLOATS, dev);
   if (rc == DATUM_OCEAN_OK)
-    rc = dmotions.reserve(ctx, nbodies * sizeof(datum_ocean_body_motion));
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
+    rc = run_body_drag(ctx, q, dev);
 
-  if (nprobes > 0)
-    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
-
-  HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, nbodies * sizeof(datum_ocean_body_motion), hipMemcpyHostToDevice, ctx->stream));
-
-  return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
-                     [&](void const *in, void *out) { return run_body_drag(ctx, cascades, count, set, iterations, in, dmotions.ptr, nbodies, dprobes.ptr, nprobes, out); });
+  return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_DRAG_RECORD_FLOATS, false);
 }
 
 }   // extern "C"
@@ -2842,20 +2908,19 @@ int datum_ocean_read_body_drag(datum_ocean_t ctx, int const *cascades, int count
 namespace
 {
   // body drag's checks with the props beside the motions, then the step's own two numbers; `name` goes into the error text
-  int check_step_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
-                      void const *props, size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void const *records, char const *name)
+  int check_step_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, int substeps, char const *name)
   {
     // (the state last: ESTATE exactly where body drag returns it, EINVAL first as there)
-    int rc = check_body_args(ctx, cascades, count, set, iterations, bodies, nbodies, probes, nprobes, records, name);
+    int rc = check_body_args(ctx, q, b, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
 
-    if (nbodies > 0 && (!motions || !props))
+    if (b.nbodies > 0 && (!b.motions || !b.props))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null motions or props").c_str());
 
-    if (((uintptr_t)motions & 15) || ((uintptr_t)props & 15))
+    if (((uintptr_t)b.motions & 15) || ((uintptr_t)b.props & 15))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": motions and props must be 16-byte aligned").c_str());
 
     if (substeps < 1 || substeps > DATUM_OCEAN_STEP_MAX_SUBSTEPS)
@@ -2867,27 +2932,23 @@ namespace
     return check_velocity_state(ctx, name);
   }
 
+  // a sub-step's length as every stepping call rounds it, once, on the host: two fp32 operations, the reciprocal and then the product (as
+  // the ray cast's inv), never dt / substeps
+  float substep_length(float dt, int substeps)
+  {
+    float const inv = 1.0f / (float)substeps;
+    return dt * inv;
+  }
+
   // device arrays, nbodies > 0
-  int run_step_bodies(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void *bodies, void *motions, void const *props,
-                      size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void *records)
+  int run_step_bodies(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, int substeps)
   {
     BodyStepArgs a = {};
-    a.d.b.q = query_args(ctx, cascades, count, set, iterations);
-    a.d.b.bodies = a.bodies = static_cast<datum_ocean_body*>(bodies);
-    a.d.b.probes = static_cast<BodyProbe const*>(probes);
-    a.d.b.records = static_cast<float4*>(records);
-    a.d.b.nbodies = (int)nbodies;
-    a.d.b.nprobes = (int)nprobes;
-    a.d.motions = a.motions = static_cast<datum_ocean_body_motion*>(motions);
-    a.props = static_cast<datum_ocean_body_props const*>(props);
-
-    for(int i = 0; i < count; ++i)
-      a.d.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
-
-    // the sub-step's length, rounded once here (two fp32 operations: the reciprocal, the product), as the ray cast's inv
-    float const inv = 1.0f / (float)substeps;
-
-    a.h = dt * inv;
+    fill_drag_args(ctx, q, b, a.d);
+    a.bodies = const_cast<datum_ocean_body*>(a.d.b.bodies);             // (the step's entry points take both writable)
+    a.motions = const_cast<datum_ocean_body_motion*>(a.d.motions);
+    a.props = static_cast<datum_ocean_body_props const*>(b.props);
+    a.h = substep_length(dt, substeps);
     a.substeps = substeps;
 
     HIPCHECK(ctx, launch_step_bodies(a, ctx->stream));
@@ -2903,61 +2964,36 @@ int datum_ocean_step_bodies(datum_ocean_t ctx, int const *cascades, int count, d
                             void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
                             float dt, int substeps, void *records_device)
 {
-  int rc = check_step_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device, "datum_ocean_step_bodies");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const b = { bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, records_device };
+
+  int rc = check_step_args(ctx, q, b, dt, substeps, "datum_ocean_step_bodies");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_step_bodies(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device);
+  return run_step_bodies(ctx, q, b, dt, substeps);
 }
 
 int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                  datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
                                  float const *probes, size_t nprobes, float dt, int substeps, float *records)
 {
-  int rc = check_step_args(ctx, cascades, count, set, iterations, bodies, motions, props, nbodies, probes, nprobes, dt, substeps, records, "datum_ocean_step_bodies_host");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const host = { bodies, motions, props, nbodies, probes, nprobes, records };
+  BodyBatch dev;
+
+  int rc = check_step_args(ctx, q, host, dt, substeps, "datum_ocean_step_bodies_host");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  // read_body_drag's staging and one more for the props, each grown on its own; bodies and motions come back beside the records
-  Staging &dbodies = ctx->staging[STAGE_BODIES], &dmotions = ctx->staging[STAGE_MOTIONS], &dprops = ctx->staging[STAGE_PROPS];
-  Staging &dprobes = ctx->staging[STAGE_PROBES], &drecords = ctx->staging[STAGE_BODY_RECORDS];
-
-  size_t const bodybytes = nbodies * sizeof(datum_ocean_body), motionbytes = nbodies * sizeof(datum_ocean_body_motion);
-  size_t const recordbytes = nbodies * DATUM_OCEAN_STEP_RECORD_FLOATS * sizeof(float);
-
-  rc = dbodies.reserve(ctx, bodybytes);
+  // bodies and motions come back beside the records
+  rc = stage_batch(ctx, host, DATUM_OCEAN_STEP_RECORD_FLOATS, dev);
   if (rc == DATUM_OCEAN_OK)
-    rc = dmotions.reserve(ctx, motionbytes);
-  if (rc == DATUM_OCEAN_OK)
-    rc = dprops.reserve(ctx, nbodies * sizeof(datum_ocean_body_props));
-  if (rc == DATUM_OCEAN_OK)
-    rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
-  if (rc == DATUM_OCEAN_OK)
-    rc = drecords.reserve(ctx, recordbytes);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
+    rc = run_step_bodies(ctx, q, dev, dt, substeps);
 
-  HIPCHECK(ctx, hipMemcpyAsync(dbodies.ptr, bodies, bodybytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, motionbytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(dprops.ptr, props, nbodies * sizeof(datum_ocean_body_props), hipMemcpyHostToDevice, ctx->stream));
-
-  if (nprobes > 0)
-    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
-
-  rc = run_step_bodies(ctx, cascades, count, set, iterations, dbodies.ptr, dmotions.ptr, dprops.ptr, nbodies, dprobes.ptr, nprobes, dt, substeps, drecords.ptr);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  HIPCHECK(ctx, hipMemcpyAsync(bodies, dbodies.ptr, bodybytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(motions, dmotions.ptr, motionbytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipMemcpyAsync(records, drecords.ptr, recordbytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_STEP_RECORD_FLOATS, true);
 }
 
 }   // extern "C"
@@ -3068,8 +3104,7 @@ namespace
   }
 
   // the layer, dt, then body drag's checks: ESTATE exactly where that call returns it once the layer is on
-  int check_ripple_wake_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
-                             size_t nbodies, void const *probes, size_t nprobes, float dt, void const *records, char const *name)
+  int check_ripple_wake_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, char const *name)
   {
     int rc = check_ripples(ctx, name);
     if (rc != DATUM_OCEAN_OK)
@@ -3078,25 +3113,14 @@ namespace
     if (!std::isfinite(dt))
       return fail(ctx, DATUM_OCEAN_EINVAL, (std::string(name) + ": dt is not finite").c_str());
 
-    return check_body_drag_args(ctx, cascades, count, set, iterations, bodies, motions, nbodies, probes, nprobes, records, name);
+    return check_body_drag_args(ctx, q, b, name);
   }
 
   // device arrays, nbodies > 0
-  int run_ripple_wake(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
-                      size_t nbodies, void const *probes, size_t nprobes, float dt, void *records)
+  int run_ripple_wake(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt)
   {
     RippleWakeArgs a = {};
-    a.d.b.q = query_args(ctx, cascades, count, set, iterations);
-    a.d.b.bodies = static_cast<datum_ocean_body const*>(bodies);
-    a.d.b.probes = static_cast<BodyProbe const*>(probes);
-    a.d.b.records = static_cast<float4*>(records);
-    a.d.b.nbodies = (int)nbodies;
-    a.d.b.nprobes = (int)nprobes;
-    a.d.motions = static_cast<datum_ocean_body_motion const*>(motions);
-
-    for(int i = 0; i < count; ++i)
-      a.d.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
-
+    fill_drag_args(ctx, q, b, a.d);
     a.src = ctx->ripplesrc;
     a.g = ripple_grid(ctx);
     a.dt = dt;
@@ -3344,9 +3368,7 @@ int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps)
   if (!std::isfinite(dt) || dt < 0.0f)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripples: dt is not finite or is negative");
 
-  // the sub-step's length, rounded once here (two fp32 operations: the reciprocal, the product), as datum_ocean_step_bodies has it
-  float const inv = 1.0f / (float)substeps;
-  float const h = dt * inv;
+  float const h = substep_length(dt, substeps);
 
   // the scheme's stability bound is c h / s <= 1 / sqrt 2
   if (ripple_courant(ctx, h) > 0.7)
@@ -3414,42 +3436,35 @@ int datum_ocean_deposit_body_ripples(datum_ocean_t ctx, int const *cascades, int
                                      void const *bodies_device, void const *motions_device, size_t nbodies, void const *probes_device, size_t nprobes,
                                      float dt, void *records_device)
 {
-  int rc = check_ripple_wake_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, dt, records_device, "datum_ocean_deposit_body_ripples");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const b = { bodies_device, motions_device, nullptr, nbodies, probes_device, nprobes, records_device };
+
+  int rc = check_ripple_wake_args(ctx, q, b, dt, "datum_ocean_deposit_body_ripples");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_ripple_wake(ctx, cascades, count, set, iterations, bodies_device, motions_device, nbodies, probes_device, nprobes, dt, records_device);
+  return run_ripple_wake(ctx, q, b, dt);
 }
 
 int datum_ocean_deposit_body_ripples_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                           datum_ocean_body const *bodies, datum_ocean_body_motion const *motions, size_t nbodies, float const *probes, size_t nprobes,
                                           float dt, float *records)
 {
-  int rc = check_ripple_wake_args(ctx, cascades, count, set, iterations, bodies, motions, nbodies, probes, nprobes, dt, records, "datum_ocean_deposit_body_ripples_host");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const host = { bodies, motions, nullptr, nbodies, probes, nprobes, records };
+  BodyBatch dev;
+
+  int rc = check_ripple_wake_args(ctx, q, host, dt, "datum_ocean_deposit_body_ripples_host");
   if (rc != DATUM_OCEAN_OK || nbodies == 0)
     return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  // read_body_drag's staging: the probes and the motions beside the bodies, each grown on its own
-  Staging &dprobes = ctx->staging[STAGE_PROBES];
-  Staging &dmotions = ctx->staging[STAGE_MOTIONS];
-
-  rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
+  rc = stage_batch(ctx, host, DATUM_OCEAN_RIPPLE_RECORD_FLOATS, dev);
   if (rc == DATUM_OCEAN_OK)
-    rc = dmotions.reserve(ctx, nbodies * sizeof(datum_ocean_body_motion));
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
+    rc = run_ripple_wake(ctx, q, dev, dt);
 
-  if (nprobes > 0)
-    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
-
-  HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, nbodies * sizeof(datum_ocean_body_motion), hipMemcpyHostToDevice, ctx->stream));
-
-  return read_staged(ctx, ctx->staging[STAGE_BODIES], bodies, nbodies * sizeof(datum_ocean_body), ctx->staging[STAGE_BODY_RECORDS], records, nbodies * 2 * sizeof(float4),
-                     [&](void const *in, void *out) { return run_ripple_wake(ctx, cascades, count, set, iterations, in, dmotions.ptr, nbodies, dprobes.ptr, nprobes, dt, out); });
+  return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_RIPPLE_RECORD_FLOATS, false);
 }
 
 int datum_ocean_sample_ripples(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device)
@@ -3482,10 +3497,9 @@ int datum_ocean_query_ripples(datum_ocean_t ctx, float const *points, size_t n, 
 namespace
 {
   // the checks the four entry points share; `name` goes into the error text
-  int check_ray_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-                     void const *rays, size_t n, void const *records, char const *name)
+  int check_ray_args(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void const *records, char const *name)
   {
-    int rc = check_query(ctx, cascades, count, set, iterations, name);
+    int rc = check_query(ctx, q, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
@@ -3522,11 +3536,10 @@ namespace
   }
 
   // device arrays, n > 0
-  int run_rays(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-               void const *rays, size_t n, void *records)
+  int run_rays(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
   {
     RayArgs a;
-    a.q = query_args(ctx, cascades, count, set, iterations);
+    a.q = query_args(ctx, q);
     a.r = ray_batch(steps, refine, rays, n, records);
 
     HIPCHECK(ctx, launch_rays(a, ctx->stream));
@@ -3548,25 +3561,27 @@ extern "C"
 int datum_ocean_cast_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                           void const *rays_device, size_t n, void *records_device)
 {
-  int rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_ray_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_rays(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
+  return run_rays(ctx, q, steps, refine, rays_device, n, records_device);
 }
 
 int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                           float const *rays, size_t n, float *records)
 {
-  int rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, "datum_ocean_read_rays");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_ray_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays(ctx, q, steps, refine, in, n, out); });
 }
 
 }   // extern "C"
@@ -3616,10 +3631,9 @@ namespace
   }
 
   // cast_rays' checks, then the state both bounded entry points need
-  int check_ray_bounded_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-                             void const *rays, size_t n, void const *records, char const *name)
+  int check_ray_bounded_args(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void const *records, char const *name)
   {
-    int rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, name);
+    int rc = check_ray_args(ctx, q, steps, refine, rays, n, records, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
@@ -3630,16 +3644,15 @@ namespace
   }
 
   // device arrays, n > 0
-  int run_rays_bounded(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-                       void const *rays, size_t n, void *records)
+  int run_rays_bounded(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
   {
     RayBoundedArgs a;
-    a.q = query_args(ctx, cascades, count, set, iterations);
+    a.q = query_args(ctx, q);
     a.r = ray_batch(steps, refine, rays, n, records);
     a.bounds = reinterpret_cast<float const*>(ctx->bounds);
 
     for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
-      a.cascades[c] = (c < count) ? cascades[c] : 0;
+      a.cascades[c] = (c < q.count) ? q.cascades[c] : 0;
 
     HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
 
@@ -3691,7 +3704,8 @@ int datum_ocean_read_bounds(datum_ocean_t ctx, float *records)
 
 int datum_ocean_surface_slab(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, float *zlo, float *zhi, float *reachx, float *reachy)
 {
-  int rc = check_blend_list(ctx, cascades, count, "datum_ocean_surface_slab");
+  Query const q = { cascades, count, set, 0 };
+  int rc = check_blend_list(ctx, q, "datum_ocean_surface_slab");
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -3719,25 +3733,27 @@ int datum_ocean_surface_slab(datum_ocean_t ctx, int const *cascades, int count, 
 int datum_ocean_cast_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   void const *rays_device, size_t n, void *records_device)
 {
-  int rc = check_ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_bounded");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_ray_bounded_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_bounded");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_rays_bounded(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
+  return run_rays_bounded(ctx, q, steps, refine, rays_device, n, records_device);
 }
 
 int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   float const *rays, size_t n, float *records)
 {
-  int rc = check_ray_bounded_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, "datum_ocean_read_rays_bounded");
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_ray_bounded_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays_bounded");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_bounded(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_bounded(ctx, q, steps, refine, in, n, out); });
 }
 
 }   // extern "C"
@@ -3748,8 +3764,7 @@ namespace
 {
   // the layer and the ripple step's rule for dt, then body stepping's checks (ESTATE exactly where body drag returns it once the layer is
   // on), then the ripple step's stability bound for the sub-step; `name` goes into the error text
-  int check_coupled_args(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *bodies, void const *motions,
-                         void const *props, size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void const *records, char const *name)
+  int check_coupled_args(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, int substeps, char const *name)
   {
     int rc = check_ripples(ctx, name);
     if (rc != DATUM_OCEAN_OK)
@@ -3760,39 +3775,26 @@ namespace
     if (!std::isfinite(dt) || dt < 0.0f)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt is not finite or is negative").c_str());
 
-    rc = check_step_args(ctx, cascades, count, set, iterations, bodies, motions, props, nbodies, probes, nprobes, dt, substeps, records, name);
+    rc = check_step_args(ctx, q, b, dt, substeps, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    float const inv = 1.0f / (float)substeps;
-
-    if (ripple_courant(ctx, dt * inv) > 0.7)
+    if (ripple_courant(ctx, substep_length(dt, substeps)) > 0.7)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": c * dt / (substeps * s) above 0.7, the ripple step's stability bound with a margin").c_str());
 
     return DATUM_OCEAN_OK;
   }
 
   // device arrays; `substeps` rounds of: the bodies' coupled sub-step (nbodies > 0), then the layer's sub-step in its first form
-  int run_step_bodies_coupled(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void *bodies, void *motions,
-                              void const *props, size_t nbodies, void const *probes, size_t nprobes, float dt, int substeps, void *records)
+  int run_step_bodies_coupled(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, int substeps)
   {
-    // the sub-step's length, rounded once here (two fp32 operations: the reciprocal, the product), as both parent calls have it
-    float const inv = 1.0f / (float)substeps;
-    float const h = dt * inv;
+    float const h = substep_length(dt, substeps);
 
     CoupleArgs a = {};
-    a.d.b.q = query_args(ctx, cascades, count, set, iterations);
-    a.d.b.bodies = a.bodies = static_cast<datum_ocean_body*>(bodies);
-    a.d.b.probes = static_cast<BodyProbe const*>(probes);
-    a.d.b.records = static_cast<float4*>(records);
-    a.d.b.nbodies = (int)nbodies;
-    a.d.b.nprobes = (int)nprobes;
-    a.d.motions = a.motions = static_cast<datum_ocean_body_motion*>(motions);
-    a.props = static_cast<datum_ocean_body_props const*>(props);
-
-    for(int i = 0; i < count; ++i)
-      a.d.vel[i] = ctx->velocity.get() + (size_t)cascades[i] * plane(ctx);
-
+    fill_drag_args(ctx, q, b, a.d);
+    a.bodies = const_cast<datum_ocean_body*>(a.d.b.bodies);             // (writable, as the step's)
+    a.motions = const_cast<datum_ocean_body_motion*>(a.d.motions);
+    a.props = static_cast<datum_ocean_body_props const*>(b.props);
     a.src = ctx->ripplesrc;
     a.g = ripple_grid(ctx);
     a.h = h;
@@ -3801,7 +3803,7 @@ namespace
 
     for(int i = 0; i < substeps; ++i)
     {
-      if (nbodies > 0)
+      if (b.nbodies > 0)
       {
         a.state = ctx->ripplestate[ctx->ripplecurrent];
         a.first = i == 0;
@@ -3831,68 +3833,36 @@ int datum_ocean_step_bodies_coupled(datum_ocean_t ctx, int const *cascades, int 
                                     void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
                                     float dt, int substeps, void *records_device)
 {
-  int rc = check_coupled_args(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device, "datum_ocean_step_bodies_coupled");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const b = { bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, records_device };
+
+  int rc = check_coupled_args(ctx, q, b, dt, substeps, "datum_ocean_step_bodies_coupled");
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_step_bodies_coupled(ctx, cascades, count, set, iterations, bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, dt, substeps, records_device);
+  return run_step_bodies_coupled(ctx, q, b, dt, substeps);
 }
 
 int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                          datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
                                          float const *probes, size_t nprobes, float dt, int substeps, float *records)
 {
-  int rc = check_coupled_args(ctx, cascades, count, set, iterations, bodies, motions, props, nbodies, probes, nprobes, dt, substeps, records, "datum_ocean_step_bodies_coupled_host");
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const host = { bodies, motions, props, nbodies, probes, nprobes, records };
+  BodyBatch dev;
+
+  int rc = check_coupled_args(ctx, q, host, dt, substeps, "datum_ocean_step_bodies_coupled_host");
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  // step_bodies_host's staging, the records' grown to 48 bytes per body; bodies and motions come back beside the records
-  Staging &dbodies = ctx->staging[STAGE_BODIES], &dmotions = ctx->staging[STAGE_MOTIONS], &dprops = ctx->staging[STAGE_PROPS];
-  Staging &dprobes = ctx->staging[STAGE_PROBES], &drecords = ctx->staging[STAGE_BODY_RECORDS];
-
-  size_t const bodybytes = nbodies * sizeof(datum_ocean_body), motionbytes = nbodies * sizeof(datum_ocean_body_motion);
-  size_t const recordbytes = nbodies * DATUM_OCEAN_COUPLED_RECORD_FLOATS * sizeof(float);
-
-  rc = dbodies.reserve(ctx, bodybytes);
+  // (no body: nothing is staged or copied, and the layer still steps)
+  rc = stage_batch(ctx, host, DATUM_OCEAN_COUPLED_RECORD_FLOATS, dev);
   if (rc == DATUM_OCEAN_OK)
-    rc = dmotions.reserve(ctx, motionbytes);
-  if (rc == DATUM_OCEAN_OK)
-    rc = dprops.reserve(ctx, nbodies * sizeof(datum_ocean_body_props));
-  if (rc == DATUM_OCEAN_OK)
-    rc = dprobes.reserve(ctx, nprobes * sizeof(BodyProbe));
-  if (rc == DATUM_OCEAN_OK)
-    rc = drecords.reserve(ctx, recordbytes);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
+    rc = run_step_bodies_coupled(ctx, q, dev, dt, substeps);
 
-  if (nbodies > 0)
-  {
-    HIPCHECK(ctx, hipMemcpyAsync(dbodies.ptr, bodies, bodybytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(dmotions.ptr, motions, motionbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(dprops.ptr, props, nbodies * sizeof(datum_ocean_body_props), hipMemcpyHostToDevice, ctx->stream));
-  }
-
-  if (nprobes > 0)
-    HIPCHECK(ctx, hipMemcpyAsync(dprobes.ptr, probes, nprobes * sizeof(BodyProbe), hipMemcpyHostToDevice, ctx->stream));
-
-  rc = run_step_bodies_coupled(ctx, cascades, count, set, iterations, dbodies.ptr, dmotions.ptr, dprops.ptr, nbodies, dprobes.ptr, nprobes, dt, substeps, drecords.ptr);
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
-
-  if (nbodies > 0)
-  {
-    HIPCHECK(ctx, hipMemcpyAsync(bodies, dbodies.ptr, bodybytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(motions, dmotions.ptr, motionbytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(records, drecords.ptr, recordbytes, hipMemcpyDeviceToHost, ctx->stream));
-  }
-
-  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_COUPLED_RECORD_FLOATS, true);
 }
 
 }   // extern "C"
@@ -3911,10 +3881,10 @@ namespace
   }
 
   // device arrays, n > 0
-  int run_surface_blend_rippled(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points, size_t n, void *samples)
+  int run_surface_blend_rippled(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples)
   {
     SurfaceBlendRippledArgs r;
-    r.b = surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples);
+    r.b = surface_blend_args(ctx, q, points, n, samples);
     r.layer = rippled_layer(ctx);
 
     HIPCHECK(ctx, launch_surface_blend_rippled(r, ctx->stream));
@@ -3923,11 +3893,10 @@ namespace
   }
 
   // device arrays, n > 0
-  int run_rays_rippled(datum_ocean_ctx *ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
-                       void const *rays, size_t n, void *records)
+  int run_rays_rippled(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
   {
     RayRippledArgs r;
-    r.a.q = query_args(ctx, cascades, count, set, iterations);
+    r.a.q = query_args(ctx, q);
     r.a.r = ray_batch(steps, refine, rays, n, records);
     r.layer = rippled_layer(ctx);
 
@@ -3944,16 +3913,17 @@ extern "C"
 
 int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
 {
+  Query const q = { cascades, count, set, 0 };
   int rc = check_ripples(ctx, "datum_ocean_gen_blend_rippled");
   if (rc == DATUM_OCEAN_OK)
-    rc = check_gen_blend_args(ctx, cascades, count, set, sizex, sizey, vertices_device, "datum_ocean_gen_blend_rippled");
+    rc = check_gen_blend_args(ctx, q, sizex, sizey, vertices_device, "datum_ocean_gen_blend_rippled");
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   GenBlendRippledArgs r;
-  r.b = gen_blend_args(ctx, cascades, count, set, vertices_device);
+  r.b = gen_blend_args(ctx, q, vertices_device);
   r.layer = rippled_layer(ctx);
 
   HIPCHECK(ctx, launch_gen_blend_rippled(r, ctx->N, sizex, sizey, ctx->stream));
@@ -3963,56 +3933,60 @@ int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int co
 
 int datum_ocean_sample_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
 {
+  Query const q = { cascades, count, set, iterations };
   int rc = check_ripples(ctx, "datum_ocean_sample_surface_blend_rippled");
   if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points_device, n, samples_device, "datum_ocean_sample_surface_blend_rippled");
+    rc = check_surface_blend_args(ctx, q, points_device, n, samples_device, "datum_ocean_sample_surface_blend_rippled");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_surface_blend_rippled(ctx, cascades, count, set, iterations, points_device, n, samples_device);
+  return run_surface_blend_rippled(ctx, q, points_device, n, samples_device);
 }
 
 int datum_ocean_read_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
 {
+  Query const q = { cascades, count, set, iterations };
   int rc = check_ripples(ctx, "datum_ocean_read_surface_blend_rippled");
   if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_blend_args(ctx, cascades, count, set, iterations, points, n, samples, "datum_ocean_read_surface_blend_rippled");
+    rc = check_surface_blend_args(ctx, q, points, n, samples, "datum_ocean_read_surface_blend_rippled");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend_rippled(ctx, cascades, count, set, iterations, in, n, out); });
+  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend_rippled(ctx, q, in, n, out); });
 }
 
 int datum_ocean_cast_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   void const *rays_device, size_t n, void *records_device)
 {
+  Query const q = { cascades, count, set, iterations };
   int rc = check_ripples(ctx, "datum_ocean_cast_rays_rippled");
   if (rc == DATUM_OCEAN_OK)
-    rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_rippled");
+    rc = check_ray_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_rippled");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return run_rays_rippled(ctx, cascades, count, set, iterations, steps, refine, rays_device, n, records_device);
+  return run_rays_rippled(ctx, q, steps, refine, rays_device, n, records_device);
 }
 
 int datum_ocean_read_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   float const *rays, size_t n, float *records)
 {
+  Query const q = { cascades, count, set, iterations };
   int rc = check_ripples(ctx, "datum_ocean_read_rays_rippled");
   if (rc == DATUM_OCEAN_OK)
-    rc = check_ray_args(ctx, cascades, count, set, iterations, steps, refine, rays, n, records, "datum_ocean_read_rays_rippled");
+    rc = check_ray_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays_rippled");
   if (rc != DATUM_OCEAN_OK || n == 0)
     return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_rippled(ctx, cascades, count, set, iterations, steps, refine, in, n, out); });
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_rippled(ctx, q, steps, refine, in, n, out); });
 }
 
 }   // extern "C"

@@ -1,9 +1,16 @@
 """The host twins' device staging (ocean_capi.hip: Staging, read_staged): the six read_* queries of one handle, interleaved, with counts that
 grow, shrink and regrow every staging buffer and cross one 256-thread workgroup.  Each result is the same query's device-array twin on
-torch tensors, bit for bit."""
+torch tensors, bit for bit.  The five body host twins share one pair of helpers (stage_batch, fetch_batch): interleaved on one handle with
+stagings that grow, shrink and go to zero, each returns what the same call returns on a fresh handle, bit for bit."""
+
+import ctypes
 
 import numpy as np
 import pytest
+
+import body64
+import drag64
+import step64
 
 pytestmark = pytest.mark.gpu
 
@@ -12,6 +19,8 @@ N, LIST, ITERATIONS, STEPS, REFINE = 64, [0, 1], 4, 16, 4
 SCALES = (22.0, 64.0)
 COUNTS = (3, 300, 1, 700, 2)
 PROBES_PER_BODY = 3
+BODY_COUNTS, PROBE_COUNTS = (1, 3, 2, 0), (4, 16, 0, 8)
+R, CELL, DT, SUBSTEPS = 64, 0.5, F(1 / 60), 2
 
 
 def _bits(a):
@@ -111,3 +120,71 @@ def test_read_twins_interleaved_are_the_device_twins_bits():
             for name in want:
                 answers = got[name][:, 3] if name.startswith("rays") else got[name]          # (a ray's status)
                 assert np.isfinite(answers).all(), (n, name)
+
+
+def _body_ocean(capi):
+    """N = 64, one cascade, velocity on, one displace, the layer on and at rest: every handle made here holds the same state"""
+    oc = capi.Ocean(N, 1)
+    oc.set_cascade(0, SCALES[0], 1.0)
+    oc.upload_state(0, (np.random.RandomState(3).standard_normal((N, N, 2)) * (0.4 / N)).astype(F))
+    oc.set_velocity("on")
+    oc.update(DT)
+    oc.displace()
+    oc.set_ripples(R, CELL)
+    return oc
+
+
+def _batch(rs, nb, npr):
+    """nb bodies inside the layer's window that all walk the same npr probes, with their motions and props"""
+    pos = np.concatenate([rs.uniform(-8, 8, (nb, 2)), rs.uniform(-0.5, 0.5, (nb, 1))], 1)
+    bodies = body64.make_bodies([np.eye(3)] * nb, pos, [0] * nb, [npr] * nb, [2.0] * nb)
+    motions = drag64.make_motions(rs.uniform(-1, 1, (nb, 3)), rs.uniform(-0.3, 0.3, (nb, 3)), [1.0] * nb, [0.5] * nb)
+    props = step64.make_props(np.full(nb, 1e-3), np.full((nb, 3), 1e-3), 9.81, 9810.0)
+    probes = np.concatenate([rs.uniform(-1, 1, (npr, 3)), rs.uniform(0.1, 1.0, (npr, 1))], 1).astype(F)
+    return bodies, motions, props, probes
+
+
+def _body_calls(oc, s, batch):
+    """the five body host twins on `oc`, from the layer at rest with one impulse pending: all they return, the layer before and after"""
+    bodies, motions, props, probes = batch
+    oc.deposit_ripples_host([[1.0, 2.0, 0.05, 0.0]])
+    out = {"lift": oc.read_bodies([0], s, bodies, probes, ITERATIONS),
+           "drag": oc.read_body_drag([0], s, bodies, motions, probes, ITERATIONS),
+           "wake": oc.deposit_body_ripples_host([0], s, bodies, motions, probes, DT, ITERATIONS)}
+    for name, step in (("step", oc.step_bodies_host), ("coupled", oc.step_bodies_coupled_host)):
+        b, m = bodies.copy(), motions.copy()
+        out["before " + name] = oc.read_ripples()
+        out[name] = step([0], s, b, m, props, probes, DT, SUBSTEPS, ITERATIONS)
+        out[name + " bodies"], out[name + " motions"] = b.view(np.uint8), m.view(np.uint8)
+    out["after"] = oc.read_ripples()
+    return out
+
+
+def test_body_twins_interleaved_are_a_fresh_handles_bits():
+    from datum_amd import capi
+
+    capi.load()
+    rs = np.random.RandomState(11)
+    s = _set(capi)
+    with _body_ocean(capi) as oc:
+        for nb, npr in zip(BODY_COUNTS, PROBE_COUNTS):
+            batch = _batch(rs, nb, npr)
+            oc.reset_ripples()
+            got = _body_calls(oc, s, batch)
+            with _body_ocean(capi) as fresh:
+                want = _body_calls(fresh, s, batch)
+            for name in want:
+                assert got[name].shape == want[name].shape, (nb, npr, name)
+                assert np.array_equal(np.ascontiguousarray(got[name]).view(np.uint8), np.ascontiguousarray(want[name]).view(np.uint8)), (nb, npr, name)
+            for name in ("lift", "drag", "wake", "step", "coupled"):
+                assert got[name].shape[0] == nb and np.isfinite(got[name]).all(), (nb, npr, name)
+            # the coupled twin steps the layer, with bodies or without: the pending impulse is in the state after it, and not before
+            assert not got["before coupled"].any() and got["after"].any(), (nb, npr)
+            if nb > 0:
+                assert got["step bodies"].tobytes() != batch[0].tobytes() and got["coupled motions"].tobytes() != batch[1].tobytes(), (nb, npr)
+        # nbodies == 0 with arrays that are there: step_bodies_host returns before it stages or writes anything
+        b, m, p, pr = _batch(rs, 2, 4)
+        keep, rec = (b.tobytes(), m.tobytes()), np.full((2, 8), 7.0, F)
+        ptr = lambda a: a.ctypes.data_as(capi.P)
+        assert oc.lib.datum_ocean_step_bodies_host(oc.h, (capi.I * 1)(0), 1, ctypes.byref(s), ITERATIONS, ptr(b), ptr(m), ptr(p), 0, ptr(pr), 4, DT, SUBSTEPS, ptr(rec)) == 0
+        assert (b.tobytes(), m.tobytes()) == keep and np.all(rec == 7.0)

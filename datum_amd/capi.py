@@ -167,6 +167,12 @@ SYMBOLS = {
     "datum_ocean_read_surface_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_cast_rays_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_rays_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_reduce_ripple_bounds": (I, [P]),
+    "datum_ocean_ripple_bounds_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
+    "datum_ocean_read_ripple_bounds": (I, [P, P]),
+    "datum_ocean_surface_slab_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), P, P, P, P]),
+    "datum_ocean_cast_rays_rippled_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    "datum_ocean_read_rays_rippled_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
 }
 
 
@@ -270,6 +276,8 @@ RAY_MISS, RAY_ENTER, RAY_LEAVE = 0, 1, 2
 
 # surface bounds (datum_ocean_reduce_bounds, added at ABI 9): floats per cascade record (zmin, zmax, xmin, xmax, ymin, ymax, nonfinite, 0)
 BOUNDS_RECORD_FLOATS = 8
+# ripple-layer bounds (datum_ocean_reduce_ripple_bounds, added at ABI 9): etamin, etamax, ratemin, ratemax, nonfinite, active, 0, 0
+RIPPLE_BOUNDS_RECORD_FLOATS = 8
 
 
 def header_abi_version():
@@ -917,6 +925,48 @@ class Ocean:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
         out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
+        return out
+
+    # -- ripple-layer bounds (datum_ocean_reduce_ripple_bounds), the rippled slab and the rippled casts that skip the samples it decides -----
+
+    def reduce_ripple_bounds(self):
+        """Enqueue the reduction of the layer's current state to its record; the record is current until the next call that writes a state
+        buffer (step_ripples, step_bodies_coupled, a center_ripples that moves the window, reset_ripples, set_ripples)."""
+        self._check(self.lib.datum_ocean_reduce_ripple_bounds(self.h))
+
+    def ripple_bounds_device(self):
+        """(device pointer, bytes) of the layer's record, 32 bytes"""
+        p = P()
+        n = ctypes.c_size_t()
+        self._check(self.lib.datum_ocean_ripple_bounds_device(self.h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def read_ripple_bounds(self):
+        """reduce_ripple_bounds and a blocking read: (8,) float32 -- etamin, etamax, ratemin, ratemax, nonfinite, active, 0, 0"""
+        out = np.empty(RIPPLE_BOUNDS_RECORD_FLOATS, np.float32)
+        self._check(self.lib.datum_ocean_read_ripple_bounds(self.h, _ptr(out)))
+        return out
+
+    def surface_slab_rippled(self, cascades, oceanset):
+        """blocking: (zlo, zhi, reachx, reachy) of the listed cascades' summed surface with the ripple layer on top, as float32"""
+        arr, c = self._list(cascades)
+        out = np.zeros(4, np.float32)
+        base = out.ctypes.data
+        self._check(self.lib.datum_ocean_surface_slab_rippled(self.h, arr, c, ctypes.byref(oceanset), P(base), P(base + 4), P(base + 8), P(base + 12)))
+        return out[0], out[1], out[2], out[3]
+
+    def cast_rays_rippled_bounded(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
+        """cast_rays_rippled with the samples outside the rippled slab decided without a height evaluation: the same records bit for bit.
+        Needs current bounds of the maps (reduce_bounds) AND of the layer (reduce_ripple_bounds), else OceanError(ESTATE)."""
+        arr, c = self._list(cascades)
+        self._check(self.lib.datum_ocean_cast_rays_rippled_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
+
+    def read_rays_rippled_bounded(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
+        """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
+        arr, c = self._list(cascades)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
+        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_ocean_read_rays_rippled_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

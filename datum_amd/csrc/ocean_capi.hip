@@ -33,6 +33,7 @@
 #include "ocean_ripple.hip"
 #include "ocean_couple.hip"
 #include "ocean_rippled.hip"
+#include "ocean_ripple_bounds.hip"
 
 using namespace ocean;
 
@@ -162,6 +163,12 @@ struct datum_ocean_ctx
   int *ripplesrc = nullptr;           // pending deposits
   double ripplec = 2.0, ripplegamma = 0.05, ripplespongegamma = 4.0;   // datum_ocean_set_ripple_params
   int ripplesponge = 8;
+
+  // datum_ocean_reduce_ripple_bounds: one block, allocated by the first reduce after a set_ripples and freed with the layer, of a guard, the
+  // workgroups' partials, a guard, the layer's record and a guard, 32 bytes each but the partials: the guards are filled with 0xCD bytes
+  // once and never written again (a test reads them round the record's pointer)
+  float4 *rippleboundsblock = nullptr;
+  bool rippleboundscurrent = false;   // the record is that of the current state buffer: set by reduce_ripple_bounds, cleared by every call that writes a state buffer
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -1001,6 +1008,7 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->ripplestate[0]);
   (void)hipFree(ctx->ripplestate[1]);
   (void)hipFree(ctx->ripplesrc);
+  (void)hipFree(ctx->rippleboundsblock);
 
   for(Staging &st : ctx->staging)
     (void)hipFree(st.ptr);
@@ -3036,6 +3044,9 @@ namespace
     ctx->ripplestate[1] = nullptr;
     HIPCHECK(ctx, hipFree(ctx->ripplesrc));
     ctx->ripplesrc = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->rippleboundsblock));
+    ctx->rippleboundsblock = nullptr;
+    ctx->rippleboundscurrent = false;
     ctx->rippleR = 0;
 
     return DATUM_OCEAN_OK;
@@ -3045,6 +3056,8 @@ namespace
   int clear_ripples(datum_ocean_ctx *ctx)
   {
     size_t const cells = ripple_cells(ctx);
+
+    ctx->rippleboundscurrent = false;
 
     HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[0], 0, cells * sizeof(float2), ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[1], 0, cells * sizeof(float2), ctx->stream));
@@ -3281,6 +3294,8 @@ int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
   g.oy = oy;
   a.g = g;
 
+  ctx->rippleboundscurrent = false;
+
   HIPCHECK(ctx, launch_ripple_scroll(a, ctx->stream));
 
   ctx->rippleox = ox;
@@ -3377,6 +3392,8 @@ int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps)
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   RippleStepArgs a = ripple_step_args(ctx, h);
+
+  ctx->rippleboundscurrent = false;
 
   for(int i = 0; i < substeps; ++i)
   {
@@ -3800,6 +3817,8 @@ namespace
     a.h = h;
 
     RippleStepArgs r = ripple_step_args(ctx, h);
+
+    ctx->rippleboundscurrent = false;
 
     for(int i = 0; i < substeps; ++i)
     {
@@ -4714,3 +4733,209 @@ int datum_ocean_algorithmic_bytes(datum_ocean_t ctx, double *rowpass_bytes, doub
 }
 
 }
+
+/* -- bounds of the ripple layer, the rippled slab and the bounded rippled cast (ocean_ripple_bounds.hip) --------------------------------- */
+
+namespace
+{
+  // the block of datum_ocean_reduce_ripple_bounds in float4s: guard, partials, guard, record, guard (2 float4 = 32 bytes each but the partials)
+  constexpr size_t RIPPLE_BOUNDS_GUARD = 2;
+
+  float4 *ripple_bounds_partials(datum_ocean_ctx const *ctx) { return ctx->rippleboundsblock + RIPPLE_BOUNDS_GUARD; }
+
+  float4 *ripple_bounds_record(datum_ocean_ctx const *ctx)
+  {
+    return ripple_bounds_partials(ctx) + 2 * (size_t)ripple_bounds_groups(ctx->rippleR) + RIPPLE_BOUNDS_GUARD;
+  }
+
+  // the block, allocated by the first reduce after a set_ripples, and the two launches
+  int reduce_ripple_bounds(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    int const groups = ripple_bounds_groups(ctx->rippleR);
+
+    if (!ctx->rippleboundsblock)
+    {
+      size_t const bytes = (3 * RIPPLE_BOUNDS_GUARD + 2 * (size_t)groups + 2) * sizeof(float4);
+
+      float4 *block = nullptr;
+
+      HIPCHECK(ctx, hipMalloc(&block, bytes));
+
+      hipError_t const e = hipMemsetAsync(block, 0xCD, bytes, ctx->stream);
+
+      if (e != hipSuccess)
+      {
+        (void)hipFree(block);
+        return fail(ctx, (int)e, "datum_ocean_reduce_ripple_bounds: hipMemsetAsync");
+      }
+
+      ctx->rippleboundsblock = block;
+    }
+
+    RippleBoundsArgs a;
+    a.state = reinterpret_cast<float4 const*>(ctx->ripplestate[ctx->ripplecurrent]);
+    a.partials = ripple_bounds_partials(ctx);
+    a.record = ripple_bounds_record(ctx);
+    a.pairs = (int)(ripple_cells(ctx) / 2);
+    a.groups = groups;
+
+    HIPCHECK(ctx, launch_ripple_bounds(a, ctx->stream));
+
+    ctx->rippleboundscurrent = true;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // reduce, then a blocking read of the record
+  int read_ripple_bounds(datum_ocean_ctx *ctx, float *record)
+  {
+    int rc = reduce_ripple_bounds(ctx);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    HIPCHECK(ctx, hipMemcpyAsync(record, ripple_bounds_record(ctx), RIPPLE_BOUNDS_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the layer first, then the bounded cast's checks (cast_rays' and the maps' mark), then the layer's mark
+  int check_ray_rippled_bounded_args(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void const *records, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc == DATUM_OCEAN_OK)
+      rc = check_ray_bounded_args(ctx, q, steps, refine, rays, n, records, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    if (!ctx->rippleboundscurrent)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (std::string(name) + ": the ripple bounds are not current (datum_ocean_reduce_ripple_bounds after the last call that stepped, moved, reset or set the layer)").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // device arrays, n > 0
+  int run_rays_rippled_bounded(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
+  {
+    RayRippledBoundedArgs a;
+    a.r.a.q = query_args(ctx, q);
+    a.r.a.r = ray_batch(steps, refine, rays, n, records);
+    a.r.layer = rippled_layer(ctx);
+    a.bounds = reinterpret_cast<float const*>(ctx->bounds);
+    a.layerbounds = reinterpret_cast<float const*>(ripple_bounds_record(ctx));
+
+    for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
+      a.cascades[c] = (c < q.count) ? q.cascades[c] : 0;
+
+    HIPCHECK(ctx, launch_rays_rippled_bounded(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_reduce_ripple_bounds(datum_ocean_t ctx)
+{
+  int rc = check_ripples(ctx, "datum_ocean_reduce_ripple_bounds");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  return reduce_ripple_bounds(ctx);
+}
+
+int datum_ocean_ripple_bounds_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes)
+{
+  int rc = check_ripples(ctx, "datum_ocean_ripple_bounds_device");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!device_ptr)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_bounds_device: null argument");
+
+  if (!ctx->rippleboundsblock)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_ripple_bounds_device: no record yet (datum_ocean_reduce_ripple_bounds)");
+
+  *device_ptr = ripple_bounds_record(ctx);
+
+  if (bytes)
+    *bytes = RIPPLE_BOUNDS_BYTES;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_ripple_bounds(datum_ocean_t ctx, float *record)
+{
+  int rc = check_ripples(ctx, "datum_ocean_read_ripple_bounds");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!record)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_ripple_bounds: null argument");
+
+  return read_ripple_bounds(ctx, record);
+}
+
+int datum_ocean_surface_slab_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, float *zlo, float *zhi, float *reachx, float *reachy)
+{
+  Query const q = { cascades, count, set, 0 };
+  int rc = check_ripples(ctx, "datum_ocean_surface_slab_rippled");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_blend_list(ctx, q, "datum_ocean_surface_slab_rippled");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!set)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_surface_slab_rippled: null set");
+
+  float records[DATUM_OCEAN_MAX_CASCADES * BOUNDS_FIELDS];
+  float layer[RIPPLE_BOUNDS_FIELDS];
+
+  rc = datum_ocean_read_bounds(ctx, records);
+  if (rc == DATUM_OCEAN_OK)
+    rc = read_ripple_bounds(ctx, layer);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  GenFrame const f = make_gen_frame(*set, ctx->N, 2, 2);      // the camera's terms are not read
+
+  BoundsSlab const s = ripple_bounds_slab(records, cascades, count, f.basez, set->swellamplitude, f.gx, f.gy, layer);
+
+  if (zlo) *zlo = s.zlo;
+  if (zhi) *zhi = s.zhi;
+  if (reachx) *reachx = s.reachx;
+  if (reachy) *reachy = s.reachy;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_cast_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                          void const *rays_device, size_t n, void *records_device)
+{
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_ray_rippled_bounded_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_rippled_bounded");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_rays_rippled_bounded(ctx, q, steps, refine, rays_device, n, records_device);
+}
+
+int datum_ocean_read_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                          float const *rays, size_t n, float *records)
+{
+  Query const q = { cascades, count, set, iterations };
+  int rc = check_ray_rippled_bounded_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays_rippled_bounded");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_rippled_bounded(ctx, q, steps, refine, in, n, out); });
+}
+
+}   // extern "C"

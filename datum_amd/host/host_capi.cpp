@@ -531,6 +531,41 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  // extrema[4]: etamin, etamax, ratemin, ratemax; counts[2]: nonfinite, active
+  int datum_host_reduce_ocean_ripple_bounds(void *c, float *extrema, std::uint32_t *counts)
+  {
+    try
+    {
+      OceanRippleBounds const b = reduce_ocean_ripple_bounds(static_cast<HostContext*>(c)->context);
+      extrema[0] = b.etamin; extrema[1] = b.etamax; extrema[2] = b.ratemin; extrema[3] = b.ratemax;
+      counts[0] = b.nonfinite; counts[1] = b.active;
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  // slab[4]: zlo, zhi, reach.x, reach.y
+  int datum_host_ocean_surface_slab_rippled(void *c, void *p, float *slab)
+  {
+    try
+    {
+      OceanSurfaceSlab const s = ocean_surface_slab_rippled(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p));
+      slab[0] = s.zlo; slab[1] = s.zhi; slab[2] = s.reach.x; slab[3] = s.reach.y;
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_cast_ocean_rays_rippled_bounded(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
+  {
+    try
+    {
+      cast_ocean_rays_rippled_bounded(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

@@ -1126,6 +1126,60 @@ void cast_ocean_rays_bounded(OceanContext &context, OceanParams const &params, O
 }
 
 
+///////////////////////// reduce_ocean_ripple_bounds ////////////////////////
+OceanRippleBounds reduce_ocean_ripple_bounds(OceanContext &context)
+{
+  if (!context.ready)
+    throw runtime_error("reduce_ocean_ripple_bounds: the context is not prepared (prepare_ocean_context)");
+
+  float record[DATUM_OCEAN_RIPPLE_BOUNDS_RECORD_FLOATS];
+
+  check(context.hip, datum_ocean_read_ripple_bounds(context.hip, record), "datum_ocean_read_ripple_bounds");
+
+  OceanRippleBounds bounds;
+  bounds.etamin = record[0];
+  bounds.etamax = record[1];
+  bounds.ratemin = record[2];
+  bounds.ratemax = record[3];
+  bounds.nonfinite = (std::uint32_t)record[4];
+  bounds.active = (std::uint32_t)record[5];
+
+  return bounds;
+}
+
+
+///////////////////////// ocean_surface_slab_rippled ////////////////////////
+OceanSurfaceSlab ocean_surface_slab_rippled(OceanContext &context, OceanParams const &params)
+{
+  if (!context.ready)
+    throw runtime_error("ocean_surface_slab_rippled: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  OceanSurfaceSlab slab;
+
+  check(context.hip, datum_ocean_surface_slab_rippled(context.hip, &cascade, 1, &set, &slab.zlo, &slab.zhi, &slab.reach.x, &slab.reach.y), "datum_ocean_surface_slab_rippled");
+
+  return slab;
+}
+
+
+///////////////////////// cast_ocean_rays_rippled_bounded ///////////////////
+void cast_ocean_rays_rippled_bounded(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
+{
+  if (!context.ready)
+    throw runtime_error("cast_ocean_rays_rippled_bounded: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_read_rays_rippled_bounded(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays_rippled_bounded");
+}
+
+
 ///////////////////////// read_ocean_displacement ///////////////////////////
 void read_ocean_displacement(OceanContext &context, float *maps)
 {

@@ -534,6 +534,25 @@ void reduce_ocean_bounds(OceanContext &context);
 OceanSurfaceSlab ocean_surface_slab(OceanContext &context, OceanParams const &params);
 void cast_ocean_rays_bounded(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
 
+// ripple-layer bounds (include/datum_ocean_hip.h: datum_ocean_reduce_ripple_bounds, the definition there): the extrema of the ripple layer's
+// height and rate, the cells that are not finite and the cells that are not at rest (active == 0: the layer is at rest, and stepping it or
+// reading through it can be skipped); the slab of the rippled water, ocean_surface_slab with the layer on top; and cast_ocean_rays_rippled
+// with the samples outside that slab decided without a height evaluation -- the same records bit for bit.  reduce_ocean_ripple_bounds
+// reduces and blocks; ocean_surface_slab_rippled reduces both the displacement and the layer and blocks; cast_ocean_rays_rippled_bounded
+// throws unless both were reduced after the last call that displaced and the last that stepped, moved, reset or set the layer.  All three
+// throw before prepare_ocean_context, and while the layer is off (set_ocean_ripples)
+struct OceanRippleBounds
+{
+  float etamin, etamax;
+  float ratemin, ratemax;
+  std::uint32_t nonfinite;
+  std::uint32_t active;
+};
+
+OceanRippleBounds reduce_ocean_ripple_bounds(OceanContext &context);
+OceanSurfaceSlab ocean_surface_slab_rippled(OceanContext &context, OceanParams const &params);
+void cast_ocean_rays_rippled_bounded(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

@@ -6,6 +6,7 @@ OceanContext + initialise/prepare/render_ocean_surface over the HIP module.  No 
 
 import ctypes
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -15,6 +16,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBPATH = os.path.join(_HERE, "lib", "libdatum_ocean_host.so")
 
 F, I, P, U32 = ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32
+
+
+class OceanRippleBounds(NamedTuple):
+    """ocean.h's OceanRippleBounds"""
+    etamin: np.float32
+    etamax: np.float32
+    ratemin: np.float32
+    ratemax: np.float32
+    nonfinite: int
+    active: int
 
 
 class Scalars(ctypes.Structure):
@@ -117,7 +128,10 @@ def load():
             "datum_host_gen_ocean_surface_rippled": (I, [P, P, ctypes.POINTER(CameraDesc), P]),
             "datum_host_reduce_ocean_bounds": (I, [P]),
             "datum_host_ocean_surface_slab": (I, [P, P, P]),
+            "datum_host_reduce_ocean_ripple_bounds": (I, [P, P, P]),
+            "datum_host_ocean_surface_slab_rippled": (I, [P, P, P]),
             "datum_host_cast_ocean_rays_bounded": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
+            "datum_host_cast_ocean_rays_rippled_bounded": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -478,6 +492,26 @@ class OceanContext:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
         out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_cast_ocean_rays_bounded(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
+        return out
+
+    def reduce_ocean_ripple_bounds(self):
+        """reduce_ocean_ripple_bounds: the OceanRippleBounds of the layer's current state, blocking: etamin, etamax, ratemin, ratemax as
+        float32, nonfinite and active as integers (active == 0: the layer is at rest)"""
+        extrema, counts = np.zeros(4, np.float32), np.zeros(2, np.uint32)
+        self._check(self.lib.datum_host_reduce_ocean_ripple_bounds(self.c, extrema.ctypes.data_as(P), counts.ctypes.data_as(P)))
+        return OceanRippleBounds(*extrema, int(counts[0]), int(counts[1]))
+
+    def ocean_surface_slab_rippled(self, params):
+        """ocean_surface_slab_rippled: (zlo, zhi, reach.x, reach.y) of the water with the ripple layer on top, as float32, blocking"""
+        out = np.zeros(4, np.float32)
+        self._check(self.lib.datum_host_ocean_surface_slab_rippled(self.c, params.p, out.ctypes.data_as(P)))
+        return out[0], out[1], out[2], out[3]
+
+    def cast_ocean_rays_rippled_bounded(self, params, rays, iterations=4, steps=32, refine=8):
+        """cast_ocean_rays_rippled_bounded: cast_ocean_rays_rippled's arguments and records; raises unless both bounds are current"""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
+        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_cast_ocean_rays_rippled_bounded(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
         return out
 
     def read_vertices(self, mesh):

@@ -59,7 +59,9 @@ extern "C" {
  *      datum_ocean_deposit_body_ripples, datum_ocean_deposit_body_ripples_host, datum_ocean_sample_ripples and datum_ocean_query_ripples;
  *      then coupled stepping, datum_ocean_step_bodies_coupled and datum_ocean_step_bodies_coupled_host; then the rippled reads,
  *      datum_ocean_gen_blend_rippled, datum_ocean_sample_surface_blend_rippled, datum_ocean_read_surface_blend_rippled,
- *      datum_ocean_cast_rays_rippled and datum_ocean_read_rays_rippled.
+ *      datum_ocean_cast_rays_rippled and datum_ocean_read_rays_rippled; then the ripple layer's bounds, datum_ocean_reduce_ripple_bounds,
+ *      datum_ocean_ripple_bounds_device, datum_ocean_read_ripple_bounds and datum_ocean_surface_slab_rippled, with the bounded rippled
+ *      casts datum_ocean_cast_rays_rippled_bounded and datum_ocean_read_rays_rippled_bounded.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -973,9 +975,9 @@ int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades,
  * Each returns what its parent call returns for the same arguments, with its own name in the error text.  The layer is looked at first:
  * while it is off the call returns DATUM_OCEAN_ESTATE whatever its other arguments are (a null handle is DATUM_OCEAN_EINVAL).  n == 0
  * enqueues nothing.  A refused call enqueues nothing and changes nothing.
- * LEFT OUT: the bounded cast (its slab would need a bound on |η|) and a slab for the layer; the layer's rate in
- * datum_ocean_sample_velocity_blend; the layer in datum_ocean_reduce_bodies, datum_ocean_reduce_body_drag and datum_ocean_step_bodies
- * (datum_ocean_step_bodies_coupled is the call for that); foam from the layer; anything on the displace path. */
+ * LEFT OUT: the layer's rate in datum_ocean_sample_velocity_blend; the layer in datum_ocean_reduce_bodies,
+ * datum_ocean_reduce_body_drag and datum_ocean_step_bodies (datum_ocean_step_bodies_coupled is the call for that); foam from the layer;
+ * anything on the displace path. */
 int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device);
 int datum_ocean_sample_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                              void const *points_device, size_t n, void *samples_device);
@@ -985,6 +987,72 @@ int datum_ocean_cast_rays_rippled(datum_ocean_t ctx, int const *cascades, int co
                                   void const *rays_device, size_t n, void *records_device);
 int datum_ocean_read_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   float const *rays, size_t n, float *records);
+
+/* -- ripple-layer bounds, the rippled slab and the bounded rippled cast (added at ABI 9; nothing in the reference) -----------------------
+ * How high and how low does the ripple layer stand right now, and is it at rest?  For the rippled water's bounding box, near plane and
+ * culling slab, for the rippled cast's march samples far above the highest crest -- and for skipping datum_ocean_step_ripples and the
+ * rippled reads altogether over a layer at rest, without datum_ocean_read_ripples' 8 bytes per cell over the bus.
+ *
+ * One record of DATUM_OCEAN_RIPPLE_BOUNDS_RECORD_FLOATS = 8 floats (32 bytes):
+ *     0, 1   etamin, etamax     2, 3   ratemin, ratemax     4   nonfinite     5   active     6, 7   0
+ * over all R² cells of the layer's CURRENT state buffer (the one datum_ocean_ripples_device returns; pending deposits are not seen, as in
+ * datum_ocean_sample_ripples).  The extrema are combined with fminf / fmaxf from +inf / −inf: a NaN enters no extremum, an infinity
+ * does; they are exact and do not depend on the order of the reduction, but for the sign of a zero: compare them by value.  nonfinite is
+ * the number of cells with a non-finite η or rate, active the number of cells with η != 0 || rate != 0 (a NaN counts).  R² ≤ 2^20: both
+ * counts are exact.  active == 0 is the test for a layer at rest: stepping it changes nothing unless deposits are pending, and the
+ * rippled reads then give the parents' values.
+ *
+ * The rippled slab of a blend list under a set: the layer is one more entry behind the list.  It displaces nothing horizontally, and a
+ * point outside the window reads 0, so 0 always lies inside the layer's interval.  With mag, hi, lo the running sums of
+ * datum_ocean_surface_slab behind its loop over the list (before pad), each line one fp32 operation:
+ *
+ *     elo  = fminf(etamin, 0)                 ehi = fmaxf(etamax, 0)
+ *     mag  = mag + fmaxf(|elo|, |ehi|)        hi  = hi + ehi             lo = lo + elo
+ *     pad  = mag · 2^-16                      zhi = hi + pad             zlo = lo − pad          reach as in datum_ocean_surface_slab
+ *
+ * Every height datum_ocean_sample_surface_blend_rippled can give for that list, set and layer lies strictly between zlo and zhi: the
+ * parent's height lies inside the parent's un-padded sums up to the parent's stated roundings, the bilinear η exceeds its four cells'
+ * extrema by at most a few ulp of max |η|, the rippled height is one more rounded addition, and pad ≥ 128 ulp(mag) covers these.  If a
+ * listed cascade or the layer has nonfinite > 0, zlo = zhi = NaN: the slab then says nothing.  datum_ocean_surface_slab keeps its results.
+ *
+ * The bounded rippled cast is datum_ocean_cast_rays_rippled with datum_ocean_cast_rays_bounded's rule over the rippled slab:
+ *     below'(t) = point(t).z > zhi ? false : point(t).z < zlo ? true : below(t)
+ *
+ *   reduce_ripple_bounds       enqueue and return: two launches on the handle's stream.  The handle then holds the record and marks it
+ *                              CURRENT.  Every call that writes a state buffer clears that mark: datum_ocean_step_ripples,
+ *                              datum_ocean_step_bodies_coupled and its host twin, a datum_ocean_center_ripples that moves the window,
+ *                              datum_ocean_reset_ripples and datum_ocean_set_ripples.  The deposit calls (they write only the pending
+ *                              deposits), datum_ocean_set_ripple_params and every read leave it
+ *   ripple_bounds_device       the record on the device, 32 bytes, handle-owned (allocated by the first reduce after a set_ripples, freed
+ *                              with the layer); DATUM_OCEAN_ESTATE before that reduce.  Ordered on the handle's stream
+ *   read_ripple_bounds         reduce_ripple_bounds, then a blocking read of 8 floats
+ *   surface_slab_rippled       blocking: read_bounds and read_ripple_bounds (both marks are current afterwards), then the slab above on the
+ *                              host.  datum_ocean_surface_slab's arguments; any of the four outputs may be NULL
+ *   cast_rays_rippled_bounded, read_rays_rippled_bounded
+ *                              cast_rays_rippled's and read_rays_rippled's arguments, rules and DATUM_OCEAN_EINVAL cases.
+ *                              DATUM_OCEAN_ESTATE unless BOTH marks are current, the maps' (datum_ocean_reduce_bounds) and the layer's:
+ *                              a call that returns DATUM_OCEAN_OK has therefore written datum_ocean_cast_rays_rippled's records BIT FOR
+ *                              BIT, all twelve floats of every ray.  A caller who writes the layer's state through
+ *                              datum_ocean_ripples_device's pointer behind the module's back without a new reduce_ripple_bounds forfeits
+ *                              that guarantee, as one who writes into a bound map buffer does
+ * The layer is looked at first: while it is off every call here returns DATUM_OCEAN_ESTATE whatever its other arguments are (a null
+ * handle is DATUM_OCEAN_EINVAL).  A refused call enqueues nothing.
+ * When to use which: as for the bounded cast (datum_ocean_cast_rays_bounded), the bounded rippled cast gains where march samples lie
+ * outside the slab -- a camera fan from above, long rays through air or deep water.  Measured (DESIGN.md 5.23;
+ * tools/ripple_bounds_bench.py, 10^6 rays, 1024^2 maps, R = 1024, lists of 1 and 4): 0.58 of datum_ocean_cast_rays_rippled's time on
+ * the camera fan and 0.63-0.65 on the random set.  Rays that start and end inside the slab evaluate every sample either way and pay
+ * the comparisons and the slab on top: 1.001-1.006 on such a set, for which datum_ocean_cast_rays_rippled is the call to prefer.
+ * LEFT OUT: a single-launch reduction; bounds per tile of the window (a tighter slab over quiet water); a wave-uniform early-out in the
+ * rippled mesh. */
+#define DATUM_OCEAN_RIPPLE_BOUNDS_RECORD_FLOATS 8
+int datum_ocean_reduce_ripple_bounds(datum_ocean_t ctx);
+int datum_ocean_ripple_bounds_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes);
+int datum_ocean_read_ripple_bounds(datum_ocean_t ctx, float *record);
+int datum_ocean_surface_slab_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, float *zlo, float *zhi, float *reachx, float *reachy);
+int datum_ocean_cast_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                          void const *rays_device, size_t n, void *records_device);
+int datum_ocean_read_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
+                                          float const *rays, size_t n, float *records);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -173,6 +173,15 @@ SYMBOLS = {
     "datum_ocean_surface_slab_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), P, P, P, P]),
     "datum_ocean_cast_rays_rippled_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_rays_rippled_bounded": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, I, P, ctypes.c_size_t, P]),
+    # wake foam (added at ABI 9): a coverage plane beside the ripple layer
+    "datum_ocean_set_ripple_foam": (I, [P, I]),
+    "datum_ocean_set_ripple_foam_params": (I, [P, F, F, F, F, F]),
+    "datum_ocean_step_ripple_foam": (I, [P, F]),
+    "datum_ocean_reset_ripple_foam": (I, [P]),
+    "datum_ocean_ripple_foam_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(I), ctypes.POINTER(I)]),
+    "datum_ocean_read_ripple_foam": (I, [P, P]),
+    "datum_ocean_sample_ripple_foam": (I, [P, P, ctypes.c_size_t, P]),
+    "datum_ocean_query_ripple_foam": (I, [P, P, ctypes.c_size_t, P]),
 }
 
 
@@ -967,6 +976,49 @@ class Ocean:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
         out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_ocean_read_rays_rippled_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
+        return out
+
+    # -- wake foam (datum_ocean_set_ripple_foam): a coverage plane beside the ripple layer, fed by its slopes and rates --------------------
+
+    def set_ripple_foam(self, on=True):
+        """Allocate and zero the R x R coverage plane beside the ripple layer, or free it; OceanError(ESTATE) while the layer is off."""
+        self._check(self.lib.datum_ocean_set_ripple_foam(self.h, 1 if on else 0))
+
+    def set_ripple_foam_params(self, t1=0.04, k1=10.0, t2=0.5, k2=2.0, decay=0.5):
+        """threshold and gain of the slope-squared source, threshold (m/s) and gain of the rate source, decay (1/s); a gain of 0 switches
+        its source off.  The defaults are design choices, not measurements."""
+        self._check(self.lib.datum_ocean_set_ripple_foam_params(self.h, t1, k1, t2, k2, decay))
+
+    def step_ripple_foam(self, dt):
+        """Enqueue one update of the plane from the layer's current state: one launch; the old coverage fades by exp(-decay dt)."""
+        self._check(self.lib.datum_ocean_step_ripple_foam(self.h, dt))
+
+    def reset_ripple_foam(self):
+        self._check(self.lib.datum_ocean_reset_ripple_foam(self.h))
+
+    def ripple_foam_device(self):
+        """(device pointer of the plane, bytes, ox, oy); the pointer does not alternate"""
+        ptr, nbytes, ox, oy = P(), ctypes.c_size_t(), I(), I()
+        self._check(self.lib.datum_ocean_ripple_foam_device(self.h, ctypes.byref(ptr), ctypes.byref(nbytes), ctypes.byref(ox), ctypes.byref(oy)))
+        return ptr.value, nbytes.value, ox.value, oy.value
+
+    def read_ripple_foam(self):
+        """the plane in window order, (R, R) float32: [j][i] is cell (ox + i, oy + j); blocking"""
+        _, nbytes, _, _ = self.ripple_foam_device()
+        R = int(round((nbytes // 4) ** 0.5))
+        out = np.empty((R, R), np.float32)
+        self._check(self.lib.datum_ocean_read_ripple_foam(self.h, _ptr(out)))
+        return out
+
+    def sample_ripple_foam(self, points_ptr, n, out_ptr):
+        """Enqueue the sample of `n` points (device pointer, 8 bytes each) into `n` floats (device pointer): the bilinear coverage."""
+        self._check(self.lib.datum_ocean_sample_ripple_foam(self.h, _dev(points_ptr), n, _dev(out_ptr)))
+
+    def query_ripple_foam(self, points):
+        """the same from a host array, blocking: `points` (n, 2) float32; returns (n,) float32"""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty(p.shape[0], np.float32)
+        self._check(self.lib.datum_ocean_query_ripple_foam(self.h, _ptr(p), p.shape[0], _ptr(out)))
         return out
 
     # -- ray casts (datum_ocean_cast_rays): a fixed march and bisection per ray on the summed surface -----------------------------------

@@ -34,6 +34,7 @@
 #include "ocean_couple.hip"
 #include "ocean_rippled.hip"
 #include "ocean_ripple_bounds.hip"
+#include "ocean_ripple_foam.hip"
 
 using namespace ocean;
 
@@ -169,6 +170,11 @@ struct datum_ocean_ctx
   // once and never written again (a test reads them round the record's pointer)
   float4 *rippleboundsblock = nullptr;
   bool rippleboundscurrent = false;   // the record is that of the current state buffer: set by reduce_ripple_bounds, cleared by every call that writes a state buffer
+
+  // wake foam (datum_ocean_set_ripple_foam): nothing is allocated while ripplefoam is null; freed with the layer
+  float *ripplefoamblock = nullptr;   // the allocation: a guard, the plane, a guard (the guards hold 0xCD bytes; no kernel's resource covers them)
+  float *ripplefoam = nullptr;        // the plane: R x R coverage on the layer's torus
+  float ripplefoamt1 = 0.04f, ripplefoamk1 = 10.0f, ripplefoamt2 = 0.5f, ripplefoamk2 = 2.0f, ripplefoamdecay = 0.5f;   // datum_ocean_set_ripple_foam_params
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -1009,6 +1015,7 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->ripplestate[1]);
   (void)hipFree(ctx->ripplesrc);
   (void)hipFree(ctx->rippleboundsblock);
+  (void)hipFree(ctx->ripplefoamblock);
 
   for(Staging &st : ctx->staging)
     (void)hipFree(st.ptr);
@@ -3036,8 +3043,17 @@ namespace
     return g;
   }
 
+  // wake foam's share of set_ripples, reset_ripples and center_ripples ("wake foam", below): each does nothing while the foam is off
+  int free_ripple_foam(datum_ocean_ctx *ctx);
+  int clear_ripple_foam(datum_ocean_ctx *ctx);
+  int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy);
+
   int free_ripples(datum_ocean_ctx *ctx)
   {
+    int const rc = free_ripple_foam(ctx);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
     HIPCHECK(ctx, hipFree(ctx->ripplestate[0]));
     ctx->ripplestate[0] = nullptr;
     HIPCHECK(ctx, hipFree(ctx->ripplestate[1]));
@@ -3298,6 +3314,10 @@ int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
 
   HIPCHECK(ctx, launch_ripple_scroll(a, ctx->stream));
 
+  rc = scroll_ripple_foam(ctx, a.g, a.oldx, a.oldy);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
   ctx->rippleox = ox;
   ctx->rippleoy = oy;
 
@@ -3312,7 +3332,9 @@ int datum_ocean_reset_ripples(datum_ocean_t ctx)
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  return clear_ripples(ctx);
+  rc = clear_ripples(ctx);
+
+  return rc != DATUM_OCEAN_OK ? rc : clear_ripple_foam(ctx);
 }
 
 int datum_ocean_ripples_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes, int *ox, int *oy)
@@ -4733,6 +4755,277 @@ int datum_ocean_algorithmic_bytes(datum_ocean_t ctx, double *rowpass_bytes, doub
 }
 
 }
+
+/* -- wake foam: a coverage plane beside the ripple layer (ocean_ripple_foam.hip) ---------------------------------------------------------- */
+
+namespace
+{
+  // floats of each guard round the plane: 256 bytes, so the plane keeps hipMalloc's alignment to that
+  constexpr size_t RIPPLE_FOAM_GUARD = 64;
+
+  int free_ripple_foam(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, hipFree(ctx->ripplefoamblock));
+    ctx->ripplefoamblock = nullptr;
+    ctx->ripplefoam = nullptr;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // no foam anywhere, on the handle's stream
+  int clear_ripple_foam(datum_ocean_ctx *ctx)
+  {
+    if (ctx->ripplefoam)
+      HIPCHECK(ctx, hipMemsetAsync(ctx->ripplefoam, 0, ripple_cells(ctx) * sizeof(float), ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the window moved from (oldx, oldy) to g's origin: the cells that entered hold no foam
+  int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy)
+  {
+    if (!ctx->ripplefoam)
+      return DATUM_OCEAN_OK;
+
+    RippleFoamScrollArgs a;
+    a.foam = ctx->ripplefoam;
+    a.g = g;
+    a.oldx = oldx;
+    a.oldy = oldy;
+
+    HIPCHECK(ctx, launch_ripple_foam_scroll(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // what every call that needs the plane refuses, the layer first; `name` goes into the error text
+  int check_ripple_foam(datum_ocean_ctx *ctx, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    if (!ctx->ripplefoam)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (std::string(name) + ": the wake foam is off (datum_ocean_set_ripple_foam)").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  int check_ripple_foam_points(datum_ocean_ctx *ctx, void const *points, size_t n, void const *out, char const *name)
+  {
+    int rc = check_ripple_foam(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    std::string const what = name;
+
+    if (n > 0 && (!points || !out))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or out").c_str());
+
+    if (((uintptr_t)points & 7) || ((uintptr_t)out & 3))
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and out 4-byte aligned").c_str());
+
+    if (n > (size_t)INT32_MAX / 16)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX / 16").c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // device arrays, n > 0
+  int run_ripple_foam_samples(datum_ocean_ctx *ctx, void const *points, size_t n, void *out)
+  {
+    RippleFoamSampleArgs a;
+    a.foam = ctx->ripplefoam;
+    a.points = static_cast<float2 const*>(points);
+    a.samples = static_cast<float*>(out);
+    a.g = ripple_grid(ctx);
+    a.count = (int)n;
+
+    HIPCHECK(ctx, launch_ripple_foam_samples(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_set_ripple_foam(datum_ocean_t ctx, int on)
+{
+  int rc = check_ripples(ctx, "datum_ocean_set_ripple_foam");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  rc = free_ripple_foam(ctx);
+  if (rc != DATUM_OCEAN_OK || !on)
+    return rc;
+
+  size_t const bytes = (ripple_cells(ctx) + 2 * RIPPLE_FOAM_GUARD) * sizeof(float);
+
+  hipError_t e = hipMalloc(&ctx->ripplefoamblock, bytes);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(ctx->ripplefoamblock, 0xCD, bytes, ctx->stream);
+
+  if (e != hipSuccess)
+  {
+    (void)free_ripple_foam(ctx);
+    return fail(ctx, (int)e, "datum_ocean_set_ripple_foam: hipMalloc");
+  }
+
+  ctx->ripplefoam = ctx->ripplefoamblock + RIPPLE_FOAM_GUARD;
+
+  rc = clear_ripple_foam(ctx);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_set_ripple_foam_params(datum_ocean_t ctx, float t1, float k1, float t2, float k2, float decay)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_foam_params: null handle");
+
+  if (!(std::isfinite(t1) && std::isfinite(t2)))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_foam_params: t1 and t2 must be finite");
+
+  if (!std::isfinite(k1) || k1 < 0.0f || !std::isfinite(k2) || k2 < 0.0f)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_foam_params: k1 and k2 must be finite and not negative");
+
+  if (!std::isfinite(decay) || decay < 0.0f)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_foam_params: decay must be finite and not negative");
+
+  ctx->ripplefoamt1 = t1;
+  ctx->ripplefoamk1 = k1;
+  ctx->ripplefoamt2 = t2;
+  ctx->ripplefoamk2 = k2;
+  ctx->ripplefoamdecay = decay;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_step_ripple_foam(datum_ocean_t ctx, float dt)
+{
+  int rc = check_ripple_foam(ctx, "datum_ocean_step_ripple_foam");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  // (a negative dt would make the fade a growth)
+  if (!std::isfinite(dt) || dt < 0.0f)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripple_foam: dt is not finite or is negative");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  RippleFoamArgs a;
+  a.state = ctx->ripplestate[ctx->ripplecurrent];
+  a.foam = ctx->ripplefoam;
+  a.g = ripple_grid(ctx);
+  a.p.hinv = 0.5f * a.g.invs;
+  a.p.t1 = ctx->ripplefoamt1;
+  a.p.k1 = ctx->ripplefoamk1;
+  a.p.t2 = ctx->ripplefoamt2;
+  a.p.k2 = ctx->ripplefoamk2;
+  a.p.fade = (float)std::exp(-(double)ctx->ripplefoamdecay * (double)dt);
+
+  HIPCHECK(ctx, launch_ripple_foam(a, ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_reset_ripple_foam(datum_ocean_t ctx)
+{
+  int rc = check_ripple_foam(ctx, "datum_ocean_reset_ripple_foam");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return clear_ripple_foam(ctx);
+}
+
+int datum_ocean_ripple_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes, int *ox, int *oy)
+{
+  int rc = check_ripple_foam(ctx, "datum_ocean_ripple_foam_device");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!device_ptr)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_foam_device: null argument");
+
+  *device_ptr = ctx->ripplefoam;
+
+  if (bytes)
+    *bytes = ripple_cells(ctx) * sizeof(float);
+  if (ox)
+    *ox = ctx->rippleox;
+  if (oy)
+    *oy = ctx->rippleoy;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_ripple_foam(datum_ocean_t ctx, float *plane)
+{
+  int rc = check_ripple_foam(ctx, "datum_ocean_read_ripple_foam");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!plane)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_ripple_foam: null argument");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // window order from the torus, as datum_ocean_read_ripples: up to four rectangles, split where the window wraps in memory
+  int const R = ctx->rippleR;
+  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
+
+  float const *src = ctx->ripplefoam;
+
+  size_t const pitch = (size_t)R * sizeof(float);
+
+  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
+  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
+
+  for(int j = 0; j < 2; ++j)
+    for(int i = 0; i < 2; ++i)
+      if (w[i] > 0 && h[j] > 0)
+        HIPCHECK(ctx, hipMemcpy2DAsync(plane + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i] * sizeof(float), (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_sample_ripple_foam(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device)
+{
+  int rc = check_ripple_foam_points(ctx, points_device, n, out_device, "datum_ocean_sample_ripple_foam");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  return run_ripple_foam_samples(ctx, points_device, n, out_device);
+}
+
+int datum_ocean_query_ripple_foam(datum_ocean_t ctx, float const *points, size_t n, float *out)
+{
+  int rc = check_ripple_foam_points(ctx, points, n, out, "datum_ocean_query_ripple_foam");
+  if (rc != DATUM_OCEAN_OK || n == 0)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // datum_ocean_query_ripples' staging: the surface queries' two buffers, grown on demand
+  return read_staged(ctx, ctx->staging[STAGE_POINTS], points, n * sizeof(float2), ctx->staging[STAGE_SAMPLES], out, n * sizeof(float),
+                     [&](void const *in, void *dev) { return run_ripple_foam_samples(ctx, in, n, dev); });
+}
+
+}   // extern "C"
 
 /* -- bounds of the ripple layer, the rippled slab and the bounded rippled cast (ocean_ripple_bounds.hip) --------------------------------- */
 

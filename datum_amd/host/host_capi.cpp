@@ -566,6 +566,46 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_ripple_foam(void *c, int on)
+  {
+    try
+    {
+      set_ocean_ripple_foam(static_cast<HostContext*>(c)->context, on != 0);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_step_ocean_ripple_foam(void *c, float dt)
+  {
+    try
+    {
+      step_ocean_ripple_foam(static_cast<HostContext*>(c)->context, dt);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_query_ocean_ripple_foam(void *c, float const *xy, size_t count, float *coverage)
+  {
+    try
+    {
+      query_ocean_ripple_foam(static_cast<HostContext*>(c)->context, reinterpret_cast<Vec2 const*>(xy), count, coverage);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_read_ocean_ripple_foam(void *c, float *plane)
+  {
+    try
+    {
+      read_ocean_ripple_foam(static_cast<HostContext*>(c)->context, plane);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_read_ocean_vertices(void *c, void *ocean, float *vertices)
   {
     try

@@ -1180,6 +1180,40 @@ void cast_ocean_rays_rippled_bounded(OceanContext &context, OceanParams const &p
 }
 
 
+///////////////////////// wake foam /////////////////////////////////////////
+void set_ocean_ripple_foam(OceanContext &context, bool on)
+{
+  if (!context.ready)
+    throw runtime_error("set_ocean_ripple_foam: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_set_ripple_foam(context.hip, on ? 1 : 0), "datum_ocean_set_ripple_foam");
+}
+
+void step_ocean_ripple_foam(OceanContext &context, float dt)
+{
+  if (!context.ready)
+    throw runtime_error("step_ocean_ripple_foam: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_step_ripple_foam(context.hip, dt), "datum_ocean_step_ripple_foam");
+}
+
+void query_ocean_ripple_foam(OceanContext &context, Vec2 const *positions, size_t count, float *coverage)
+{
+  if (!context.ready)
+    throw runtime_error("query_ocean_ripple_foam: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_query_ripple_foam(context.hip, reinterpret_cast<float const*>(positions), count, coverage), "datum_ocean_query_ripple_foam");
+}
+
+void read_ocean_ripple_foam(OceanContext &context, float *plane)
+{
+  if (!context.ready)
+    throw runtime_error("read_ocean_ripple_foam: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_read_ripple_foam(context.hip, plane), "datum_ocean_read_ripple_foam");
+}
+
+
 ///////////////////////// read_ocean_displacement ///////////////////////////
 void read_ocean_displacement(OceanContext &context, float *maps)
 {

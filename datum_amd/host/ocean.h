@@ -553,6 +553,16 @@ OceanRippleBounds reduce_ocean_ripple_bounds(OceanContext &context);
 OceanSurfaceSlab ocean_surface_slab_rippled(OceanContext &context, OceanParams const &params);
 void cast_ocean_rays_rippled_bounded(OceanContext &context, OceanParams const &params, OceanRay const *rays, std::size_t n, OceanRayRecord *records, int iterations = 4, int steps = 32, int refine = 8);
 
+// wake foam (include/datum_ocean_hip.h: "wake foam", the definition there): an R x R plane of coverage in [0, 1] beside the ripple layer, off
+// until set_ocean_ripple_foam(context, true); set_ocean_ripples switches it off again.  step_ocean_ripple_foam updates it from the layer's
+// current state (one launch, enqueued); query_ocean_ripple_foam gives the bilinear coverage at `count` positions and read_ocean_ripple_foam
+// the whole plane in window order, R x R floats for the R given to set_ocean_ripples -- host arrays, blocking.  All four throw before
+// prepare_ocean_context and while the layer is off; all but set_ocean_ripple_foam while the foam is off
+void set_ocean_ripple_foam(OceanContext &context, bool on);
+void step_ocean_ripple_foam(OceanContext &context, float dt);
+void query_ocean_ripple_foam(OceanContext &context, lml::Vec2 const *positions, std::size_t count, float *coverage);
+void read_ocean_ripple_foam(OceanContext &context, float *plane);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

@@ -132,6 +132,10 @@ def load():
             "datum_host_ocean_surface_slab_rippled": (I, [P, P, P]),
             "datum_host_cast_ocean_rays_bounded": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_cast_ocean_rays_rippled_bounded": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
+            "datum_host_set_ocean_ripple_foam": (I, [P, I]),
+            "datum_host_step_ocean_ripple_foam": (I, [P, F]),
+            "datum_host_query_ocean_ripple_foam": (I, [P, P, ctypes.c_size_t, P]),
+            "datum_host_read_ocean_ripple_foam": (I, [P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -512,6 +516,27 @@ class OceanContext:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
         out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_cast_ocean_rays_rippled_bounded(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
+        return out
+
+    def set_ocean_ripple_foam(self, on=True):
+        """set_ocean_ripple_foam: the wake foam plane beside the ripple layer, zeroed; False frees it"""
+        self._check(self.lib.datum_host_set_ocean_ripple_foam(self.c, 1 if on else 0))
+
+    def step_ocean_ripple_foam(self, dt):
+        """step_ocean_ripple_foam: one update of the plane from the layer's current state"""
+        self._check(self.lib.datum_host_step_ocean_ripple_foam(self.c, dt))
+
+    def query_ocean_ripple_foam(self, xy):
+        """query_ocean_ripple_foam: (M,) float32, the bilinear coverage at the positions"""
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty(pts.shape[0], np.float32)
+        self._check(self.lib.datum_host_query_ocean_ripple_foam(self.c, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P)))
+        return out
+
+    def read_ocean_ripple_foam(self, R):
+        """read_ocean_ripple_foam: the plane in window order, (R, R) float32 for the R given to set_ocean_ripples"""
+        out = np.empty((R, R), np.float32)
+        self._check(self.lib.datum_host_read_ocean_ripple_foam(self.c, out.ctypes.data_as(P)))
         return out
 
     def read_vertices(self, mesh):

@@ -61,7 +61,9 @@ extern "C" {
  *      datum_ocean_gen_blend_rippled, datum_ocean_sample_surface_blend_rippled, datum_ocean_read_surface_blend_rippled,
  *      datum_ocean_cast_rays_rippled and datum_ocean_read_rays_rippled; then the ripple layer's bounds, datum_ocean_reduce_ripple_bounds,
  *      datum_ocean_ripple_bounds_device, datum_ocean_read_ripple_bounds and datum_ocean_surface_slab_rippled, with the bounded rippled
- *      casts datum_ocean_cast_rays_rippled_bounded and datum_ocean_read_rays_rippled_bounded.
+ *      casts datum_ocean_cast_rays_rippled_bounded and datum_ocean_read_rays_rippled_bounded; then wake foam, datum_ocean_set_ripple_foam,
+ *      datum_ocean_set_ripple_foam_params, datum_ocean_step_ripple_foam, datum_ocean_reset_ripple_foam, datum_ocean_ripple_foam_device,
+ *      datum_ocean_read_ripple_foam, datum_ocean_sample_ripple_foam and datum_ocean_query_ripple_foam.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -976,8 +978,8 @@ int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades,
  * while it is off the call returns DATUM_OCEAN_ESTATE whatever its other arguments are (a null handle is DATUM_OCEAN_EINVAL).  n == 0
  * enqueues nothing.  A refused call enqueues nothing and changes nothing.
  * LEFT OUT: the layer's rate in datum_ocean_sample_velocity_blend; the layer in datum_ocean_reduce_bodies,
- * datum_ocean_reduce_body_drag and datum_ocean_step_bodies (datum_ocean_step_bodies_coupled is the call for that); foam from the layer;
- * anything on the displace path. */
+ * datum_ocean_reduce_body_drag and datum_ocean_step_bodies (datum_ocean_step_bodies_coupled is the call for that);
+ * anything on the displace path.  (The foam from the layer is no longer left out: "wake foam", below, behind the ripple layer's bounds.) */
 int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device);
 int datum_ocean_sample_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
                                              void const *points_device, size_t n, void *samples_device);
@@ -1053,6 +1055,64 @@ int datum_ocean_cast_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades
                                           void const *rays_device, size_t n, void *records_device);
 int datum_ocean_read_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                           float const *rays, size_t n, float *records);
+
+/* -- wake foam (added at ABI 9; nothing in the reference) ---------------------------------------------------------------------------------
+ * The white water of a wake.  The foam plane above ("foam") follows the periodic Jacobian of the FFT surface, which knows nothing of the
+ * bodies: a boat's wake, the ring round a dropped crate and an impact leave no foam there.  This is an opt-in R x R plane of fp32
+ * coverage in [0, 1] beside the ripple layer's state, on the layer's torus -- world cell (I, J) at (J mod R)·R + (I mod R) -- that scrolls
+ * with the window and is updated from the layer's state by an explicit call; the renderer adds it to the FFT foam the way it adds η to
+ * the height (sum, then clamp).  Off by default: while it is off nothing is allocated or launched and no call changes
+ * by a bit; while it is on no other call's outputs change by a bit either -- the state buffers, src, the FFT foam plane, the maps and
+ * every record keep their bits.
+ *
+ * THE UPDATE.  step_ripple_foam(dt), per window cell.  η_t is the cell's rate and eL, eR, eD, eU are the step's four neighbours' heights
+ * in the layer's CURRENT state buffer (the one datum_ocean_ripples_device returns; pending deposits are not seen); a neighbour outside
+ * the window is 0.  Every operator is one fp32 operation as written (no contraction):
+ *     hx  = (eR − eL) · hinv          hinv = 0.5f · invs: the central difference over 2 s
+ *     hy  = (eU − eD) · hinv
+ *     q   = hx·hx + hy·hy             the slope squared (two products, one addition)
+ *     g1  = (q − t1) · k1             breaking: slope² over a threshold
+ *     g2  = (fabsf(η_t) − t2) · k2    churn: the rate over a threshold
+ *     g   = fminf(fmaxf(fmaxf(g1, g2), 0.0f), 1.0f)
+ *     new = fmaxf(g, old · fade)      fade = (float)exp(−(double)decay · (double)dt), on the host
+ * FOAM_ACCUMULATE's rule with two sources.  A NaN loses every fmaxf; of two zeros of opposite sign fmaxf gives +0 here (C leaves that
+ * case open, and a gain of 0 makes a −0 of every cell under its threshold: with the case decided the plane repeats bit for bit on the
+ * device and on any host).  The plane stays in [0, 1].
+ *
+ *   set_ripple_foam          on != 0 allocates the plane (4 R² bytes) and zero-fills it, a second time as well; on == 0 frees it.  Waits for
+ *                            the stream.  DATUM_OCEAN_ESTATE while the layer is off.  datum_ocean_set_ripples with any R, 0 included,
+ *                            switches the foam off and frees the plane.
+ *   set_ripple_foam_params   t1, k1, t2, k2, decay: all five finite, the gains k1, k2 and decay >= 0, else DATUM_OCEAN_EINVAL.  A gain of 0
+ *                            switches its source off.  Works while the foam is off; kept over set_ripples and set_ripple_foam.  The
+ *                            defaults are DESIGN CHOICES, NOT MEASUREMENTS: t1 = 0.04 (a slope of 0.2), k1 = 10, t2 = 0.5 m/s, k2 = 2,
+ *                            decay = 0.5 1/s.
+ *   step_ripple_foam         enqueues one launch on the handle's stream and returns.  dt < 0 or not finite is DATUM_OCEAN_EINVAL; dt = 0 is
+ *                            legal and gives fade = 1.  It writes the plane only.
+ *   reset_ripple_foam        no foam anywhere; one memset on the handle's stream.
+ *   ripple_foam_device       the plane, its bytes and the layer's origin, for a renderer that binds it.  The pointer does not alternate:
+ *                            it holds from one set_ripple_foam to the next (or to the next set_ripples).
+ *   read_ripple_foam         the plane to the HOST in window order, [j][i] for cell (ox + i, oy + j); blocking.
+ *   sample_ripple_foam       per DEVICE point (8 bytes, x y) one float, 4-byte aligned: the bilinear patch between the four cell centres
+ *                            around the point, in the deposit's u, I0, wx:
+ *                                f0 = f00 + wx·(f10 − f00)     f1 = f01 + wx·(f11 − f01)     f = f0 + wy·(f1 − f0)
+ *                            Cells outside the window read 0.  A non-finite point gives NaN and fetches nothing; a finite one beyond
+ *                            2^30 cells gives 0.
+ *   query_ripple_foam        the same from HOST arrays, blocking, through the surface queries' staging, as datum_ocean_query_ripples.
+ * While the foam is on, datum_ocean_center_ripples also zeroes the plane's cells that entered the window (one more launch; a jump of R
+ * cells or more clears the plane) and datum_ocean_reset_ripples also clears the plane.
+ * Every call but the two setters returns DATUM_OCEAN_ESTATE while the layer or the foam is off.  The layer is looked at first.  A null
+ * handle is DATUM_OCEAN_EINVAL, with the call's name in the error text.  n == 0 enqueues nothing.  A refused call enqueues nothing.
+ * LEFT OUT: fusing the update into the last ripple sub-step (it would read the state the step has in registers, and change the step's
+ * device code); advection of the foam by the water's velocity; a direct source from src, that is, hull churn before it becomes a wave;
+ * wake foam as field 7 of the rippled query's record; a bounds/`active` record for the plane. */
+int datum_ocean_set_ripple_foam(datum_ocean_t ctx, int on);
+int datum_ocean_set_ripple_foam_params(datum_ocean_t ctx, float t1, float k1, float t2, float k2, float decay);
+int datum_ocean_step_ripple_foam(datum_ocean_t ctx, float dt);
+int datum_ocean_reset_ripple_foam(datum_ocean_t ctx);
+int datum_ocean_ripple_foam_device(datum_ocean_t ctx, void **device_ptr, size_t *bytes, int *ox, int *oy);
+int datum_ocean_read_ripple_foam(datum_ocean_t ctx, float *plane);
+int datum_ocean_sample_ripple_foam(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device);
+int datum_ocean_query_ripple_foam(datum_ocean_t ctx, float const *points, size_t n, float *out);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -707,6 +707,32 @@ class Ocean:
         c = [int(x) for x in cascades]
         return (I * len(c))(*c), len(c)
 
+    def _sample_points(self, fn, cascades, oceanset, iterations, points_ptr, count, samples_ptr):
+        """a point query on device arrays through the C function `fn`: the list, the pointers, the return code"""
+        arr, n = self._list(cascades)
+        self._check(fn(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(samples_ptr)))
+
+    def _read_points(self, fn, cascades, oceanset, iterations, points, floats):
+        """its host twin: `points` as (M, 2) float32, (M, floats) float32 back"""
+        arr, n = self._list(cascades)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], floats), np.float32)
+        self._check(fn(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
+
+    def _cast(self, fn, cascades, oceanset, iterations, steps, refine, rays_ptr, n, records_ptr):
+        """a ray cast on device arrays through the C function `fn`"""
+        arr, c = self._list(cascades)
+        self._check(fn(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
+
+    def _read_cast(self, fn, cascades, oceanset, iterations, steps, refine, rays):
+        """its host twin: `rays` as (n, RAY_FLOATS) float32, (n, RAY_RECORD_FLOATS) float32 back"""
+        arr, c = self._list(cascades)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
+        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
+        self._check(fn(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
+        return out
+
     def gen_blend(self, cascades, oceanset, sizex, sizey, vertices_device_ptr):
         """gen() of the sum of the listed cascades, each sampled with the handle's own 1 / wavescale (oceanset.scale is ignored)"""
         arr, n = self._list(cascades)
@@ -714,16 +740,11 @@ class Ocean:
 
     def sample_surface_blend(self, cascades, oceanset, points_ptr, count, samples_ptr, iterations=4):
         """sample_surface() of the sum of the listed cascades: device pointers, enqueued on the handle's stream"""
-        arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_sample_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(samples_ptr)))
+        self._sample_points(self.lib.datum_ocean_sample_surface_blend, cascades, oceanset, iterations, points_ptr, count, samples_ptr)
 
     def read_surface_blend(self, cascades, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
-        arr, n = self._list(cascades)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
-        out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_surface_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
-        return out
+        return self._read_points(self.lib.datum_ocean_read_surface_blend, cascades, oceanset, iterations, points, SURFACE_SAMPLE_FLOATS)
 
     # -- surface velocity (datum_ocean_set_velocity): d/dt of map layer 0, one float4 plane per cascade -----------------------------------
 
@@ -752,16 +773,11 @@ class Ocean:
 
     def sample_velocity_blend(self, cascades, oceanset, points_ptr, count, out_ptr, iterations=4):
         """sample_surface_blend()'s solve, then the listed cascades' velocity planes at the same texels: device pointers, enqueued"""
-        arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_sample_velocity_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(out_ptr)))
+        self._sample_points(self.lib.datum_ocean_sample_velocity_blend, cascades, oceanset, iterations, points_ptr, count, out_ptr)
 
     def read_velocity_blend(self, cascades, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32: V(b), residual, velocity, 0"""
-        arr, n = self._list(cascades)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
-        out = np.empty((pts.shape[0], VELOCITY_SAMPLE_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_velocity_blend(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
-        return out
+        return self._read_points(self.lib.datum_ocean_read_velocity_blend, cascades, oceanset, iterations, points, VELOCITY_SAMPLE_FLOATS)
 
     # -- body buoyancy (datum_ocean_reduce_bodies): per-body force and torque from hull probes -----------------------------------------
 
@@ -912,29 +928,19 @@ class Ocean:
 
     def sample_surface_blend_rippled(self, cascades, oceanset, points_ptr, count, samples_ptr, iterations=4):
         """sample_surface_blend() with the layer sampled at the asked point: device pointers, enqueued on the handle's stream"""
-        arr, n = self._list(cascades)
-        self._check(self.lib.datum_ocean_sample_surface_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(points_ptr), count, _dev(samples_ptr)))
+        self._sample_points(self.lib.datum_ocean_sample_surface_blend_rippled, cascades, oceanset, iterations, points_ptr, count, samples_ptr)
 
     def read_surface_blend_rippled(self, cascades, oceanset, points, iterations=4):
         """the same from a host (M, 2) float32 array, blocking; returns (M, 8) float32"""
-        arr, n = self._list(cascades)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
-        out = np.empty((pts.shape[0], SURFACE_SAMPLE_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_surface_blend_rippled(self.h, arr, n, ctypes.byref(oceanset), iterations, _ptr(pts), pts.shape[0], _ptr(out)))
-        return out
+        return self._read_points(self.lib.datum_ocean_read_surface_blend_rippled, cascades, oceanset, iterations, points, SURFACE_SAMPLE_FLOATS)
 
     def cast_rays_rippled(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
         """cast_rays() on the rippled water: every height of the search and the record at hi carry the layer"""
-        arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
+        self._cast(self.lib.datum_ocean_cast_rays_rippled, cascades, oceanset, iterations, steps, refine, rays_ptr, n, records_ptr)
 
     def read_rays_rippled(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
-        arr, c = self._list(cascades)
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
-        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_rays_rippled(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
-        return out
+        return self._read_cast(self.lib.datum_ocean_read_rays_rippled, cascades, oceanset, iterations, steps, refine, rays)
 
     # -- ripple-layer bounds (datum_ocean_reduce_ripple_bounds), the rippled slab and the rippled casts that skip the samples it decides -----
 
@@ -967,16 +973,11 @@ class Ocean:
     def cast_rays_rippled_bounded(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
         """cast_rays_rippled with the samples outside the rippled slab decided without a height evaluation: the same records bit for bit.
         Needs current bounds of the maps (reduce_bounds) AND of the layer (reduce_ripple_bounds), else OceanError(ESTATE)."""
-        arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays_rippled_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
+        self._cast(self.lib.datum_ocean_cast_rays_rippled_bounded, cascades, oceanset, iterations, steps, refine, rays_ptr, n, records_ptr)
 
     def read_rays_rippled_bounded(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
-        arr, c = self._list(cascades)
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
-        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_rays_rippled_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
-        return out
+        return self._read_cast(self.lib.datum_ocean_read_rays_rippled_bounded, cascades, oceanset, iterations, steps, refine, rays)
 
     # -- wake foam (datum_ocean_set_ripple_foam): a coverage plane beside the ripple layer, fed by its slopes and rates --------------------
 
@@ -1026,16 +1027,11 @@ class Ocean:
     def cast_rays(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
         """Enqueue the cast of `n` rays (device pointer, 32 bytes each: ox, oy, oz, tmin, dx, dy, dz, tmax) into `n` records of 12 floats
         (device pointer): hi, lo, g(hi), status (0 miss, 1 enter, 2 leave) and the surface record at hi."""
-        arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
+        self._cast(self.lib.datum_ocean_cast_rays, cascades, oceanset, iterations, steps, refine, rays_ptr, n, records_ptr)
 
     def read_rays(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
-        arr, c = self._list(cascades)
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
-        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_rays(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
-        return out
+        return self._read_cast(self.lib.datum_ocean_read_rays, cascades, oceanset, iterations, steps, refine, rays)
 
     # -- surface bounds (datum_ocean_reduce_bounds) and the ray casts that skip the samples they decide ------------------------------------
 
@@ -1067,16 +1063,11 @@ class Ocean:
     def cast_rays_bounded(self, cascades, oceanset, rays_ptr, n, records_ptr, iterations=4, steps=32, refine=8):
         """cast_rays with the samples outside the slab decided without a height evaluation: the same records bit for bit.  Needs current
         bounds (reduce_bounds after the last displace or bind_maps), else OceanError(ESTATE)."""
-        arr, c = self._list(cascades)
-        self._check(self.lib.datum_ocean_cast_rays_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _dev(rays_ptr), n, _dev(records_ptr)))
+        self._cast(self.lib.datum_ocean_cast_rays_bounded, cascades, oceanset, iterations, steps, refine, rays_ptr, n, records_ptr)
 
     def read_rays_bounded(self, cascades, oceanset, rays, iterations=4, steps=32, refine=8):
         """the same from a host array, blocking: `rays` (n, 8) float32; returns (n, 12) float32"""
-        arr, c = self._list(cascades)
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, RAY_FLOATS)
-        out = np.empty((r.shape[0], RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_ocean_read_rays_bounded(self.h, arr, c, ctypes.byref(oceanset), iterations, steps, refine, _ptr(r), r.shape[0], _ptr(out)))
-        return out
+        return self._read_cast(self.lib.datum_ocean_read_rays_bounded, cascades, oceanset, iterations, steps, refine, rays)
 
     def algorithmic_bytes(self):
         row, col = D(), D()

@@ -114,24 +114,6 @@ namespace ocean
     query_each_point(b.points, b.samples, b.count, [&](float2 q) { return query_record<LAYOUT>(b.q, query_solve<LAYOUT>(b.q, q), q); });
   }
 
-  inline void const *gen_blend_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_gen_blend_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_gen_blend_kernel<GEN_BANDED>);
-    }
-  }
-
-  inline void const *surface_blend_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_surface_blend_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_surface_blend_kernel<GEN_BANDED>);
-    }
-  }
-
   // b.g.set, b.g.vertices and b.list filled in
   inline hipError_t launch_gen_blend(GenBlendArgs &b, int N, int sizex, int sizey, hipStream_t stream)
   {
@@ -139,7 +121,7 @@ namespace ocean
 
     void *args[] = { &b };
 
-    return hipLaunchKernel(gen_blend_kernel_for(N), dim3(gen_groups(b.g)), dim3(GEN_THREADS), args, GEN_LDS, stream);
+    return hipLaunchKernel(layout_kernel(N, &ocean_gen_blend_kernel<GEN_PLAIN>, &ocean_gen_blend_kernel<GEN_BANDED>), dim3(gen_groups(b.g)), dim3(GEN_THREADS), args, GEN_LDS, stream);
   }
 
   // b.q (but its frame), points, samples and count (> 0) filled in
@@ -149,6 +131,6 @@ namespace ocean
 
     void *args[] = { &b };
 
-    return hipLaunchKernel(surface_blend_kernel_for(b.q.N), dim3((unsigned)((b.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(b.q.N, &ocean_surface_blend_kernel<GEN_PLAIN>, &ocean_surface_blend_kernel<GEN_BANDED>), dim3((unsigned)((b.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
   }
 }

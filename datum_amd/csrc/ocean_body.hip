@@ -173,15 +173,6 @@ namespace ocean
     });
   }
 
-  inline void const *body_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_body_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_body_kernel<GEN_BANDED>);
-    }
-  }
-
   // a.q (but its frame), bodies, probes, records, nbodies (> 0) and nprobes filled in
   inline hipError_t launch_bodies(BodyArgs &a, hipStream_t stream)
   {
@@ -189,6 +180,6 @@ namespace ocean
 
     void *args[] = { &a };
 
-    return hipLaunchKernel(body_kernel_for(a.q.N), dim3((unsigned)(((size_t)a.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(a.q.N, &ocean_body_kernel<GEN_PLAIN>, &ocean_body_kernel<GEN_BANDED>), dim3((unsigned)(((size_t)a.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
   }
 }

@@ -226,18 +226,9 @@ namespace ocean
     ray_cast<LAYOUT>(a.q, r, [&](Ray const &ray, auto &height) { return ray_search_bounded(ray, r.steps, r.inv, r.refine, slab.zlo, slab.zhi, height); });
   }
 
-  inline void const *ray_bounded_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_ray_bounded_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_ray_bounded_kernel<GEN_BANDED>);
-    }
-  }
-
   // a.q and a.r as launch_rays takes them; a.bounds and a.cascades filled in
   inline hipError_t launch_rays_bounded(RayBoundedArgs &a, hipStream_t stream)
   {
-    return ray_launch(ray_bounded_kernel_for(a.q.N), a.q, a.r, &a, stream);
+    return ray_launch(layout_kernel(a.q.N, &ocean_ray_bounded_kernel<GEN_PLAIN>, &ocean_ray_bounded_kernel<GEN_BANDED>), a.q, a.r, &a, stream);
   }
 }

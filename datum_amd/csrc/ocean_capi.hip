@@ -2331,6 +2331,17 @@ namespace
   // a body call's arrays as the caller gave them, device or host alike; motions and props are null where the call takes none
   struct BodyBatch { void const *bodies, *motions, *props; size_t nbodies; void const *probes; size_t nprobes; void *records; };
 
+  // a ray cast's own arguments and arrays as the caller gave them, device or host alike
+  struct RayCall { int steps, refine; void const *rays; size_t n; void *records; };
+
+  // what a read of the summed surface takes besides: the ripple layer on top, and (a cast) the samples the slab decides skipped
+  struct ReadVariant { bool rippled, bounded; };
+
+  // the ripple layer as the reads see it, defined with the layer and with its bounds below
+  int check_ripples(datum_ocean_ctx *ctx, char const *name);
+  RippledLayer rippled_layer(datum_ocean_ctx const *ctx);
+  float4 *ripple_bounds_record(datum_ocean_ctx const *ctx);
+
   // the list's checks, shared by every entry point that takes one; `name` goes into the error text
   int check_blend_list(datum_ocean_ctx *ctx, Query const &q, char const *name)
   {
@@ -2448,14 +2459,79 @@ namespace
     return b;
   }
 
+  // the mesh of the summed surface, with the ripple layer on top where `rippled`: the layer's check first (a null handle EINVAL, the
+  // layer off ESTATE), then the mesh's own, then the launch
+  int gen_blend(datum_ocean_ctx *ctx, Query const &q, int sizex, int sizey, void *vertices, bool rippled, char const *name)
+  {
+    int rc = rippled ? check_ripples(ctx, name) : DATUM_OCEAN_OK;
+    if (rc == DATUM_OCEAN_OK)
+      rc = check_gen_blend_args(ctx, q, sizex, sizey, vertices, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    GenBlendArgs b = gen_blend_args(ctx, q, vertices);
+
+    if (rippled)
+    {
+      GenBlendRippledArgs r = { b, rippled_layer(ctx) };
+
+      HIPCHECK(ctx, launch_gen_blend_rippled(r, ctx->N, sizex, sizey, ctx->stream));
+    }
+    else
+      HIPCHECK(ctx, launch_gen_blend(b, ctx->N, sizex, sizey, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the point read's checks in their order: the layer where it is on top, then the query and the arrays
+  int check_surface_read(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void const *samples, bool rippled, char const *name)
+  {
+    int rc = rippled ? check_ripples(ctx, name) : DATUM_OCEAN_OK;
+
+    return rc != DATUM_OCEAN_OK ? rc : check_surface_blend_args(ctx, q, points, n, samples, name);
+  }
+
   // device arrays, n > 0
-  int run_surface_blend(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples)
+  int run_surface_blend(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples, bool rippled)
   {
     SurfaceBlendArgs b = surface_blend_args(ctx, q, points, n, samples);
 
-    HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
+    if (rippled)
+    {
+      SurfaceBlendRippledArgs r = { b, rippled_layer(ctx) };
+
+      HIPCHECK(ctx, launch_surface_blend_rippled(r, ctx->stream));
+    }
+    else
+      HIPCHECK(ctx, launch_surface_blend(b, ctx->stream));
 
     return DATUM_OCEAN_OK;
+  }
+
+  // the point read on device arrays
+  int sample_surface_blend(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples, bool rippled, char const *name)
+  {
+    int rc = check_surface_read(ctx, q, points, n, samples, rippled, name);
+    if (rc != DATUM_OCEAN_OK || n == 0)
+      return rc;
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    return run_surface_blend(ctx, q, points, n, samples, rippled);
+  }
+
+  // ... and its host twin
+  int read_surface_blend(datum_ocean_ctx *ctx, Query const &q, float const *points, size_t n, float *samples, bool rippled, char const *name)
+  {
+    int rc = check_surface_read(ctx, q, points, n, samples, rippled, name);
+    if (rc != DATUM_OCEAN_OK || n == 0)
+      return rc;
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend(ctx, q, in, n, out, rippled); });
   }
 }
 
@@ -2465,41 +2541,22 @@ extern "C"
 int datum_ocean_gen_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
 {
   Query const q = { cascades, count, set, 0 };
-  int rc = check_gen_blend_args(ctx, q, sizex, sizey, vertices_device, "datum_ocean_gen_blend");
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  GenBlendArgs b = gen_blend_args(ctx, q, vertices_device);
-
-  HIPCHECK(ctx, launch_gen_blend(b, ctx->N, sizex, sizey, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return gen_blend(ctx, q, sizex, sizey, vertices_device, false, "datum_ocean_gen_blend");
 }
 
 int datum_ocean_sample_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_surface_blend_args(ctx, q, points_device, n, samples_device, "datum_ocean_sample_surface_blend");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return run_surface_blend(ctx, q, points_device, n, samples_device);
+  return sample_surface_blend(ctx, q, points_device, n, samples_device, false, "datum_ocean_sample_surface_blend");
 }
 
 int datum_ocean_read_surface_blend(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_surface_blend_args(ctx, q, points, n, samples, "datum_ocean_read_surface_blend");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend(ctx, q, in, n, out); });
+  return read_surface_blend(ctx, q, points, n, samples, false, "datum_ocean_read_surface_blend");
 }
 
 }   // extern "C"
@@ -3535,62 +3592,124 @@ int datum_ocean_query_ripples(datum_ocean_t ctx, float const *points, size_t n, 
 
 namespace
 {
-  // the checks the four entry points share; `name` goes into the error text
-  int check_ray_args(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void const *records, char const *name)
+  // the checks of the eight casts in their order: the layer where it is on top (a null handle EINVAL, the layer off ESTATE), the query, the
+  // cast's own arguments and arrays, then the marks a bounded cast needs: the maps' records, and with the layer on top the layer's record
+  int check_rays(datum_ocean_ctx *ctx, Query const &q, RayCall const &call, ReadVariant v, char const *name)
   {
-    int rc = check_query(ctx, q, name);
+    int rc = v.rippled ? check_ripples(ctx, name) : DATUM_OCEAN_OK;
+    if (rc == DATUM_OCEAN_OK)
+      rc = check_query(ctx, q, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     std::string const what = name;
 
-    if (steps < 1 || steps > DATUM_OCEAN_RAY_MAX_STEPS)
+    if (call.steps < 1 || call.steps > DATUM_OCEAN_RAY_MAX_STEPS)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": steps outside [1, DATUM_OCEAN_RAY_MAX_STEPS]").c_str());
 
-    if (refine < 0 || refine > DATUM_OCEAN_RAY_MAX_REFINE)
+    if (call.refine < 0 || call.refine > DATUM_OCEAN_RAY_MAX_REFINE)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": refine outside [0, DATUM_OCEAN_RAY_MAX_REFINE]").c_str());
 
-    if (n > 0 && (!rays || !records))
+    if (call.n > 0 && (!call.rays || !call.records))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null rays or records").c_str());
 
-    if (((uintptr_t)rays & 15) || ((uintptr_t)records & 15))
+    if (((uintptr_t)call.rays & 15) || ((uintptr_t)call.records & 15))
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": rays and records must be 16-byte aligned").c_str());
 
-    if (n > (size_t)INT32_MAX)
+    if (call.n > (size_t)INT32_MAX)
       return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX").c_str());
+
+    if (v.bounded && !ctx->boundscurrent)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": the bounds are not current (datum_ocean_reduce_bounds after the last displace or bind_maps)").c_str());
+
+    if (v.bounded && v.rippled && !ctx->rippleboundscurrent)
+      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": the ripple bounds are not current (datum_ocean_reduce_ripple_bounds after the last call that stepped, moved, reset or set the layer)").c_str());
 
     return DATUM_OCEAN_OK;
   }
 
-  RayBatch ray_batch(int steps, int refine, void const *rays, size_t n, void *records)
+  RayBatch ray_batch(RayCall const &call)
   {
     RayBatch r;
-    r.rays = static_cast<float4 const*>(rays);
-    r.records = static_cast<float4*>(records);
-    r.n = (int)n;
-    r.steps = steps;
-    r.refine = refine;
+    r.rays = static_cast<float4 const*>(call.rays);
+    r.records = static_cast<float4*>(call.records);
+    r.n = (int)call.n;
+    r.steps = call.steps;
+    r.refine = call.refine;
     r.inv = 0.0f;           // ray_launch
     return r;
   }
 
-  // device arrays, n > 0
-  int run_rays(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
+  // the list as cascade numbers, as the bounded kernels index the handle's records
+  void list_cascades(Query const &q, int *cascades)
+  {
+    for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
+      cascades[c] = (c < q.count) ? q.cascades[c] : 0;
+  }
+
+  // device arrays, n > 0: the variant's kernel argument filled from the one query and the one batch, and its launch
+  int run_rays(datum_ocean_ctx *ctx, Query const &q, RayCall const &call, ReadVariant v)
   {
     RayArgs a;
     a.q = query_args(ctx, q);
-    a.r = ray_batch(steps, refine, rays, n, records);
+    a.r = ray_batch(call);
 
-    HIPCHECK(ctx, launch_rays(a, ctx->stream));
+    if (!v.rippled && !v.bounded)
+      HIPCHECK(ctx, launch_rays(a, ctx->stream));
+    else if (!v.rippled)
+    {
+      RayBoundedArgs b;
+      b.q = a.q;
+      b.r = a.r;
+      b.bounds = reinterpret_cast<float const*>(ctx->bounds);
+      list_cascades(q, b.cascades);
+
+      HIPCHECK(ctx, launch_rays_bounded(b, ctx->stream));
+    }
+    else if (!v.bounded)
+    {
+      RayRippledArgs r = { a, rippled_layer(ctx) };
+
+      HIPCHECK(ctx, launch_rays_rippled(r, ctx->stream));
+    }
+    else
+    {
+      RayRippledBoundedArgs b;
+      b.r.a = a;
+      b.r.layer = rippled_layer(ctx);
+      b.bounds = reinterpret_cast<float const*>(ctx->bounds);
+      b.layerbounds = reinterpret_cast<float const*>(ripple_bounds_record(ctx));
+      list_cascades(q, b.cascades);
+
+      HIPCHECK(ctx, launch_rays_rippled_bounded(b, ctx->stream));
+    }
 
     return DATUM_OCEAN_OK;
   }
 
-  // a read_* twin of a ray cast: `n` rays in, a record per ray out
-  template<class Run>
-  int read_rays(datum_ocean_ctx *ctx, float const *rays, size_t n, float *records, Run &&run)
+  // a cast on device arrays
+  int cast_rays(datum_ocean_ctx *ctx, Query const &q, RayCall const &call, ReadVariant v, char const *name)
   {
-    return read_staged(ctx, ctx->staging[STAGE_RAYS], rays, n * RAY_BYTES, ctx->staging[STAGE_RAY_RECORDS], records, n * RAY_RECORD_BYTES, run);
+    int rc = check_rays(ctx, q, call, v, name);
+    if (rc != DATUM_OCEAN_OK || call.n == 0)
+      return rc;
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    return run_rays(ctx, q, call, v);
+  }
+
+  // ... and its host twin: `n` rays in, a record per ray out
+  int read_rays(datum_ocean_ctx *ctx, Query const &q, RayCall const &call, ReadVariant v, char const *name)
+  {
+    int rc = check_rays(ctx, q, call, v, name);
+    if (rc != DATUM_OCEAN_OK || call.n == 0)
+      return rc;
+
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+    return read_staged(ctx, ctx->staging[STAGE_RAYS], call.rays, call.n * RAY_BYTES, ctx->staging[STAGE_RAY_RECORDS], call.records, call.n * RAY_RECORD_BYTES,
+                       [&](void const *in, void *out) { return run_rays(ctx, q, RayCall{ call.steps, call.refine, in, call.n, out }, v); });
   }
 }
 
@@ -3601,26 +3720,18 @@ int datum_ocean_cast_rays(datum_ocean_t ctx, int const *cascades, int count, dat
                           void const *rays_device, size_t n, void *records_device)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ray_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays_device, n, records_device };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return run_rays(ctx, q, steps, refine, rays_device, n, records_device);
+  return cast_rays(ctx, q, call, ReadVariant{ false, false }, "datum_ocean_cast_rays");
 }
 
 int datum_ocean_read_rays(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                           float const *rays, size_t n, float *records)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ray_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays, n, records };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays(ctx, q, steps, refine, in, n, out); });
+  return read_rays(ctx, q, call, ReadVariant{ false, false }, "datum_ocean_read_rays");
 }
 
 }   // extern "C"
@@ -3665,35 +3776,6 @@ namespace
     HIPCHECK(ctx, launch_bounds(a, ctx->cascades, ctx->stream));
 
     ctx->boundscurrent = true;
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // cast_rays' checks, then the state both bounded entry points need
-  int check_ray_bounded_args(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void const *records, char const *name)
-  {
-    int rc = check_ray_args(ctx, q, steps, refine, rays, n, records, name);
-    if (rc != DATUM_OCEAN_OK)
-      return rc;
-
-    if (!ctx->boundscurrent)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (std::string(name) + ": the bounds are not current (datum_ocean_reduce_bounds after the last displace or bind_maps)").c_str());
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // device arrays, n > 0
-  int run_rays_bounded(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
-  {
-    RayBoundedArgs a;
-    a.q = query_args(ctx, q);
-    a.r = ray_batch(steps, refine, rays, n, records);
-    a.bounds = reinterpret_cast<float const*>(ctx->bounds);
-
-    for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
-      a.cascades[c] = (c < q.count) ? q.cascades[c] : 0;
-
-    HIPCHECK(ctx, launch_rays_bounded(a, ctx->stream));
 
     return DATUM_OCEAN_OK;
   }
@@ -3773,26 +3855,18 @@ int datum_ocean_cast_rays_bounded(datum_ocean_t ctx, int const *cascades, int co
                                   void const *rays_device, size_t n, void *records_device)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ray_bounded_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_bounded");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays_device, n, records_device };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return run_rays_bounded(ctx, q, steps, refine, rays_device, n, records_device);
+  return cast_rays(ctx, q, call, ReadVariant{ false, true }, "datum_ocean_cast_rays_bounded");
 }
 
 int datum_ocean_read_rays_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   float const *rays, size_t n, float *records)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ray_bounded_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays_bounded");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays, n, records };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_bounded(ctx, q, steps, refine, in, n, out); });
+  return read_rays(ctx, q, call, ReadVariant{ false, true }, "datum_ocean_read_rays_bounded");
 }
 
 }   // extern "C"
@@ -3920,114 +3994,50 @@ namespace
     l.g = ripple_grid(ctx);
     return l;
   }
-
-  // device arrays, n > 0
-  int run_surface_blend_rippled(datum_ocean_ctx *ctx, Query const &q, void const *points, size_t n, void *samples)
-  {
-    SurfaceBlendRippledArgs r;
-    r.b = surface_blend_args(ctx, q, points, n, samples);
-    r.layer = rippled_layer(ctx);
-
-    HIPCHECK(ctx, launch_surface_blend_rippled(r, ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // device arrays, n > 0
-  int run_rays_rippled(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
-  {
-    RayRippledArgs r;
-    r.a.q = query_args(ctx, q);
-    r.a.r = ray_batch(steps, refine, rays, n, records);
-    r.layer = rippled_layer(ctx);
-
-    HIPCHECK(ctx, launch_rays_rippled(r, ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
 }
 
 extern "C"
 {
 
-// (each: the layer first -- a null handle EINVAL, the layer off ESTATE -- then the parent call's own checks under this call's name)
+// (each is its parent call with the layer on top: the layer's check first, then the parent's own under this call's name)
 
 int datum_ocean_gen_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int sizex, int sizey, void *vertices_device)
 {
   Query const q = { cascades, count, set, 0 };
-  int rc = check_ripples(ctx, "datum_ocean_gen_blend_rippled");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_gen_blend_args(ctx, q, sizex, sizey, vertices_device, "datum_ocean_gen_blend_rippled");
-  if (rc != DATUM_OCEAN_OK)
-    return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  GenBlendRippledArgs r;
-  r.b = gen_blend_args(ctx, q, vertices_device);
-  r.layer = rippled_layer(ctx);
-
-  HIPCHECK(ctx, launch_gen_blend_rippled(r, ctx->N, sizex, sizey, ctx->stream));
-
-  return DATUM_OCEAN_OK;
+  return gen_blend(ctx, q, sizex, sizey, vertices_device, true, "datum_ocean_gen_blend_rippled");
 }
 
 int datum_ocean_sample_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, void const *points_device, size_t n, void *samples_device)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ripples(ctx, "datum_ocean_sample_surface_blend_rippled");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_blend_args(ctx, q, points_device, n, samples_device, "datum_ocean_sample_surface_blend_rippled");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return run_surface_blend_rippled(ctx, q, points_device, n, samples_device);
+  return sample_surface_blend(ctx, q, points_device, n, samples_device, true, "datum_ocean_sample_surface_blend_rippled");
 }
 
 int datum_ocean_read_surface_blend_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, float const *points, size_t n, float *samples)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ripples(ctx, "datum_ocean_read_surface_blend_rippled");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_surface_blend_args(ctx, q, points, n, samples, "datum_ocean_read_surface_blend_rippled");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return read_points(ctx, points, n, samples, [&](void const *in, void *out) { return run_surface_blend_rippled(ctx, q, in, n, out); });
+  return read_surface_blend(ctx, q, points, n, samples, true, "datum_ocean_read_surface_blend_rippled");
 }
 
 int datum_ocean_cast_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   void const *rays_device, size_t n, void *records_device)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ripples(ctx, "datum_ocean_cast_rays_rippled");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_ray_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_rippled");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays_device, n, records_device };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return run_rays_rippled(ctx, q, steps, refine, rays_device, n, records_device);
+  return cast_rays(ctx, q, call, ReadVariant{ true, false }, "datum_ocean_cast_rays_rippled");
 }
 
 int datum_ocean_read_rays_rippled(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                   float const *rays, size_t n, float *records)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ripples(ctx, "datum_ocean_read_rays_rippled");
-  if (rc == DATUM_OCEAN_OK)
-    rc = check_ray_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays_rippled");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays, n, records };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_rippled(ctx, q, steps, refine, in, n, out); });
+  return read_rays(ctx, q, call, ReadVariant{ true, false }, "datum_ocean_read_rays_rippled");
 }
 
 }   // extern "C"
@@ -5093,39 +5103,6 @@ namespace
 
     return DATUM_OCEAN_OK;
   }
-
-  // the layer first, then the bounded cast's checks (cast_rays' and the maps' mark), then the layer's mark
-  int check_ray_rippled_bounded_args(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void const *records, char const *name)
-  {
-    int rc = check_ripples(ctx, name);
-    if (rc == DATUM_OCEAN_OK)
-      rc = check_ray_bounded_args(ctx, q, steps, refine, rays, n, records, name);
-    if (rc != DATUM_OCEAN_OK)
-      return rc;
-
-    if (!ctx->rippleboundscurrent)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (std::string(name) + ": the ripple bounds are not current (datum_ocean_reduce_ripple_bounds after the last call that stepped, moved, reset or set the layer)").c_str());
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // device arrays, n > 0
-  int run_rays_rippled_bounded(datum_ocean_ctx *ctx, Query const &q, int steps, int refine, void const *rays, size_t n, void *records)
-  {
-    RayRippledBoundedArgs a;
-    a.r.a.q = query_args(ctx, q);
-    a.r.a.r = ray_batch(steps, refine, rays, n, records);
-    a.r.layer = rippled_layer(ctx);
-    a.bounds = reinterpret_cast<float const*>(ctx->bounds);
-    a.layerbounds = reinterpret_cast<float const*>(ripple_bounds_record(ctx));
-
-    for(int c = 0; c < DATUM_OCEAN_MAX_CASCADES; ++c)
-      a.cascades[c] = (c < q.count) ? q.cascades[c] : 0;
-
-    HIPCHECK(ctx, launch_rays_rippled_bounded(a, ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
 }
 
 extern "C"
@@ -5209,26 +5186,18 @@ int datum_ocean_cast_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades
                                           void const *rays_device, size_t n, void *records_device)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ray_rippled_bounded_args(ctx, q, steps, refine, rays_device, n, records_device, "datum_ocean_cast_rays_rippled_bounded");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays_device, n, records_device };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return run_rays_rippled_bounded(ctx, q, steps, refine, rays_device, n, records_device);
+  return cast_rays(ctx, q, call, ReadVariant{ true, true }, "datum_ocean_cast_rays_rippled_bounded");
 }
 
 int datum_ocean_read_rays_rippled_bounded(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations, int steps, int refine,
                                           float const *rays, size_t n, float *records)
 {
   Query const q = { cascades, count, set, iterations };
-  int rc = check_ray_rippled_bounded_args(ctx, q, steps, refine, rays, n, records, "datum_ocean_read_rays_rippled_bounded");
-  if (rc != DATUM_OCEAN_OK || n == 0)
-    return rc;
+  RayCall const call = { steps, refine, rays, n, records };
 
-  HIPCHECK(ctx, hipSetDevice(ctx->device));
-
-  return read_rays(ctx, rays, n, records, [&](void const *in, void *out) { return run_rays_rippled_bounded(ctx, q, steps, refine, in, n, out); });
+  return read_rays(ctx, q, call, ReadVariant{ true, true }, "datum_ocean_read_rays_rippled_bounded");
 }
 
 }   // extern "C"

@@ -185,15 +185,6 @@ namespace ocean
     }
   }
 
-  inline void const *couple_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_couple_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_couple_kernel<GEN_BANDED>);
-    }
-  }
-
   // a.d (but its frame), bodies, motions, props, the layer, h and first filled in; a.d.b.nbodies > 0
   inline hipError_t launch_couple(CoupleArgs &a, hipStream_t stream)
   {
@@ -201,6 +192,6 @@ namespace ocean
 
     void *args[] = { &a };
 
-    return hipLaunchKernel(couple_kernel_for(a.d.b.q.N), dim3((unsigned)(((size_t)a.d.b.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(a.d.b.q.N, &ocean_couple_kernel<GEN_PLAIN>, &ocean_couple_kernel<GEN_BANDED>), dim3((unsigned)(((size_t)a.d.b.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
   }
 }

@@ -45,15 +45,6 @@ namespace ocean
     });
   }
 
-  inline void const *drag_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_drag_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_drag_kernel<GEN_BANDED>);
-    }
-  }
-
   // a.b (but its frame), motions and vel filled in; a.b.nbodies > 0
   inline hipError_t launch_body_drag(DragArgs &a, hipStream_t stream)
   {
@@ -61,6 +52,6 @@ namespace ocean
 
     void *args[] = { &a };
 
-    return hipLaunchKernel(drag_kernel_for(a.b.q.N), dim3((unsigned)(((size_t)a.b.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(a.b.q.N, &ocean_drag_kernel<GEN_PLAIN>, &ocean_drag_kernel<GEN_BANDED>), dim3((unsigned)(((size_t)a.b.nbodies + BODY_WAVES - 1) / BODY_WAVES)), dim3(BODY_THREADS), args, 0, stream);
   }
 }

@@ -389,15 +389,6 @@ namespace ocean
     g.block0 = 0;
   }
 
-  inline void const *gen_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_gen_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_gen_kernel<GEN_BANDED>);
-    }
-  }
-
   // workgroups of the whole mesh (with XCD chunks: rounded up to whole sets of eight chunks)
   inline int gen_groups(GenArgs const &g)
   {
@@ -408,7 +399,7 @@ namespace ocean
   inline hipError_t launch_gen_part(GenArgs &g, int first, int count, hipStream_t stream)
   {
     void *args[] = { &g };
-    void const *kernel = gen_kernel_for(g.N);
+    void const *kernel = layout_kernel(g.N, &ocean_gen_kernel<GEN_PLAIN>, &ocean_gen_kernel<GEN_BANDED>);
 
     g.block0 = first;
 

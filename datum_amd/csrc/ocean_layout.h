@@ -130,6 +130,12 @@ namespace ocean
 
   inline GenLayout gen_layout(int N) { return (band_cols(N) != N) ? GEN_BANDED : GEN_PLAIN; }
 
+  // of a kernel template's two instances, the one for N's layout, as hipLaunchKernel takes it
+  template<class Kernel> inline void const *layout_kernel(int N, Kernel *plain, Kernel *banded)
+  {
+    return reinterpret_cast<void const*>(gen_layout(N) == GEN_PLAIN ? plain : banded);
+  }
+
   //|---------------------- displacement maps, byte offset -> texel -------------
   // The layout read backwards, for the kernels that take the maps in the order they lie in memory (ocean_pack_kernel, ocean_export_kernel):
   // the layout's shape as shifts, and part number r of a cascade -- parts A (and B) counted patch after patch -- back to its texel.

@@ -111,15 +111,6 @@ namespace ocean
     ray_cast<LAYOUT>(a.q, r, [&](Ray const &ray, auto &height) { return ray_search(ray, r.steps, r.inv, r.refine, height); });
   }
 
-  inline void const *ray_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_ray_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_ray_kernel<GEN_BANDED>);
-    }
-  }
-
   // what launch_rays and launch_rays_bounded share: q (but its frame) and r (but inv) filled in, r.n > 0; `args` is the kernel's one argument
   inline hipError_t ray_launch(void const *kernel, QueryArgs &q, RayBatch &r, void *args, hipStream_t stream)
   {
@@ -131,6 +122,6 @@ namespace ocean
 
   inline hipError_t launch_rays(RayArgs &a, hipStream_t stream)
   {
-    return ray_launch(ray_kernel_for(a.q.N), a.q, a.r, &a, stream);
+    return ray_launch(layout_kernel(a.q.N, &ocean_ray_kernel<GEN_PLAIN>, &ocean_ray_kernel<GEN_BANDED>), a.q, a.r, &a, stream);
   }
 }

@@ -214,18 +214,9 @@ namespace ocean
     ray_cast_rippled<LAYOUT>(q, a.r.layer, r, [&](Ray const &ray, auto &height) { return ray_search_bounded(ray, r.steps, r.inv, r.refine, slab.zlo, slab.zhi, height); });
   }
 
-  inline void const *ray_rippled_bounded_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_ray_rippled_bounded_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_ray_rippled_bounded_kernel<GEN_BANDED>);
-    }
-  }
-
   // a.r as launch_rays_rippled takes it; a.bounds, a.layerbounds and a.cascades filled in
   inline hipError_t launch_rays_rippled_bounded(RayRippledBoundedArgs &a, hipStream_t stream)
   {
-    return ray_launch(ray_rippled_bounded_kernel_for(a.r.a.q.N), a.r.a.q, a.r.a.r, &a, stream);
+    return ray_launch(layout_kernel(a.r.a.q.N, &ocean_ray_rippled_bounded_kernel<GEN_PLAIN>, &ocean_ray_rippled_bounded_kernel<GEN_BANDED>), a.r.a.q, a.r.a.r, &a, stream);
   }
 }

@@ -258,33 +258,6 @@ namespace ocean
     ray_cast_rippled<LAYOUT>(ra.a.q, ra.layer, r, [&](Ray const &ray, auto &height) { return ray_search(ray, r.steps, r.inv, r.refine, height); });
   }
 
-  inline void const *gen_blend_rippled_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_gen_blend_rippled_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_gen_blend_rippled_kernel<GEN_BANDED>);
-    }
-  }
-
-  inline void const *surface_blend_rippled_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_surface_blend_rippled_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_surface_blend_rippled_kernel<GEN_BANDED>);
-    }
-  }
-
-  inline void const *ray_rippled_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_ray_rippled_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_ray_rippled_kernel<GEN_BANDED>);
-    }
-  }
-
   // r.b as launch_gen_blend wants it, r.layer filled in
   inline hipError_t launch_gen_blend_rippled(GenBlendRippledArgs &r, int N, int sizex, int sizey, hipStream_t stream)
   {
@@ -292,7 +265,7 @@ namespace ocean
 
     void *args[] = { &r };
 
-    return hipLaunchKernel(gen_blend_rippled_kernel_for(N), dim3(gen_groups(r.b.g)), dim3(GEN_THREADS), args, GEN_LDS, stream);
+    return hipLaunchKernel(layout_kernel(N, &ocean_gen_blend_rippled_kernel<GEN_PLAIN>, &ocean_gen_blend_rippled_kernel<GEN_BANDED>), dim3(gen_groups(r.b.g)), dim3(GEN_THREADS), args, GEN_LDS, stream);
   }
 
   // r.b as launch_surface_blend wants it (count > 0), r.layer filled in
@@ -302,12 +275,12 @@ namespace ocean
 
     void *args[] = { &r };
 
-    return hipLaunchKernel(surface_blend_rippled_kernel_for(r.b.q.N), dim3((unsigned)((r.b.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(r.b.q.N, &ocean_surface_blend_rippled_kernel<GEN_PLAIN>, &ocean_surface_blend_rippled_kernel<GEN_BANDED>), dim3((unsigned)((r.b.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
   }
 
   // r.a as launch_rays wants it (n > 0), r.layer filled in
   inline hipError_t launch_rays_rippled(RayRippledArgs &r, hipStream_t stream)
   {
-    return ray_launch(ray_rippled_kernel_for(r.a.q.N), r.a.q, r.a.r, &r, stream);
+    return ray_launch(layout_kernel(r.a.q.N, &ocean_ray_rippled_kernel<GEN_PLAIN>, &ocean_ray_rippled_kernel<GEN_BANDED>), r.a.q, r.a.r, &r, stream);
   }
 }

@@ -210,15 +210,6 @@ namespace ocean
     out[1] = make_float4(mx, my, mz, foam);
   }
 
-  inline void const *surface_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_surface_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_surface_kernel<GEN_BANDED>);
-    }
-  }
-
   // s.set, s.map, s.foam, s.points, s.samples, s.N, s.count and s.iterations filled in; count > 0
   inline hipError_t launch_surface(SurfaceArgs &s, hipStream_t stream)
   {
@@ -226,6 +217,6 @@ namespace ocean
 
     void *args[] = { &s };
 
-    return hipLaunchKernel(surface_kernel_for(s.N), dim3((unsigned)((s.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(s.N, &ocean_surface_kernel<GEN_PLAIN>, &ocean_surface_kernel<GEN_BANDED>), dim3((unsigned)((s.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
   }
 }

@@ -340,15 +340,6 @@ namespace ocean
     query_each_point(vb.points, vb.samples, vb.count, [&](float2 q) { return query_velocity<LAYOUT>(vb.q, query_solve<LAYOUT>(vb.q, q), q, vb.vel); });
   }
 
-  inline void const *velocity_blend_kernel_for(int N)
-  {
-    switch(gen_layout(N))
-    {
-      case GEN_PLAIN: return reinterpret_cast<void const*>(&ocean_velocity_blend_kernel<GEN_PLAIN>);
-      default: return reinterpret_cast<void const*>(&ocean_velocity_blend_kernel<GEN_BANDED>);
-    }
-  }
-
   // vb.q (but its frame), points, samples, count (> 0) and vb.vel filled in
   inline hipError_t launch_velocity_blend(VelocityBlendArgs &vb, hipStream_t stream)
   {
@@ -356,6 +347,6 @@ namespace ocean
 
     void *args[] = { &vb };
 
-    return hipLaunchKernel(velocity_blend_kernel_for(vb.q.N), dim3((unsigned)((vb.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
+    return hipLaunchKernel(layout_kernel(vb.q.N, &ocean_velocity_blend_kernel<GEN_PLAIN>, &ocean_velocity_blend_kernel<GEN_BANDED>), dim3((unsigned)((vb.count + SURFACE_THREADS - 1) / SURFACE_THREADS)), dim3(SURFACE_THREADS), args, 0, stream);
   }
 }

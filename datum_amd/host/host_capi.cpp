@@ -54,6 +54,30 @@ namespace
     return -1;
   }
 
+  // the flat view of a shim ray cast, and of a surface query: the arrays as the shim types them, an exception as the return code
+  using CastRays = void (*)(OceanContext&, OceanParams const&, OceanRay const*, std::size_t, OceanRayRecord*, int, int, int);
+  using QuerySurface = void (*)(OceanContext&, OceanParams const&, Vec2 const*, std::size_t, OceanSurfaceSample*, int);
+
+  int cast_rays(CastRays cast, void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
+  {
+    try
+    {
+      cast(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int query_surface(QuerySurface query, void *c, void *p, float const *xy, size_t count, float *samples, int iterations)
+  {
+    try
+    {
+      query(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanSurfaceSample*>(samples), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   Camera make_camera(datum_host_camera const &c)
   {
     Camera camera;
@@ -321,12 +345,7 @@ extern "C"
 
   int datum_host_query_ocean_surface(void *c, void *p, float const *xy, size_t count, float *samples, int iterations)
   {
-    try
-    {
-      query_ocean_surface(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanSurfaceSample*>(samples), iterations);
-      return 0;
-    }
-    catch(std::exception const &e) { return caught(e); }
+    return query_surface(query_ocean_surface, c, p, xy, count, samples, iterations);
   }
 
   int datum_host_set_ocean_velocity(void *c, int mode)
@@ -461,32 +480,17 @@ extern "C"
 
   int datum_host_cast_ocean_rays(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
-    try
-    {
-      cast_ocean_rays(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
-      return 0;
-    }
-    catch(std::exception const &e) { return caught(e); }
+    return cast_rays(cast_ocean_rays, c, p, rays, n, records, iterations, steps, refine);
   }
 
   int datum_host_query_ocean_surface_rippled(void *c, void *p, float const *xy, size_t count, float *samples, int iterations)
   {
-    try
-    {
-      query_ocean_surface_rippled(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<Vec2 const*>(xy), count, reinterpret_cast<OceanSurfaceSample*>(samples), iterations);
-      return 0;
-    }
-    catch(std::exception const &e) { return caught(e); }
+    return query_surface(query_ocean_surface_rippled, c, p, xy, count, samples, iterations);
   }
 
   int datum_host_cast_ocean_rays_rippled(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
-    try
-    {
-      cast_ocean_rays_rippled(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
-      return 0;
-    }
-    catch(std::exception const &e) { return caught(e); }
+    return cast_rays(cast_ocean_rays_rippled, c, p, rays, n, records, iterations, steps, refine);
   }
 
   int datum_host_gen_ocean_surface_rippled(void *c, void *ocean, datum_host_camera const *camera, void *p)
@@ -523,12 +527,7 @@ extern "C"
 
   int datum_host_cast_ocean_rays_bounded(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
-    try
-    {
-      cast_ocean_rays_bounded(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
-      return 0;
-    }
-    catch(std::exception const &e) { return caught(e); }
+    return cast_rays(cast_ocean_rays_bounded, c, p, rays, n, records, iterations, steps, refine);
   }
 
   // extrema[4]: etamin, etamax, ratemin, ratemax; counts[2]: nonfinite, active
@@ -558,12 +557,7 @@ extern "C"
 
   int datum_host_cast_ocean_rays_rippled_bounded(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
-    try
-    {
-      cast_ocean_rays_rippled_bounded(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), reinterpret_cast<OceanRay const*>(rays), n, reinterpret_cast<OceanRayRecord*>(records), iterations, steps, refine);
-      return 0;
-    }
-    catch(std::exception const &e) { return caught(e); }
+    return cast_rays(cast_ocean_rays_rippled_bounded, c, p, rays, n, records, iterations, steps, refine);
   }
 
   int datum_host_set_ocean_ripple_foam(void *c, int on)

@@ -877,6 +877,34 @@ void ocean_foam_device(OceanContext &context, void **device_ptr, size_t *bytes)
 }
 
 
+///////////////////////// reads of cascade 0 ////////////////////////////////
+namespace
+{
+  // the host-array entry points of the C ABI that take a cascade list: a point query and a ray cast
+  using ReadPoints = int (*)(datum_ocean_t, int const*, int, datum_ocean_set const*, int, float const*, size_t, float*);
+  using ReadRays = int (*)(datum_ocean_t, int const*, int, datum_ocean_set const*, int, int, int, float const*, size_t, float*);
+
+  // `read`, named `what` in the error, on the one-cascade list and the set of `params`; the caller has thrown where the context is not prepared
+  void read_points(OceanContext &context, OceanParams const &params, ReadPoints read, char const *what, Vec2 const *positions, size_t count, void *samples, int iterations)
+  {
+    datum_ocean_set set = make_oceanset(Camera(), params);
+
+    int const cascade = 0;
+
+    check(context.hip, read(context.hip, &cascade, 1, &set, iterations, reinterpret_cast<float const*>(positions), count, static_cast<float*>(samples)), what);
+  }
+
+  void read_rays(OceanContext &context, OceanParams const &params, ReadRays read, char const *what, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
+  {
+    datum_ocean_set set = make_oceanset(Camera(), params);
+
+    int const cascade = 0;
+
+    check(context.hip, read(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), what);
+  }
+}
+
+
 ///////////////////////// query_ocean_surface ///////////////////////////////
 void query_ocean_surface(OceanContext &context, OceanParams const &params, Vec2 const *positions, size_t count, OceanSurfaceSample *samples, int iterations)
 {
@@ -911,11 +939,7 @@ void query_ocean_velocity(OceanContext &context, OceanParams const &params, Vec2
   if (!context.ready)
     throw runtime_error("query_ocean_velocity: the context is not prepared (prepare_ocean_context)");
 
-  datum_ocean_set set = make_oceanset(Camera(), params);
-
-  int const cascade = 0;
-
-  check(context.hip, datum_ocean_read_velocity_blend(context.hip, &cascade, 1, &set, iterations, reinterpret_cast<float const*>(positions), count, reinterpret_cast<float*>(samples)), "datum_ocean_read_velocity_blend");
+  read_points(context, params, datum_ocean_read_velocity_blend, "datum_ocean_read_velocity_blend", positions, count, samples, iterations);
 }
 
 
@@ -1035,11 +1059,7 @@ void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay 
   if (!context.ready)
     throw runtime_error("cast_ocean_rays: the context is not prepared (prepare_ocean_context)");
 
-  datum_ocean_set set = make_oceanset(Camera(), params);
-
-  int const cascade = 0;
-
-  check(context.hip, datum_ocean_read_rays(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays");
+  read_rays(context, params, datum_ocean_read_rays, "datum_ocean_read_rays", rays, n, records, iterations, steps, refine);
 }
 
 
@@ -1049,11 +1069,7 @@ void query_ocean_surface_rippled(OceanContext &context, OceanParams const &param
   if (!context.ready)
     throw runtime_error("query_ocean_surface_rippled: the context is not prepared (prepare_ocean_context)");
 
-  datum_ocean_set set = make_oceanset(Camera(), params);
-
-  int const cascade = 0;
-
-  check(context.hip, datum_ocean_read_surface_blend_rippled(context.hip, &cascade, 1, &set, iterations, reinterpret_cast<float const*>(positions), count, reinterpret_cast<float*>(samples)), "datum_ocean_read_surface_blend_rippled");
+  read_points(context, params, datum_ocean_read_surface_blend_rippled, "datum_ocean_read_surface_blend_rippled", positions, count, samples, iterations);
 }
 
 void cast_ocean_rays_rippled(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
@@ -1061,11 +1077,7 @@ void cast_ocean_rays_rippled(OceanContext &context, OceanParams const &params, O
   if (!context.ready)
     throw runtime_error("cast_ocean_rays_rippled: the context is not prepared (prepare_ocean_context)");
 
-  datum_ocean_set set = make_oceanset(Camera(), params);
-
-  int const cascade = 0;
-
-  check(context.hip, datum_ocean_read_rays_rippled(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays_rippled");
+  read_rays(context, params, datum_ocean_read_rays_rippled, "datum_ocean_read_rays_rippled", rays, n, records, iterations, steps, refine);
 }
 
 void gen_ocean_surface_rippled(OceanContext &context, Ocean const *target, Camera const &camera, OceanParams const &params)
@@ -1118,11 +1130,7 @@ void cast_ocean_rays_bounded(OceanContext &context, OceanParams const &params, O
   if (!context.ready)
     throw runtime_error("cast_ocean_rays_bounded: the context is not prepared (prepare_ocean_context)");
 
-  datum_ocean_set set = make_oceanset(Camera(), params);
-
-  int const cascade = 0;
-
-  check(context.hip, datum_ocean_read_rays_bounded(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays_bounded");
+  read_rays(context, params, datum_ocean_read_rays_bounded, "datum_ocean_read_rays_bounded", rays, n, records, iterations, steps, refine);
 }
 
 
@@ -1172,11 +1180,7 @@ void cast_ocean_rays_rippled_bounded(OceanContext &context, OceanParams const &p
   if (!context.ready)
     throw runtime_error("cast_ocean_rays_rippled_bounded: the context is not prepared (prepare_ocean_context)");
 
-  datum_ocean_set set = make_oceanset(Camera(), params);
-
-  int const cascade = 0;
-
-  check(context.hip, datum_ocean_read_rays_rippled_bounded(context.hip, &cascade, 1, &set, iterations, steps, refine, reinterpret_cast<float const*>(rays), n, reinterpret_cast<float*>(records)), "datum_ocean_read_rays_rippled_bounded");
+  read_rays(context, params, datum_ocean_read_rays_rippled_bounded, "datum_ocean_read_rays_rippled_bounded", rays, n, records, iterations, steps, refine);
 }
 
 

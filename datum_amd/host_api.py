@@ -341,13 +341,24 @@ class OceanContext:
         self._check(self.lib.datum_host_read_ocean_foam(self.c, out.ctypes.data_as(P)))
         return out
 
+    def _query(self, fn, params, xy, iterations, floats):
+        """a point query through the C function `fn`: `xy` as (M, 2) float32, (M, floats) float32 back"""
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty((pts.shape[0], floats), np.float32)
+        self._check(fn(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
+        return out
+
+    def _cast(self, fn, params, rays, iterations, steps, refine):
+        """a ray cast through the C function `fn`: `rays` as (n, RAY_FLOATS) float32, (n, RAY_RECORD_FLOATS) float32 back"""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
+        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
+        self._check(fn(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
+        return out
+
     def query_ocean_surface(self, params, xy, iterations=4):
         """query_ocean_surface: the surface above the (M, 2) world points on the maps the context last displaced, swell, plane and scale from
         `params`; returns (M, 8) float32 records (OceanSurfaceSample: position, residual, normal, foam)"""
-        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
-        out = np.empty((pts.shape[0], capi.SURFACE_SAMPLE_FLOATS), np.float32)
-        self._check(self.lib.datum_host_query_ocean_surface(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
-        return out
+        return self._query(self.lib.datum_host_query_ocean_surface, params, xy, iterations, capi.SURFACE_SAMPLE_FLOATS)
 
     def set_velocity(self, mode):
         """set_ocean_velocity: "off", "on" or a capi.VELOCITY_MODES value"""
@@ -361,10 +372,7 @@ class OceanContext:
 
     def query_ocean_velocity(self, params, xy, iterations=4):
         """query_ocean_velocity: (M, 8) float32 records (OceanVelocitySample: position, residual, velocity, 0)"""
-        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
-        out = np.empty((pts.shape[0], capi.VELOCITY_SAMPLE_FLOATS), np.float32)
-        self._check(self.lib.datum_host_query_ocean_velocity(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
-        return out
+        return self._query(self.lib.datum_host_query_ocean_velocity, params, xy, iterations, capi.VELOCITY_SAMPLE_FLOATS)
 
     def reduce_ocean_bodies(self, params, bodies, probes, iterations=4):
         """reduce_ocean_bodies: `bodies` an array of capi.BODY_DTYPE, `probes` (n, 4) float32 (x, y, z, weight); returns (nbodies, 8) float32
@@ -457,24 +465,15 @@ class OceanContext:
     def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):
         """cast_ocean_rays: `rays` (n, 8) float32 (origin, tmin, direction, tmax); returns (n, 12) float32 records (OceanRayRecord: hi, lo,
         g(hi), status, the surface sample at hi)"""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
-        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_host_cast_ocean_rays(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
-        return out
+        return self._cast(self.lib.datum_host_cast_ocean_rays, params, rays, iterations, steps, refine)
 
     def query_ocean_surface_rippled(self, params, xy, iterations=4):
         """query_ocean_surface_rippled: query_ocean_surface with the ripple layer's height and slopes on top; (M, 8) float32"""
-        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
-        out = np.empty((pts.shape[0], capi.SURFACE_SAMPLE_FLOATS), np.float32)
-        self._check(self.lib.datum_host_query_ocean_surface_rippled(self.c, params.p, pts.ctypes.data_as(P), pts.shape[0], out.ctypes.data_as(P), iterations))
-        return out
+        return self._query(self.lib.datum_host_query_ocean_surface_rippled, params, xy, iterations, capi.SURFACE_SAMPLE_FLOATS)
 
     def cast_ocean_rays_rippled(self, params, rays, iterations=4, steps=32, refine=8):
         """cast_ocean_rays_rippled: cast_ocean_rays' arguments and records, on the water with the ripple layer on top"""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
-        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_host_cast_ocean_rays_rippled(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
-        return out
+        return self._cast(self.lib.datum_host_cast_ocean_rays_rippled, params, rays, iterations, steps, refine)
 
     def gen_ocean_surface_rippled(self, mesh, params, camera=None):
         """gen_ocean_surface_rippled: the rippled mesh of cascade 0 into the mesh's vertex buffer, from the maps last displaced"""
@@ -493,10 +492,7 @@ class OceanContext:
 
     def cast_ocean_rays_bounded(self, params, rays, iterations=4, steps=32, refine=8):
         """cast_ocean_rays_bounded: cast_ocean_rays' arguments and records; raises unless the bounds are current"""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
-        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_host_cast_ocean_rays_bounded(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
-        return out
+        return self._cast(self.lib.datum_host_cast_ocean_rays_bounded, params, rays, iterations, steps, refine)
 
     def reduce_ocean_ripple_bounds(self):
         """reduce_ocean_ripple_bounds: the OceanRippleBounds of the layer's current state, blocking: etamin, etamax, ratemin, ratemax as
@@ -513,10 +509,7 @@ class OceanContext:
 
     def cast_ocean_rays_rippled_bounded(self, params, rays, iterations=4, steps=32, refine=8):
         """cast_ocean_rays_rippled_bounded: cast_ocean_rays_rippled's arguments and records; raises unless both bounds are current"""
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, capi.RAY_FLOATS)
-        out = np.empty((r.shape[0], capi.RAY_RECORD_FLOATS), np.float32)
-        self._check(self.lib.datum_host_cast_ocean_rays_rippled_bounded(self.c, params.p, r.ctypes.data_as(P), r.shape[0], out.ctypes.data_as(P), iterations, steps, refine))
-        return out
+        return self._cast(self.lib.datum_host_cast_ocean_rays_rippled_bounded, params, rays, iterations, steps, refine)
 
     def set_ocean_ripple_foam(self, on=True):
         """set_ocean_ripple_foam: the wake foam plane beside the ripple layer, zeroed; False frees it"""

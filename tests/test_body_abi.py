@@ -111,7 +111,7 @@ def test_the_point_evaluation_is_stated_once():
     # the query kernel and the body kernel reach their records through the functions alone: neither makes a texel or loads from a map
     assert_query_is_stated_once()
     blend, body = read_csrc("ocean_blend.hip"), read_csrc("ocean_body.hip")
-    kernel = blend.split("ocean_surface_blend_kernel(SurfaceBlendArgs b)")[1].split("inline void const *gen_blend_kernel_for")[0]
+    kernel = blend.split("ocean_surface_blend_kernel(SurfaceBlendArgs b)")[1].split("inline hipError_t launch_gen_blend(")[0]
     for text in (kernel, body):
         assert text.count("query_record<LAYOUT>(") == 1 and text.count("query_solve<LAYOUT>(") == 1
         assert "SurfaceTexel" not in text and "rmap" not in text and ".map" not in text

@@ -9,6 +9,7 @@ import re
 import numpy as np
 
 from test_body_abi import read_csrc
+from test_rippled_abi import assert_ray_calls_are_stated_once
 from test_surface_abi import _set
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,8 +110,10 @@ def test_the_kernels_call_the_header():
     assert bounds.count("OR_HD BoundsSlab bounds_slab(") == 1 and bounds.count("ray_search_bounded(") == 1 and "ripple" not in bounds
     # the parents' checks are shared, not copied
     section = host.split("/* -- bounds of the ripple layer, the rippled slab and the bounded rippled cast (ocean_ripple_bounds.hip)")[1]
-    assert section.count("check_ripples(ctx, ") == 5 and section.count("check_ray_bounded_args(") == 1 and section.count("check_blend_list(") == 1
-    assert section.count("read_rays(ctx, ") == 1 and "check_ray_args(" not in section
+    # (the four calls that are the layer's own check it themselves; the two casts are the shared cast with both flags, checked in its order)
+    assert section.count("check_ripples(ctx, ") == 4 and section.count("check_blend_list(") == 1 and "check_ray" not in section and "run_rays" not in section
+    assert section.count("read_rays(ctx, ") == 1 and section.count("cast_rays(ctx, ") == 1 and section.count("ReadVariant{ true, true }") == 2
+    assert_ray_calls_are_stated_once(host)
     # the mark: set in one place, cleared by the calls that write a state buffer
     assert host.count("ctx->rippleboundscurrent = true") == 1 and host.count("ctx->rippleboundscurrent = false") == 5
     emul = open(os.path.join(ROOT, "tests", "cpu", "ripple_bounds_emul.cpp"), encoding="utf-8").read()

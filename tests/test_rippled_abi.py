@@ -25,6 +25,40 @@ def _header():
     return open(HEADER, encoding="utf-8").read()
 
 
+def entry_points(text):
+    """the C entry points defined in a stretch of ocean_capi.hip: {name: body}, in the text's order"""
+    return dict(re.findall(r"^int (datum_ocean_\w+)\([^{;]*\)\n\{\n(.*?)^\}\n", text, re.S | re.M))
+
+
+RAY_VARIANTS = {"": "false, false", "_bounded": "false, true", "_rippled": "true, false", "_rippled_bounded": "true, true"}
+
+
+def assert_ray_calls_are_stated_once(host):
+    """ocean_capi.hip: the eight casts build the query, the call and the variant and name one shared function once; that function's check
+    and run are defined once; no entry point refuses, copies or launches by itself"""
+    entries = entry_points(host)
+    for suffix, flags in RAY_VARIANTS.items():
+        for shared in ("cast_rays", "read_rays"):
+            name = "datum_ocean_" + shared + suffix
+            body = entries[name]
+            assert re.findall(r"\b(\w+)\(ctx, ", body) == [shared], name
+            assert '%s(ctx, q, call, ReadVariant{ %s }, "%s");' % (shared, flags, name) in body, name
+            assert "Query const q = { cascades, count, set, iterations };" in body and "RayCall const call = { steps, refine, rays" in body, name
+            for word in ("fail(", "hipMemcpy", "hipSetDevice", "check_", "launch_"):
+                assert word not in body, (name, word)
+    for fn in ("int check_rays(", "int run_rays(", "int cast_rays(", "int read_rays(", "RayBatch ray_batch(", "void list_cascades("):
+        assert host.count(fn) == 1, fn
+    assert host.count("check_rays(ctx, q, call, v, name)") == 2 and host.count("run_rays(ctx, q, ") == 2 and host.count("list_cascades(q, ") == 2
+    # the refusals in their order: the layer, the query, the cast's own, the maps' mark, the layer's mark
+    check = host.split("int check_rays(")[1].split("RayBatch ray_batch(")[0]
+    order = ["v.rippled ? check_ripples(ctx, name)", "check_query(ctx, q, name)", "steps outside", "refine outside", "null rays or records", "16-byte aligned", "n above INT32_MAX",
+             "v.bounded && !ctx->boundscurrent", "v.bounded && v.rippled && !ctx->rippleboundscurrent"]
+    assert [check.count(text) for text in order] == [1] * len(order) and sorted(order, key=check.index) == order
+    assert host.count("!ctx->boundscurrent") == 1 and host.count("!ctx->rippleboundscurrent") == 1
+    for gone in ("check_ray_args(", "check_ray_bounded_args(", "check_ray_rippled_bounded_args(", "run_rays_bounded(", "run_rays_rippled(", "run_rays_rippled_bounded("):
+        assert gone not in host, gone
+
+
 def test_header_declares_and_library_exports():
     from datum_amd import capi
 
@@ -98,10 +132,21 @@ def test_the_kernels_call_the_headers():
     query = read_csrc("ocean_query.hip")
     assert query.count("sx = fmaf(nx, rz, sx);") == 1 and "return query_finish(a, b, q, query_sums<LAYOUT>(a, b));" in query
     assert read_csrc("ocean_blend.hip").count('#include "ocean_gen_cascades.inc"') == 1
-    # the parents' checks are shared, not copied
+    # the parents' checks are shared, not copied: each call here is its parent's one function with the layer on top, and that function
+    # is defined once, the layer's check ahead of the parent's own
     section = host.split("/* -- rippled reads:")[1].split("// a cascade's maps as the reference's")[0]
-    assert section.count("check_ripples(ctx, ") == 5 and section.count("check_gen_blend_args(") == 1 and section.count("check_surface_blend_args(") == 2 and section.count("check_ray_args(") == 2
-    assert "fail(" not in section and "hipMemcpy" not in section
+    assert "fail(" not in section and "hipMemcpy" not in section and "check_" not in section and "launch_" not in section
+    entries = entry_points(section)
+    assert list(entries) == ["datum_ocean_gen_blend_rippled", "datum_ocean_sample_surface_blend_rippled", "datum_ocean_read_surface_blend_rippled",
+                             "datum_ocean_cast_rays_rippled", "datum_ocean_read_rays_rippled"]
+    for name, body in entries.items():
+        parent = name[len("datum_ocean_"):-len("_rippled")]
+        assert re.findall(r"\b(\w+)\(ctx, ", body) == [parent], name
+        assert ('ReadVariant{ true, false }, "%s");' % name if "rays" in name else 'true, "%s");' % name) in body, name
+    for fn in ("int gen_blend(", "int check_surface_read(", "int run_surface_blend(", "int sample_surface_blend(", "int read_surface_blend("):
+        assert host.count(fn) == 1, fn
+    assert host.count("int rc = rippled ? check_ripples(ctx, name) : DATUM_OCEAN_OK;") == 2 and host.count("check_gen_blend_args(ctx, ") == 1 and host.count("check_surface_read(ctx, ") == 2
+    assert_ray_calls_are_stated_once(host)
     emul = open(os.path.join(ROOT, "tests", "cpu", "rippled_emul.cpp"), encoding="utf-8").read()
     for fn in ("ocean_rippled.h", "ocean_ray.h", "rippled_height(", "rippled_slope(", "ripple_sample(", "ray_search("):
         assert fn in emul, fn

@@ -149,6 +149,8 @@ SYMBOLS = {
     "datum_ocean_step_bodies_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
     "datum_ocean_set_ripples": (I, [P, I, F]),
     "datum_ocean_set_ripple_params": (I, [P, F, F, I, F]),
+    "datum_ocean_set_ripple_dispersion": (I, [P, I, F]),
+    "datum_ocean_ripple_deep_weights": (I, [P]),
     "datum_ocean_center_ripples": (I, [P, F, F]),
     "datum_ocean_reset_ripples": (I, [P]),
     "datum_ocean_ripples_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(I), ctypes.POINTER(I)]),
@@ -209,6 +211,7 @@ SURFACE_MAX_ITERATIONS = 16
 
 # the ripple layer (datum_ocean_set_ripples, added at ABI 9): the sizes a layer can have, floats per wake record, the limits of a step
 RIPPLE_SIZES = (64, 128, 256, 512, 1024)
+RIPPLE_WAVE, RIPPLE_DEEP = 0, 1          # DATUM_OCEAN_RIPPLE_WAVE, DATUM_OCEAN_RIPPLE_DEEP: datum_ocean_set_ripple_dispersion's modes
 RIPPLE_RECORD_FLOATS = 8
 RIPPLE_MAX_SUBSTEPS = 16
 RIPPLE_MAX_SPONGE = 64
@@ -839,6 +842,11 @@ class Ocean:
     def set_ripple_params(self, c=2.0, gamma=0.05, sponge_cells=8, sponge_gamma=4.0):
         """wave speed (m/s), damping (1/s), width of the absorbing border in cells (0: none) and its extra damping at the edge (1/s)"""
         self._check(self.lib.datum_ocean_set_ripple_params(self.h, c, gamma, sponge_cells, sponge_gamma))
+
+    def set_ripple_dispersion(self, mode=RIPPLE_WAVE, g=9.81):
+        """the step's mode: RIPPLE_WAVE (the default, the wave equation with speed c) or RIPPLE_DEEP (omega^2 = g |k|, a 13 x 13
+        convolution); works while the layer is off, survives set_ripples and writes no state"""
+        self._check(self.lib.datum_ocean_set_ripple_dispersion(self.h, mode, g))
 
     def center_ripples(self, x, y):
         """Move the window so that the cell of (x, y) is its middle; the cells that entered are zeroed, none is copied."""

@@ -31,6 +31,7 @@
 #include "ocean_drag.hip"
 #include "ocean_step.hip"
 #include "ocean_ripple.hip"
+#include "ocean_ripple_deep.hip"
 #include "ocean_couple.hip"
 #include "ocean_rippled.hip"
 #include "ocean_ripple_bounds.hip"
@@ -160,10 +161,13 @@ struct datum_ocean_ctx
   double ripples = 0.0;               // cell side, metres
   int rippleox = 0, rippleoy = 0;     // the window's origin, cells
   float2 *ripplestate[2] = { nullptr, nullptr };
+  float2 *ripplestateblock[2] = { nullptr, nullptr };   // their allocations: a guard, the buffer, a guard (0xCD bytes; no kernel's resource covers the guards)
   int ripplecurrent = 0;              // the state buffer the next sub-step reads
   int *ripplesrc = nullptr;           // pending deposits
   double ripplec = 2.0, ripplegamma = 0.05, ripplespongegamma = 4.0;   // datum_ocean_set_ripple_params
   int ripplesponge = 8;
+  int rippledispersion = DATUM_OCEAN_RIPPLE_WAVE;   // datum_ocean_set_ripple_dispersion: the step's mode, and g of the DEEP one (9.81 as a float)
+  double rippleg = (double)9.81f;
 
   // datum_ocean_reduce_ripple_bounds: one block, allocated by the first reduce after a set_ripples and freed with the layer, of a guard, the
   // workgroups' partials, a guard, the layer's record and a guard, 32 bytes each but the partials: the guards are filled with 0xCD bytes
@@ -1011,8 +1015,8 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->foam.own);
   (void)hipFree(ctx->velocity.own);
   (void)hipFree(ctx->velocitywork);
-  (void)hipFree(ctx->ripplestate[0]);
-  (void)hipFree(ctx->ripplestate[1]);
+  (void)hipFree(ctx->ripplestateblock[0]);
+  (void)hipFree(ctx->ripplestateblock[1]);
   (void)hipFree(ctx->ripplesrc);
   (void)hipFree(ctx->rippleboundsblock);
   (void)hipFree(ctx->ripplefoamblock);
@@ -3105,16 +3109,20 @@ namespace
   int clear_ripple_foam(datum_ocean_ctx *ctx);
   int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy);
 
+  // the two state buffers between their guards ("the ripple layer's state buffers", below)
+  hipError_t alloc_ripple_state(datum_ocean_ctx *ctx, size_t cells);
+  int free_ripple_state(datum_ocean_ctx *ctx);
+
   int free_ripples(datum_ocean_ctx *ctx)
   {
     int const rc = free_ripple_foam(ctx);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    HIPCHECK(ctx, hipFree(ctx->ripplestate[0]));
-    ctx->ripplestate[0] = nullptr;
-    HIPCHECK(ctx, hipFree(ctx->ripplestate[1]));
-    ctx->ripplestate[1] = nullptr;
+    int const rcs = free_ripple_state(ctx);
+    if (rcs != DATUM_OCEAN_OK)
+      return rcs;
+
     HIPCHECK(ctx, hipFree(ctx->ripplesrc));
     ctx->ripplesrc = nullptr;
     HIPCHECK(ctx, hipFree(ctx->rippleboundsblock));
@@ -3222,11 +3230,67 @@ namespace
     return ctx->ripplec * (double)h / ctx->ripples;
   }
 
-  // what a sub-step of length h takes but its two state buffers: src, the grid, c2s2 and the sponge table, rounded once from double
-  // (datum_ocean_step_ripples, and datum_ocean_step_bodies_coupled for the layer's share of a coupled sub-step)
-  RippleStepArgs ripple_step_args(datum_ocean_ctx const *ctx, float h)
+  // the DEEP step's weights (ocean_ripple_deep.h), built by the first call that asks for them: the table and Sum |F| of its 169 weights
+  struct RippleDeepTable
   {
-    RippleStepArgs a = {};
+    float G[RIPPLE_DEEP_WEIGHTS];
+    double mass;
+
+    RippleDeepTable() { mass = ripple_deep_weights(G); }
+  };
+
+  RippleDeepTable const &ripple_deep_table()
+  {
+    static RippleDeepTable const table;
+
+    return table;
+  }
+
+  // h sqrt(g Sum |F| / s) in double, which a DEEP step holds against semi-implicit Euler's bound h Omega < 2
+  double ripple_deep_bound(datum_ocean_ctx const *ctx, float h)
+  {
+    return (double)h * std::sqrt(ctx->rippleg * ripple_deep_table().mass / ctx->ripples);
+  }
+
+  // the stability rule of the layer's mode for a sub-step of length h; `wave` is what a refusal in the WAVE mode says behind the call's name
+  int check_ripple_stability(datum_ocean_ctx *ctx, float h, char const *name, char const *wave)
+  {
+    std::string const what = name;
+
+    if (ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP)
+    {
+      if (ripple_deep_bound(ctx, h) > 1.9)
+        return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt / substeps * sqrt(g * sum|F| / s) above 1.9, the DEEP step's stability bound of 2 with a margin").c_str());
+    }
+    else if (ripple_courant(ctx, h) > 0.7)
+      return fail(ctx, DATUM_OCEAN_EINVAL, (what + wave).c_str());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // a sub-step in the layer's mode: the wave step's arguments (a.s, its two state buffers among them), which the DEEP step takes too,
+  // and the DEEP step's own
+  struct RippleStep
+  {
+    bool deep;
+    RippleDeepStepArgs a;
+  };
+
+  // what a sub-step of length h takes but its two state buffers: src, the grid, c2s2 and the sponge table, rounded once from double,
+  // and in the DEEP mode g / s and the weights
+  // (datum_ocean_step_ripples, and datum_ocean_step_bodies_coupled for the layer's share of a coupled sub-step)
+  RippleStep ripple_step_args(datum_ocean_ctx const *ctx, float h)
+  {
+    RippleStep r = {};
+    r.deep = ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP;
+
+    if (r.deep)
+    {
+      r.a.gs = (float)(ctx->rippleg / ctx->ripples);
+      std::memcpy(r.a.G, ripple_deep_table().G, sizeof r.a.G);
+    }
+
+    RippleStepArgs &a = r.a.s;
     a.src = ctx->ripplesrc;
     a.g = ripple_grid(ctx);
     a.B = ctx->ripplesponge;
@@ -3240,7 +3304,13 @@ namespace
       a.f[k] = (float)(1.0 / (1.0 + (double)h * (ctx->ripplegamma + ctx->ripplespongegamma * (u * u))));
     }
 
-    return a;
+    return r;
+  }
+
+  // the one place where the mode chooses the kernel (the name is ocean::launch_ripple_step's: a call site reads the same in either mode)
+  hipError_t launch_ripple_step(RippleStep &r, bool first, hipStream_t stream)
+  {
+    return r.deep ? ocean::launch_ripple_deep_step(r.a, first, stream) : ocean::launch_ripple_step(r.a.s, first, stream);
   }
 
   int check_ripple_points(datum_ocean_ctx *ctx, void const *points, size_t n, void const *out, char const *name)
@@ -3287,9 +3357,7 @@ int datum_ocean_set_ripples(datum_ocean_t ctx, int R, float s)
 
   size_t const cells = (size_t)R * R;
 
-  hipError_t e = hipMalloc(&ctx->ripplestate[0], cells * sizeof(float2));
-  if (e == hipSuccess)
-    e = hipMalloc(&ctx->ripplestate[1], cells * sizeof(float2));
+  hipError_t e = alloc_ripple_state(ctx, cells);
   if (e == hipSuccess)
     e = hipMalloc(&ctx->ripplesrc, cells * sizeof(int));
 
@@ -3334,6 +3402,33 @@ int datum_ocean_set_ripple_params(datum_ocean_t ctx, float c, float gamma, int s
   ctx->ripplegamma = (double)gamma;
   ctx->ripplesponge = sponge_cells;
   ctx->ripplespongegamma = (double)sponge_gamma;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_set_ripple_dispersion(datum_ocean_t ctx, int mode, float g)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_dispersion: null handle");
+
+  if (mode != DATUM_OCEAN_RIPPLE_WAVE && mode != DATUM_OCEAN_RIPPLE_DEEP)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_dispersion: mode must be DATUM_OCEAN_RIPPLE_WAVE or DATUM_OCEAN_RIPPLE_DEEP");
+
+  if (!std::isfinite(g) || !(g > 0.0f))
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_dispersion: g must be finite and positive");
+
+  ctx->rippledispersion = mode;
+  ctx->rippleg = (double)g;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_ripple_deep_weights(float *quadrant49)
+{
+  if (!quadrant49)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_deep_weights: null argument");
+
+  std::memcpy(quadrant49, ripple_deep_table().G, sizeof ripple_deep_table().G);
 
   return DATUM_OCEAN_OK;
 }
@@ -3464,22 +3559,23 @@ int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps)
 
   float const h = substep_length(dt, substeps);
 
-  // the scheme's stability bound is c h / s <= 1 / sqrt 2
-  if (ripple_courant(ctx, h) > 0.7)
-    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_step_ripples: c * dt / (substeps * s) above 0.7, the scheme's stability bound with a margin");
+  // the wave scheme's stability bound is c h / s <= 1 / sqrt 2
+  rc = check_ripple_stability(ctx, h, "datum_ocean_step_ripples", ": c * dt / (substeps * s) above 0.7, the scheme's stability bound with a margin");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  RippleStepArgs a = ripple_step_args(ctx, h);
+  RippleStep r = ripple_step_args(ctx, h);
 
   ctx->rippleboundscurrent = false;
 
   for(int i = 0; i < substeps; ++i)
   {
-    a.in = ctx->ripplestate[ctx->ripplecurrent];
-    a.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
+    r.a.s.in = ctx->ripplestate[ctx->ripplecurrent];
+    r.a.s.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
 
-    HIPCHECK(ctx, launch_ripple_step(a, i == 0, ctx->stream));
+    HIPCHECK(ctx, launch_ripple_step(r, i == 0, ctx->stream));
 
     ctx->ripplecurrent ^= 1;
 
@@ -3892,10 +3988,7 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    if (ripple_courant(ctx, substep_length(dt, substeps)) > 0.7)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": c * dt / (substeps * s) above 0.7, the ripple step's stability bound with a margin").c_str());
-
-    return DATUM_OCEAN_OK;
+    return check_ripple_stability(ctx, substep_length(dt, substeps), name, ": c * dt / (substeps * s) above 0.7, the ripple step's stability bound with a margin");
   }
 
   // device arrays; `substeps` rounds of: the bodies' coupled sub-step (nbodies > 0), then the layer's sub-step in its first form
@@ -3912,7 +4005,7 @@ namespace
     a.g = ripple_grid(ctx);
     a.h = h;
 
-    RippleStepArgs r = ripple_step_args(ctx, h);
+    RippleStep r = ripple_step_args(ctx, h);
 
     ctx->rippleboundscurrent = false;
 
@@ -3927,8 +4020,8 @@ namespace
       }
 
       // datum_ocean_step_ripples(h, 1): the first form takes the deposits in, and no kernel clears src
-      r.in = ctx->ripplestate[ctx->ripplecurrent];
-      r.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
+      r.a.s.in = ctx->ripplestate[ctx->ripplecurrent];
+      r.a.s.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
 
       HIPCHECK(ctx, launch_ripple_step(r, true, ctx->stream));
 
@@ -4764,6 +4857,47 @@ int datum_ocean_algorithmic_bytes(datum_ocean_t ctx, double *rowpass_bytes, doub
   return DATUM_OCEAN_OK;
 }
 
+}
+
+/* -- the ripple layer's state buffers: each between two guards ------------------------------------------------------------------------------ */
+
+namespace
+{
+  // 32 cells, 256 bytes, of 0xCD bytes before and after each state buffer, filled once: the buffers keep hipMalloc's alignment, the step
+  // kernels' resources cover exactly the buffers, and a test finds the guards whole (tests/test_gpu_ripple_deep.py)
+  constexpr size_t RIPPLE_STATE_GUARD = 32;
+
+  hipError_t alloc_ripple_state(datum_ocean_ctx *ctx, size_t cells)
+  {
+    size_t const bytes = (cells + 2 * RIPPLE_STATE_GUARD) * sizeof(float2);
+
+    for(int i = 0; i < 2; ++i)
+    {
+      hipError_t e = hipMalloc(&ctx->ripplestateblock[i], bytes);
+
+      if (e == hipSuccess)
+        e = hipMemsetAsync(ctx->ripplestateblock[i], 0xCD, bytes, ctx->stream);
+
+      if (e != hipSuccess)
+        return e;
+
+      ctx->ripplestate[i] = ctx->ripplestateblock[i] + RIPPLE_STATE_GUARD;
+    }
+
+    return hipSuccess;
+  }
+
+  int free_ripple_state(datum_ocean_ctx *ctx)
+  {
+    for(int i = 0; i < 2; ++i)
+    {
+      HIPCHECK(ctx, hipFree(ctx->ripplestateblock[i]));
+      ctx->ripplestateblock[i] = nullptr;
+      ctx->ripplestate[i] = nullptr;
+    }
+
+    return DATUM_OCEAN_OK;
+  }
 }
 
 /* -- wake foam: a coverage plane beside the ripple layer (ocean_ripple_foam.hip) ---------------------------------------------------------- */

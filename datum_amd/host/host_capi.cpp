@@ -418,6 +418,16 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_ripple_dispersion(void *c, int mode, float g)
+  {
+    try
+    {
+      set_ocean_ripple_dispersion(static_cast<HostContext*>(c)->context, static_cast<OceanRippleDispersion>(mode), g);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_center_ocean_ripples(void *c, float x, float y)
   {
     try

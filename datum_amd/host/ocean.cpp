@@ -994,6 +994,14 @@ void set_ocean_ripples(OceanContext &context, int R, float cellsize)
   check(context.hip, datum_ocean_set_ripples(context.hip, R, cellsize), "datum_ocean_set_ripples");
 }
 
+void set_ocean_ripple_dispersion(OceanContext &context, OceanRippleDispersion mode, float g)
+{
+  if (!context.ready)
+    throw runtime_error("set_ocean_ripple_dispersion: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_set_ripple_dispersion(context.hip, static_cast<int>(mode), g), "datum_ocean_set_ripple_dispersion");
+}
+
 void center_ocean_ripples(OceanContext &context, Vec2 const &centre)
 {
   if (!context.ready)

@@ -563,6 +563,17 @@ void step_ocean_ripple_foam(OceanContext &context, float dt);
 void query_ocean_ripple_foam(OceanContext &context, lml::Vec2 const *positions, std::size_t count, float *coverage);
 void read_ocean_ripple_foam(OceanContext &context, float *plane);
 
+// dispersive ripples (include/datum_ocean_hip.h: "dispersive ripples", the definition there): the mode of step_ocean_ripples and of the
+// layer's share of step_ocean_bodies_coupled -- the wave equation (the default) or deep water, omega^2 = g |k|, with gravity `g`.  Works
+// while the layer is off and survives set_ocean_ripples; writes no state.  Throws before prepare_ocean_context
+enum class OceanRippleDispersion
+{
+  Wave = 0,                               // DATUM_OCEAN_RIPPLE_WAVE
+  Deep = 1,                               // DATUM_OCEAN_RIPPLE_DEEP
+};
+
+void set_ocean_ripple_dispersion(OceanContext &context, OceanRippleDispersion mode, float g = 9.81f);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

@@ -116,6 +116,7 @@ def load():
             "datum_host_reduce_ocean_body_drag": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, I]),
             "datum_host_step_ocean_bodies": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
             "datum_host_set_ocean_ripples": (I, [P, I, F]),
+            "datum_host_set_ocean_ripple_dispersion": (I, [P, I, F]),
             "datum_host_center_ocean_ripples": (I, [P, F, F]),
             "datum_host_deposit_ocean_ripples": (I, [P, P, ctypes.c_size_t]),
             "datum_host_deposit_ocean_body_ripples": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P, I]),
@@ -414,6 +415,10 @@ class OceanContext:
     def set_ocean_ripples(self, R, cellsize=1.0):
         """set_ocean_ripples: the ripple layer with R x R cells of `cellsize` metres (R one of capi.RIPPLE_SIZES), at rest; R = 0 frees it"""
         self._check(self.lib.datum_host_set_ocean_ripples(self.c, R, cellsize))
+
+    def set_ocean_ripple_dispersion(self, mode, g=9.81):
+        """set_ocean_ripple_dispersion: the ripple step's mode, 0 the wave equation (the default) or 1 deep water with gravity g"""
+        self._check(self.lib.datum_host_set_ocean_ripple_dispersion(self.c, int(mode), g))
 
     def center_ocean_ripples(self, x, y):
         """center_ocean_ripples: the window's middle becomes the cell of (x, y); entered cells are zeroed"""

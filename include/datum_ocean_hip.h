@@ -63,7 +63,8 @@ extern "C" {
  *      datum_ocean_ripple_bounds_device, datum_ocean_read_ripple_bounds and datum_ocean_surface_slab_rippled, with the bounded rippled
  *      casts datum_ocean_cast_rays_rippled_bounded and datum_ocean_read_rays_rippled_bounded; then wake foam, datum_ocean_set_ripple_foam,
  *      datum_ocean_set_ripple_foam_params, datum_ocean_step_ripple_foam, datum_ocean_reset_ripple_foam, datum_ocean_ripple_foam_device,
- *      datum_ocean_read_ripple_foam, datum_ocean_sample_ripple_foam and datum_ocean_query_ripple_foam.
+ *      datum_ocean_read_ripple_foam, datum_ocean_sample_ripple_foam and datum_ocean_query_ripple_foam; then dispersive ripples,
+ *      datum_ocean_set_ripple_dispersion and datum_ocean_ripple_deep_weights.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -1113,6 +1114,57 @@ int datum_ocean_ripple_foam_device(datum_ocean_t ctx, void **device_ptr, size_t 
 int datum_ocean_read_ripple_foam(datum_ocean_t ctx, float *plane);
 int datum_ocean_sample_ripple_foam(datum_ocean_t ctx, void const *points_device, size_t n, void *out_device);
 int datum_ocean_query_ripple_foam(datum_ocean_t ctx, float const *points, size_t n, float *out);
+
+/* -- dispersive ripples (added at ABI 9; nothing in the reference) ---------------------------------------------------------------------------
+ * The ripple layer's step is the plain wave equation: c is one speed for every wavelength.  A boat at speed U then drags a Mach cone of
+ * half-angle asin(c/U) and at U < c has no wake pattern at all.  Deep water has ω² = g·|k|: the Kelvin wedge of 19.47° whatever the speed
+ * (here: while the wake's waves stay shorter than about 14 cells, see BELOW),
+ * long waves outrunning short ones in the ring round a dropped crate, transverse waves behind the stern.  DEEP is a second, OPT-IN step mode
+ * of the layer with that dispersion relation -- Tessendorf's iWave idea: the vertical-derivative operator √(−∇²) as a 13 × 13 convolution.
+ * The default mode is DATUM_OCEAN_RIPPLE_WAVE, the step stated under "ripple layer", and in it every call keeps its bits.  Everything that
+ * READS the state is unchanged in either mode: datum_ocean_sample_ripples, the rippled reads, the ripple bounds, wake foam,
+ * datum_ocean_center_ripples and the deposits.
+ *
+ * WEIGHTS.  P = 6 (DATUM_OCEAN_RIPPLE_DEEP_RADIUS).  The quadrant table G[l][k], 0 <= k, l <= 6 (DATUM_OCEAN_RIPPLE_DEEP_WEIGHTS = 49
+ * floats, [l][k]), is built once on the host in double:
+ *   1  G0[l][k] = (1/M²) Σ_a Σ_b |θ_ab| cos(k θ_a) cos(l θ_b)     M = 1024, θ_a = 2π(a − M/2)/M, |θ_ab| = √(θ_a² + θ_b²)
+ *      the truncated Fourier series of the cone, summed separably (over b for every a and l, then over a);
+ *   2  unfold to the 169 weights F(di, dj) = G0[|dj|][|di|], subtract ΣF / 169 from every one, and round each to fp32;
+ *   3  replace the centre by the fp32 value that makes the sum of the 169 fp32 weights, taken in double, the smallest value >= 0: round
+ *      towards that, with one nextafterf upward if needed.
+ * The subtraction is the least-squares correction for Ĝ(0) = 0, where the SYMBOL is Ĝ(θ) = Σ F(di, dj) cos(di·θx) cos(dj·θy): its effect on
+ * the symbol is a Dirichlet kernel concentrated at θ = 0.  Of this table (tests/test_ripple_deep64.py): Ĝ >= 0, with its minimum at θ = 0;
+ * |Ĝ − |θ|| / |θ| <= 0.08 for 0.5 <= |θ| <= 1 and <= 0.02 for 1 <= |θ| <= 3; max Ĝ = 4.30, Σ|F| = 5.37, F(0, 0) ≈ 2.40.
+ * BELOW |θ| ≈ 0.45 (WAVELENGTHS ABOVE 14 CELLS) THE SYMBOL IS QUADRATIC AND SUCH WAVES RUN SLOW: the truncation's price.  The FFT surface
+ * owns those wavelengths.
+ *
+ * THE SUB-STEP.  h, f[k], the sponge index, the first sub-step's e = η + (float)src · 2^-20, the window, the torus and the memset behind the
+ * first launch are exactly datum_ocean_step_ripples'.  Per window cell, every operator one fp32 operation as written, no contraction:
+ *     acc = 0.0f
+ *     for dj = −6 .. 6 (outer), di = −6 .. 6 (inner):   acc = acc + G[|dj|][|di|] · e(I + di, J + dj)     a cell outside the window is 0.0f
+ *     v1  = (η_t − h · (gs · acc)) · f[k]                gs = g / s, rounded once on the host from double
+ *     e1  = e + h · v1                                   the new cell is (e1, v1)
+ *
+ * STABILITY.  Semi-implicit Euler needs h·Ω < 2, and Ω² <= gs · Σ|F|.  A step in DEEP computes h · √(g · Σ|F| / s) in double, Σ|F| from
+ * the 169 fp32 weights, and refuses a value above 1.9 with DATUM_OCEAN_EINVAL.  This replaces the c·h/s > 0.7 check in this mode only; the
+ * rules for dt < 0 and a dt that is not finite stay.
+ *
+ *   set_ripple_dispersion   mode DATUM_OCEAN_RIPPLE_WAVE (0, the default) or DATUM_OCEAN_RIPPLE_DEEP (1); g finite and > 0, default 9.81
+ *                           (as a float); c is unused in DEEP and g in WAVE.  Works while the layer is off, survives
+ *                           datum_ocean_set_ripples, writes no state, enqueues nothing and leaves the ripple bounds' CURRENT mark alone.  A
+ *                           null handle, an unknown mode or a bad g is DATUM_OCEAN_EINVAL and changes nothing.
+ *   ripple_deep_weights     takes NO HANDLE and needs no GPU: the table above, [l][k], 49 floats, the exact weights the kernel uses, for a
+ *                           renderer or a test.  A null pointer is DATUM_OCEAN_EINVAL.
+ * datum_ocean_step_ripples, datum_ocean_step_bodies_coupled and its host twin take the layer's mode.  Coupled stepping's contract holds in
+ * DEEP bit for bit -- K rounds of the reductions and the wake from rippled records, then datum_ocean_step_ripples(h, 1) -- and its refusal
+ * uses the DEEP bound.  A mode switch between two calls behaves as two layers would: the state is common, (η, η_t) in both modes.
+ * LEFT OUT: temporal blocking; finite-depth dispersion (ω² = g·k·tanh(k·d)); radii other than 6; obstacles. */
+#define DATUM_OCEAN_RIPPLE_WAVE 0
+#define DATUM_OCEAN_RIPPLE_DEEP 1
+#define DATUM_OCEAN_RIPPLE_DEEP_RADIUS 6
+#define DATUM_OCEAN_RIPPLE_DEEP_WEIGHTS 49
+int datum_ocean_set_ripple_dispersion(datum_ocean_t ctx, int mode, float g);
+int datum_ocean_ripple_deep_weights(float *quadrant49);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

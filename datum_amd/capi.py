@@ -184,6 +184,10 @@ SYMBOLS = {
     "datum_ocean_read_ripple_foam": (I, [P, P]),
     "datum_ocean_sample_ripple_foam": (I, [P, P, ctypes.c_size_t, P]),
     "datum_ocean_query_ripple_foam": (I, [P, P, ctypes.c_size_t, P]),
+    # ripple walls (added at ABI 9): a byte plane beside the ripple layer
+    "datum_ocean_set_ripple_walls": (I, [P, P, I]),
+    "datum_ocean_ripple_walls_device": (I, [P, ctypes.POINTER(P)]),
+    "datum_ocean_read_ripple_walls": (I, [P, P]),
 }
 
 
@@ -213,6 +217,10 @@ SURFACE_MAX_ITERATIONS = 16
 RIPPLE_SIZES = (64, 128, 256, 512, 1024)
 RIPPLE_WAVE, RIPPLE_DEEP = 0, 1          # DATUM_OCEAN_RIPPLE_WAVE, DATUM_OCEAN_RIPPLE_DEEP: datum_ocean_set_ripple_dispersion's modes
 RIPPLE_RECORD_FLOATS = 8
+# ripple walls (datum_ocean_set_ripple_walls): the kinds, the most records, and the 32-byte datum_ocean_ripple_wall
+RIPPLE_WALL_BOX, RIPPLE_WALL_ELLIPSE = 0, 1
+RIPPLE_MAX_WALLS = 256
+RIPPLE_WALL = np.dtype([("center", np.float32, 2), ("axis", np.float32, 2), ("half", np.float32, 2), ("kind", np.int32), ("reserved", np.int32)])
 RIPPLE_MAX_SUBSTEPS = 16
 RIPPLE_MAX_SPONGE = 64
 
@@ -847,6 +855,26 @@ class Ocean:
         """the step's mode: RIPPLE_WAVE (the default, the wave equation with speed c) or RIPPLE_DEEP (omega^2 = g |k|, a 13 x 13
         convolution); works while the layer is off, survives set_ripples and writes no state"""
         self._check(self.lib.datum_ocean_set_ripple_dispersion(self.h, mode, g))
+
+    def set_ripple_walls(self, walls=None):
+        """obstacles the layer's waves reflect off: `walls` an array of RIPPLE_WALL records (center, axis as (cosine, sine), half, kind
+        RIPPLE_WALL_BOX or RIPPLE_WALL_ELLIPSE), at most RIPPLE_MAX_WALLS; None or an empty array turns walls off.  One launch writes
+        the plane and zeroes the wall cells' state in both state buffers."""
+        w = np.ascontiguousarray(walls if walls is not None else [], RIPPLE_WALL).reshape(-1)
+        self._check(self.lib.datum_ocean_set_ripple_walls(self.h, _ptr(w) if len(w) else None, len(w)))
+
+    def ripple_walls_device(self):
+        """the device pointer of the wall plane (R x R bytes in memory order), None while walls are off"""
+        ptr = P()
+        self._check(self.lib.datum_ocean_ripple_walls_device(self.h, ctypes.byref(ptr)))
+        return ptr.value
+
+    def read_ripple_walls(self):
+        """the wall plane in window order, (R, R) uint8: [j][i] is cell (ox + i, oy + j); blocking"""
+        R = int(round((self.ripples_device()[1] // 8) ** 0.5))
+        out = np.empty((R, R), np.uint8)
+        self._check(self.lib.datum_ocean_read_ripple_walls(self.h, _ptr(out)))
+        return out
 
     def center_ripples(self, x, y):
         """Move the window so that the cell of (x, y) is its middle; the cells that entered are zeroed, none is copied."""

@@ -36,6 +36,7 @@
 #include "ocean_rippled.hip"
 #include "ocean_ripple_bounds.hip"
 #include "ocean_ripple_foam.hip"
+#include "ocean_ripple_wall.hip"
 
 using namespace ocean;
 
@@ -179,6 +180,12 @@ struct datum_ocean_ctx
   float *ripplefoamblock = nullptr;   // the allocation: a guard, the plane, a guard (the guards hold 0xCD bytes; no kernel's resource covers them)
   float *ripplefoam = nullptr;        // the plane: R x R coverage on the layer's torus
   float ripplefoamt1 = 0.04f, ripplefoamk1 = 10.0f, ripplefoamt2 = 0.5f, ripplefoamk2 = 2.0f, ripplefoamdecay = 0.5f;   // datum_ocean_set_ripple_foam_params
+
+  // ripple walls (datum_ocean_set_ripple_walls): nothing is allocated while ripplewall is null; freed with the layer
+  unsigned char *ripplewallblock = nullptr;             // the allocation: a guard, the plane, a guard (256 bytes of 0xCD each; no kernel's resource covers them)
+  unsigned char *ripplewall = nullptr;                  // the plane: R x R bytes on the layer's torus, 1 = wall
+  datum_ocean_ripple_wall *ripplewalllist = nullptr;    // the handle's copy of the records, on the device
+  int ripplewallcount = 0;
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -1020,6 +1027,8 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->ripplesrc);
   (void)hipFree(ctx->rippleboundsblock);
   (void)hipFree(ctx->ripplefoamblock);
+  (void)hipFree(ctx->ripplewallblock);
+  (void)hipFree(ctx->ripplewalllist);
 
   for(Staging &st : ctx->staging)
     (void)hipFree(st.ptr);
@@ -3109,6 +3118,10 @@ namespace
   int clear_ripple_foam(datum_ocean_ctx *ctx);
   int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy);
 
+  // the walls' share of set_ripples and center_ripples ("ripple walls", below): each does nothing while walls are off
+  int free_ripple_walls(datum_ocean_ctx *ctx);
+  int raster_ripple_walls(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero);
+
   // the two state buffers between their guards ("the ripple layer's state buffers", below)
   hipError_t alloc_ripple_state(datum_ocean_ctx *ctx, size_t cells);
   int free_ripple_state(datum_ocean_ctx *ctx);
@@ -3118,6 +3131,10 @@ namespace
     int const rc = free_ripple_foam(ctx);
     if (rc != DATUM_OCEAN_OK)
       return rc;
+
+    int const rcw = free_ripple_walls(ctx);
+    if (rcw != DATUM_OCEAN_OK)
+      return rcw;
 
     int const rcs = free_ripple_state(ctx);
     if (rcs != DATUM_OCEAN_OK)
@@ -3274,6 +3291,7 @@ namespace
   {
     bool deep;
     RippleDeepStepArgs a;
+    unsigned char const *wall;      // the wall plane, null while walls are off
   };
 
   // what a sub-step of length h takes but its two state buffers: src, the grid, c2s2 and the sponge table, rounded once from double,
@@ -3283,6 +3301,7 @@ namespace
   {
     RippleStep r = {};
     r.deep = ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP;
+    r.wall = ctx->ripplewall;
 
     if (r.deep)
     {
@@ -3307,9 +3326,24 @@ namespace
     return r;
   }
 
-  // the one place where the mode chooses the kernel (the name is ocean::launch_ripple_step's: a call site reads the same in either mode)
+  // the one place where the mode and the walls choose the kernel (the name is ocean::launch_ripple_step's: a call site reads the same
+  // in either mode, with walls or without)
   hipError_t launch_ripple_step(RippleStep &r, bool first, hipStream_t stream)
   {
+    if (r.wall && r.deep)
+    {
+      RippleWallDeepStepArgs w = { r.a, r.wall };
+
+      return launch_ripple_deep_step_walls(w, first, stream);
+    }
+
+    if (r.wall)
+    {
+      RippleWallStepArgs w = { r.a.s, r.wall };
+
+      return launch_ripple_step_walls(w, first, stream);
+    }
+
     return r.deep ? ocean::launch_ripple_deep_step(r.a, first, stream) : ocean::launch_ripple_step(r.a.s, first, stream);
   }
 
@@ -3467,6 +3501,10 @@ int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
   HIPCHECK(ctx, launch_ripple_scroll(a, ctx->stream));
 
   rc = scroll_ripple_foam(ctx, a.g, a.oldx, a.oldy);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  rc = raster_ripple_walls(ctx, a.g, false);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -4898,6 +4936,165 @@ namespace
 
     return DATUM_OCEAN_OK;
   }
+}
+
+/* -- ripple walls: a byte plane beside the ripple layer (ocean_ripple_wall.hip) ------------------------------------------------------------ */
+
+namespace
+{
+  // bytes of each guard round the plane: the plane keeps hipMalloc's alignment to that
+  constexpr size_t RIPPLE_WALL_GUARD = 256;
+
+  int free_ripple_walls(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, hipFree(ctx->ripplewallblock));
+    ctx->ripplewallblock = nullptr;
+    ctx->ripplewall = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->ripplewalllist));
+    ctx->ripplewalllist = nullptr;
+    ctx->ripplewallcount = 0;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the whole plane from the handle's list at g's origin, on the handle's stream; with `zero` the wall cells' state in both buffers too
+  int raster_ripple_walls(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
+  {
+    if (!ctx->ripplewall)
+      return DATUM_OCEAN_OK;
+
+    RippleWallRasterArgs a;
+    a.wall = ctx->ripplewall;
+    a.state[0] = ctx->ripplestate[0];
+    a.state[1] = ctx->ripplestate[1];
+    a.walls = ctx->ripplewalllist;
+    a.count = ctx->ripplewallcount;
+    a.zero = zero ? 1 : 0;
+
+    // (with `zero` the launch writes both state buffers: the ripple bounds' record is no longer that of the current one)
+    ctx->rippleboundscurrent = ctx->rippleboundscurrent && !zero;
+    a.g = g;
+    a.s = (float)ctx->ripples;
+
+    HIPCHECK(ctx, launch_ripple_wall_raster(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall const *walls, int count)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_walls: null handle");
+
+  if (count < 0 || count > DATUM_OCEAN_RIPPLE_MAX_WALLS)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_walls: count outside [0, DATUM_OCEAN_RIPPLE_MAX_WALLS]");
+
+  if (count > 0 && !walls)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_walls: null walls");
+
+  for(int k = 0; k < count; ++k)
+  {
+    datum_ocean_ripple_wall const &w = walls[k];
+
+    for(float v : { w.center[0], w.center[1], w.axis[0], w.axis[1], w.half[0], w.half[1] })
+      if (!std::isfinite(v))
+        return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_walls: a field is not finite");
+
+    if (!(w.half[0] > 0.0f && w.half[1] > 0.0f))
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_walls: half must be positive");
+
+    if (w.kind != DATUM_OCEAN_RIPPLE_WALL_BOX && w.kind != DATUM_OCEAN_RIPPLE_WALL_ELLIPSE)
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_walls: kind must be DATUM_OCEAN_RIPPLE_WALL_BOX or DATUM_OCEAN_RIPPLE_WALL_ELLIPSE");
+  }
+
+  int rc = check_ripples(ctx, "datum_ocean_set_ripple_walls");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  rc = free_ripple_walls(ctx);
+  if (rc != DATUM_OCEAN_OK || count == 0)
+    return rc;
+
+  size_t const cells = ripple_cells(ctx), bytes = cells + 2 * RIPPLE_WALL_GUARD;
+
+  hipError_t e = hipMalloc(&ctx->ripplewallblock, bytes);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(ctx->ripplewallblock, 0xCD, bytes, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMalloc(&ctx->ripplewalllist, (size_t)count * sizeof(datum_ocean_ripple_wall));
+  // (the caller's array may go away behind the call: the copy is waited for)
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(ctx->ripplewalllist, walls, (size_t)count * sizeof(datum_ocean_ripple_wall), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(ctx->stream);
+
+  if (e != hipSuccess)
+  {
+    (void)free_ripple_walls(ctx);
+    return fail(ctx, (int)e, "datum_ocean_set_ripple_walls: hipMalloc");
+  }
+
+  ctx->ripplewall = ctx->ripplewallblock + RIPPLE_WALL_GUARD;
+  ctx->ripplewallcount = count;
+
+  return raster_ripple_walls(ctx, ripple_grid(ctx), true);
+}
+
+int datum_ocean_ripple_walls_device(datum_ocean_t ctx, unsigned char const **plane)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_walls_device: null handle");
+
+  if (!plane)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_walls_device: null argument");
+
+  *plane = ctx->ripplewall;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host)
+{
+  int rc = check_ripples(ctx, "datum_ocean_read_ripple_walls");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!ctx->ripplewall)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_read_ripple_walls: walls are off (datum_ocean_set_ripple_walls)");
+
+  if (!host)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_ripple_walls: null argument");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // window order from the torus, as datum_ocean_read_ripple_foam: up to four rectangles, split where the window wraps in memory
+  int const R = ctx->rippleR;
+  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
+
+  unsigned char const *src = ctx->ripplewall;
+
+  size_t const pitch = (size_t)R;
+
+  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
+  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
+
+  for(int j = 0; j < 2; ++j)
+    for(int i = 0; i < 2; ++i)
+      if (w[i] > 0 && h[j] > 0)
+        HIPCHECK(ctx, hipMemcpy2DAsync(host + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i], (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
 }
 
 /* -- wake foam: a coverage plane beside the ripple layer (ocean_ripple_foam.hip) ---------------------------------------------------------- */

@@ -428,6 +428,26 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_ripple_walls(void *c, void const *walls, size_t count)
+  {
+    try
+    {
+      set_ocean_ripple_walls(static_cast<HostContext*>(c)->context, static_cast<OceanRippleWall const*>(walls), count);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_read_ocean_ripple_walls(void *c, unsigned char *plane)
+  {
+    try
+    {
+      read_ocean_ripple_walls(static_cast<HostContext*>(c)->context, plane);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_center_ocean_ripples(void *c, float x, float y)
   {
     try

@@ -1002,6 +1002,25 @@ void set_ocean_ripple_dispersion(OceanContext &context, OceanRippleDispersion mo
   check(context.hip, datum_ocean_set_ripple_dispersion(context.hip, static_cast<int>(mode), g), "datum_ocean_set_ripple_dispersion");
 }
 
+void set_ocean_ripple_walls(OceanContext &context, OceanRippleWall const *walls, size_t count)
+{
+  if (!context.ready)
+    throw runtime_error("set_ocean_ripple_walls: the context is not prepared (prepare_ocean_context)");
+
+  if (count > DATUM_OCEAN_RIPPLE_MAX_WALLS)
+    throw runtime_error("set_ocean_ripple_walls: more than DATUM_OCEAN_RIPPLE_MAX_WALLS records");
+
+  check(context.hip, datum_ocean_set_ripple_walls(context.hip, walls, (int)count), "datum_ocean_set_ripple_walls");
+}
+
+void read_ocean_ripple_walls(OceanContext &context, unsigned char *plane)
+{
+  if (!context.ready)
+    throw runtime_error("read_ocean_ripple_walls: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_read_ripple_walls(context.hip, plane), "datum_ocean_read_ripple_walls");
+}
+
 void center_ocean_ripples(OceanContext &context, Vec2 const &centre)
 {
   if (!context.ready)

@@ -574,6 +574,14 @@ enum class OceanRippleDispersion
 
 void set_ocean_ripple_dispersion(OceanContext &context, OceanRippleDispersion mode, float g = 9.81f);
 
+// ripple walls (include/datum_ocean_hip.h: "ripple walls", the definition there): obstacles the layer's waves reflect off, boxes and
+// ellipses whose axis the caller gives as (cosine, sine); a harbour is a list of boxes.  count == 0 turns walls off.  The read returns the
+// R x R byte plane in window order.  Both throw before prepare_ocean_context and while the layer is off
+typedef datum_ocean_ripple_wall OceanRippleWall;
+
+void set_ocean_ripple_walls(OceanContext &context, OceanRippleWall const *walls, size_t count);
+void read_ocean_ripple_walls(OceanContext &context, unsigned char *plane /* [R][R] */);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

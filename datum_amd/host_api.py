@@ -117,6 +117,8 @@ def load():
             "datum_host_step_ocean_bodies": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
             "datum_host_set_ocean_ripples": (I, [P, I, F]),
             "datum_host_set_ocean_ripple_dispersion": (I, [P, I, F]),
+            "datum_host_set_ocean_ripple_walls": (I, [P, P, ctypes.c_size_t]),
+            "datum_host_read_ocean_ripple_walls": (I, [P, P]),
             "datum_host_center_ocean_ripples": (I, [P, F, F]),
             "datum_host_deposit_ocean_ripples": (I, [P, P, ctypes.c_size_t]),
             "datum_host_deposit_ocean_body_ripples": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P, I]),
@@ -419,6 +421,17 @@ class OceanContext:
     def set_ocean_ripple_dispersion(self, mode, g=9.81):
         """set_ocean_ripple_dispersion: the ripple step's mode, 0 the wave equation (the default) or 1 deep water with gravity g"""
         self._check(self.lib.datum_host_set_ocean_ripple_dispersion(self.c, int(mode), g))
+
+    def set_ocean_ripple_walls(self, walls=None):
+        """set_ocean_ripple_walls: `walls` an array of capi.RIPPLE_WALL records (OceanRippleWall); None or empty turns walls off"""
+        w = np.ascontiguousarray(walls if walls is not None else [], capi.RIPPLE_WALL).reshape(-1)
+        self._check(self.lib.datum_host_set_ocean_ripple_walls(self.c, w.ctypes.data_as(P) if len(w) else None, len(w)))
+
+    def read_ocean_ripple_walls(self, R):
+        """read_ocean_ripple_walls: the (R, R) uint8 wall plane in window order"""
+        out = np.empty((R, R), np.uint8)
+        self._check(self.lib.datum_host_read_ocean_ripple_walls(self.c, out.ctypes.data_as(P)))
+        return out
 
     def center_ocean_ripples(self, x, y):
         """center_ocean_ripples: the window's middle becomes the cell of (x, y); entered cells are zeroed"""

@@ -64,7 +64,8 @@ extern "C" {
  *      casts datum_ocean_cast_rays_rippled_bounded and datum_ocean_read_rays_rippled_bounded; then wake foam, datum_ocean_set_ripple_foam,
  *      datum_ocean_set_ripple_foam_params, datum_ocean_step_ripple_foam, datum_ocean_reset_ripple_foam, datum_ocean_ripple_foam_device,
  *      datum_ocean_read_ripple_foam, datum_ocean_sample_ripple_foam and datum_ocean_query_ripple_foam; then dispersive ripples,
- *      datum_ocean_set_ripple_dispersion and datum_ocean_ripple_deep_weights.
+ *      datum_ocean_set_ripple_dispersion and datum_ocean_ripple_deep_weights; then ripple walls, datum_ocean_set_ripple_walls,
+ *      datum_ocean_ripple_walls_device and datum_ocean_read_ripple_walls.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -1158,13 +1159,77 @@ int datum_ocean_query_ripple_foam(datum_ocean_t ctx, float const *points, size_t
  * datum_ocean_step_ripples, datum_ocean_step_bodies_coupled and its host twin take the layer's mode.  Coupled stepping's contract holds in
  * DEEP bit for bit -- K rounds of the reductions and the wake from rippled records, then datum_ocean_step_ripples(h, 1) -- and its refusal
  * uses the DEEP bound.  A mode switch between two calls behaves as two layers would: the state is common, (η, η_t) in both modes.
- * LEFT OUT: temporal blocking; finite-depth dispersion (ω² = g·k·tanh(k·d)); radii other than 6; obstacles. */
+ * LEFT OUT: temporal blocking; finite-depth dispersion (ω² = g·k·tanh(k·d)); radii other than 6; obstacles
+ * (no longer left out: "ripple walls", below). */
 #define DATUM_OCEAN_RIPPLE_WAVE 0
 #define DATUM_OCEAN_RIPPLE_DEEP 1
 #define DATUM_OCEAN_RIPPLE_DEEP_RADIUS 6
 #define DATUM_OCEAN_RIPPLE_DEEP_WEIGHTS 49
 int datum_ocean_set_ripple_dispersion(datum_ocean_t ctx, int mode, float g);
 int datum_ocean_ripple_deep_weights(float *quadrant49);
+
+/* -- ripple walls (added at ABI 9; nothing in the reference) -----------------------------------------------------------------------------------
+ * Obstacles the ripple layer's waves reflect off: piers, quays, rocks, a harbour wall.  OPT-IN: while no list is set nothing is allocated,
+ * nothing more is launched, and every call keeps its bits in both step modes.  Every reader of the layer (mesh, query, ray cast, bounds,
+ * wake foam, coupled bodies) only reads the state, so walls in the step serve all of them.
+ *
+ * THE PLANE.  R × R bytes, 0 water, 1 wall; world cell (I, J) lives at the state's place on the torus, (J mod R)·R + (I mod R).
+ *
+ * THE SHAPES.  A wall is a 32-byte datum_ocean_ripple_wall; at most DATUM_OCEAN_RIPPLE_MAX_WALLS = 256 of them.  `axis` is the shape's
+ * local x direction, GIVEN BY THE CALLER AS (cosine, sine): the library takes no sine or cosine of its own and DOES NOT NORMALISE the
+ * axis -- a non-unit axis scales the shape.  `half` are the half extents (box) or semi-axes (ellipse) along the local x and y.
+ *
+ * THE RASTER RULE.  For world cell (I, J), s the fp32 cell side given to datum_ocean_set_ripples, every operator one fp32 operation as
+ * written, no contraction, no division:
+ *     x  = ((float)I + 0.5f) · s          y  = ((float)J + 0.5f) · s
+ *     dx = x − center[0]                  dy = y − center[1]
+ *     u  = dx·axis[0] + dy·axis[1]        v  = dy·axis[0] − dx·axis[1]
+ *     BOX:      |u| <= half[0] && |v| <= half[1]
+ *     ELLIPSE:  a = u·half[1], b = v·half[0], r = half[0]·half[1];   a·a + b·b <= r·r
+ * A cell is wall if any record covers its centre.  The plane is a function of (list, world cell) only: after any
+ * datum_ocean_center_ripples it equals that function at the new origin, cells that entered and a jump of R cells or more included (the
+ * call rasterises the whole plane again behind the scroll).
+ *
+ * THE SUB-STEP WITH WALLS.  h, f[k], the sponge, the window test, the first sub-step's e = η + (float)src · 2^-20, the torus and the
+ * memset behind the first launch are datum_ocean_step_ripples', unchanged.
+ *   - a wall cell's new state is (+0.0f, +0.0f) in both modes; its src is ignored (a deposit that lands on a wall cell is lost, uncounted);
+ *   - reading a neighbour: outside the WINDOW -> 0.0f, the wall flag of the torus-aliased cell is not consulted; else wall -> the rule of
+ *     the mode; else its height;
+ *   - WAVE: a wall neighbour reads as the cell's own e -- a hard vertical wall, the mirror plane the face between the two cells, the wave
+ *     reflected without a change of sign; the update is the wave step's as it stands;
+ *   - DEEP: a wall cell reads 0.0f in the convolution, the pending deposit of a first sub-step included (iWave's obstruction); the sum
+ *     and the update are the DEEP step's as they stand, over an image in which wall cells are zero.
+ * No new stability refusal: in WAVE the mirrored operator is the graph Laplacian of the open cells (symmetric, eigenvalues in [−8, 0]),
+ * in DEEP a principal submatrix of the windowed operator (symmetric, the same bound gs·Σ|F|).
+ *
+ *   set_ripple_walls       `walls` is a HOST pointer to `count` records; the handle keeps its own copy.  count == 0 turns walls off and
+ *                          frees the plane.  Otherwise ONE launch on the handle's stream writes the plane and makes the state of every wall
+ *                          cell (+0, +0) in BOTH state buffers; the ripple bounds' CURRENT mark is cleared; src, the wake-foam plane and
+ *                          everything else are left alone.  DATUM_OCEAN_EINVAL: a null handle, count < 0 or above the maximum, null walls
+ *                          with count > 0, a field that is not finite, a half that is not > 0, an unknown kind.  DATUM_OCEAN_ESTATE while
+ *                          the layer is off.  datum_ocean_set_ripples with any R drops the walls, as it drops the wake foam;
+ *                          datum_ocean_reset_ripples keeps them.
+ *   ripple_walls_device    *plane = the device plane in memory order, R·R bytes, null while walls are off; a renderer masks with it.
+ *                          Stable until the next set_ripple_walls or set_ripples.
+ *   read_ripple_walls      the plane to the HOST in window order, [j][i] for cell (ox + i, oy + j), as datum_ocean_read_ripple_foam;
+ *                          blocking.  DATUM_OCEAN_ESTATE while walls are off.
+ * LEFT OUT: moving walls and hull footprints as walls (a wall that moves must displace the water it covers; the wake deposit is the model
+ * for hulls); fractional obstruction; walls in the bilinear sample (it blends the wall cell's zero as it is); walls in wake foam and the
+ * ripple bounds (they see wall cells as water at rest); a count of deposits lost on wall cells; finite depth; a shoreline. */
+#define DATUM_OCEAN_RIPPLE_WALL_BOX 0
+#define DATUM_OCEAN_RIPPLE_WALL_ELLIPSE 1
+#define DATUM_OCEAN_RIPPLE_MAX_WALLS 256
+typedef struct datum_ocean_ripple_wall
+{
+  float center[2];      /* world metres */
+  float axis[2];        /* the local x direction: (cosine, sine), not normalised by the library */
+  float half[2];        /* half extents / semi-axes along the local x and y, each > 0 */
+  int kind;             /* DATUM_OCEAN_RIPPLE_WALL_BOX or DATUM_OCEAN_RIPPLE_WALL_ELLIPSE */
+  int reserved;         /* not read */
+} datum_ocean_ripple_wall;
+int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall const *walls, int count);
+int datum_ocean_ripple_walls_device(datum_ocean_t ctx, unsigned char const **plane);
+int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

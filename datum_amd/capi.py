@@ -188,6 +188,10 @@ SYMBOLS = {
     "datum_ocean_set_ripple_walls": (I, [P, P, I]),
     "datum_ocean_ripple_walls_device": (I, [P, ctypes.POINTER(P)]),
     "datum_ocean_read_ripple_walls": (I, [P, P]),
+    # the ripple bed (added at ABI 9): a depth plane and a surf plane beside the ripple layer
+    "datum_ocean_set_ripple_bed": (I, [P, P, P]),
+    "datum_ocean_ripple_bed_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
+    "datum_ocean_read_ripple_bed": (I, [P, P, P]),
 }
 
 
@@ -221,6 +225,11 @@ RIPPLE_RECORD_FLOATS = 8
 RIPPLE_WALL_BOX, RIPPLE_WALL_ELLIPSE = 0, 1
 RIPPLE_MAX_WALLS = 256
 RIPPLE_WALL = np.dtype([("center", np.float32, 2), ("axis", np.float32, 2), ("half", np.float32, 2), ("kind", np.int32), ("reserved", np.int32)])
+# the ripple bed (datum_ocean_set_ripple_bed): the surf levels, the map's largest side, and the 40-byte datum_ocean_ripple_bed
+RIPPLE_SURF_LEVELS = 16
+RIPPLE_BED_MAX_SIDE = 4096
+RIPPLE_BED = np.dtype([("width", np.int32), ("height", np.int32), ("origin", np.float32, 2), ("texel", np.float32), ("outside", np.float32),
+                       ("max_depth", np.float32), ("dry_depth", np.float32), ("surf_depth", np.float32), ("surf_gamma", np.float32)])
 RIPPLE_MAX_SUBSTEPS = 16
 RIPPLE_MAX_SPONGE = 64
 
@@ -875,6 +884,33 @@ class Ocean:
         out = np.empty((R, R), np.uint8)
         self._check(self.lib.datum_ocean_read_ripple_walls(self.h, _ptr(out)))
         return out
+
+    def set_ripple_bed(self, bed=None, depths=None):
+        """still-water depth under the layer: `bed` a RIPPLE_BED record (width, height, origin, texel, outside, max_depth, dry_depth,
+        surf_depth, surf_gamma), `depths` its (height, width) float32 map in metres, positive down; None turns the bed off.  One launch
+        rasters the depth and surf planes and zeroes the solid cells' state in both state buffers.  WAVE mode only."""
+        if bed is None:
+            self._check(self.lib.datum_ocean_set_ripple_bed(self.h, None, None))
+            return
+        b = np.array([bed], RIPPLE_BED).reshape(-1)[:1]
+        d = np.ascontiguousarray(depths, np.float32)
+        if d.size != int(b["width"][0]) * int(b["height"][0]):
+            raise ValueError("set_ripple_bed: depths must hold width * height values")
+        self._check(self.lib.datum_ocean_set_ripple_bed(self.h, _ptr(b), _ptr(d)))
+
+    def ripple_bed_device(self):
+        """(depth pointer, surf pointer, cells): the device planes in memory order, R * R floats and R * R bytes; (None, None, 0) while
+        the bed is off"""
+        depth, surf, cells = P(), P(), ctypes.c_size_t()
+        self._check(self.lib.datum_ocean_ripple_bed_device(self.h, ctypes.byref(depth), ctypes.byref(surf), ctypes.byref(cells)))
+        return depth.value, surf.value, cells.value
+
+    def read_ripple_bed(self):
+        """(depth (R, R) float32, surf (R, R) uint8) in window order: [j][i] is cell (ox + i, oy + j); blocking"""
+        R = int(round((self.ripples_device()[1] // 8) ** 0.5))
+        depth, surf = np.empty((R, R), np.float32), np.empty((R, R), np.uint8)
+        self._check(self.lib.datum_ocean_read_ripple_bed(self.h, _ptr(depth), _ptr(surf)))
+        return depth, surf
 
     def center_ripples(self, x, y):
         """Move the window so that the cell of (x, y) is its middle; the cells that entered are zeroed, none is copied."""

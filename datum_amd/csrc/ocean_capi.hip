@@ -37,6 +37,7 @@
 #include "ocean_ripple_bounds.hip"
 #include "ocean_ripple_foam.hip"
 #include "ocean_ripple_wall.hip"
+#include "ocean_ripple_bed.hip"
 
 using namespace ocean;
 
@@ -186,6 +187,14 @@ struct datum_ocean_ctx
   unsigned char *ripplewall = nullptr;                  // the plane: R x R bytes on the layer's torus, 1 = wall
   datum_ocean_ripple_wall *ripplewalllist = nullptr;    // the handle's copy of the records, on the device
   int ripplewallcount = 0;
+
+  // the ripple bed (datum_ocean_set_ripple_bed): nothing is allocated while ripplebed is null; freed with the layer
+  float *ripplebedblock = nullptr;                      // the allocation: a guard, the depth plane, a guard (256 bytes of 0xCD each; no kernel's resource covers them)
+  float *ripplebed = nullptr;                           // the depth plane: R x R floats on the layer's torus, +0 = solid
+  unsigned char *ripplesurfblock = nullptr;             // a guard, the surf plane, a guard
+  unsigned char *ripplesurf = nullptr;                  // the surf plane: R x R bytes, 0 .. DATUM_OCEAN_RIPPLE_SURF_LEVELS
+  float *ripplebedmap = nullptr;                        // the handle's copy of the map, on the device
+  datum_ocean_ripple_bed ripplebedparams = {};
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -1029,6 +1038,9 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->ripplefoamblock);
   (void)hipFree(ctx->ripplewallblock);
   (void)hipFree(ctx->ripplewalllist);
+  (void)hipFree(ctx->ripplebedblock);
+  (void)hipFree(ctx->ripplesurfblock);
+  (void)hipFree(ctx->ripplebedmap);
 
   for(Staging &st : ctx->staging)
     (void)hipFree(st.ptr);
@@ -3122,6 +3134,13 @@ namespace
   int free_ripple_walls(datum_ocean_ctx *ctx);
   int raster_ripple_walls(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero);
 
+  // the bed's share of set_ripples, center_ripples and set_ripple_walls ("ripple bed", below): each does nothing while the bed is off
+  int free_ripple_bed(datum_ocean_ctx *ctx);
+  int raster_ripple_bed(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero);
+
+  // the bed's share of a sub-step's arguments: the surf table for a sub-step of length h, rounded once from double
+  void fill_ripple_surf(datum_ocean_ctx const *ctx, float h, float *fsurf);
+
   // the two state buffers between their guards ("the ripple layer's state buffers", below)
   hipError_t alloc_ripple_state(datum_ocean_ctx *ctx, size_t cells);
   int free_ripple_state(datum_ocean_ctx *ctx);
@@ -3135,6 +3154,10 @@ namespace
     int const rcw = free_ripple_walls(ctx);
     if (rcw != DATUM_OCEAN_OK)
       return rcw;
+
+    int const rcb = free_ripple_bed(ctx);
+    if (rcb != DATUM_OCEAN_OK)
+      return rcb;
 
     int const rcs = free_ripple_state(ctx);
     if (rcs != DATUM_OCEAN_OK)
@@ -3241,10 +3264,13 @@ namespace
     return DATUM_OCEAN_OK;
   }
 
-  // c h / s in double, which a step holds against the scheme's stability bound
+  // c h / s in double, which a step holds against the scheme's stability bound; over a bed c is the fastest speed it allows,
+  // sqrt(g max_depth)
   double ripple_courant(datum_ocean_ctx const *ctx, float h)
   {
-    return ctx->ripplec * (double)h / ctx->ripples;
+    double const c = ctx->ripplebed ? std::sqrt(ctx->rippleg * (double)ctx->ripplebedparams.max_depth) : ctx->ripplec;
+
+    return c * (double)h / ctx->ripples;
   }
 
   // the DEEP step's weights (ocean_ripple_deep.h), built by the first call that asks for them: the table and Sum |F| of its 169 weights
@@ -3292,6 +3318,10 @@ namespace
     bool deep;
     RippleDeepStepArgs a;
     unsigned char const *wall;      // the wall plane, null while walls are off
+    float const *bed;               // the bed's depth plane, null while the bed is off; then its surf plane, g / s^2 and the surf table
+    unsigned char const *surf;
+    float gs2;
+    float fsurf[RIPPLE_SURF_LEVELS + 1];
   };
 
   // what a sub-step of length h takes but its two state buffers: src, the grid, c2s2 and the sponge table, rounded once from double,
@@ -3302,6 +3332,14 @@ namespace
     RippleStep r = {};
     r.deep = ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP;
     r.wall = ctx->ripplewall;
+    r.bed = ctx->ripplebed;
+    r.surf = ctx->ripplesurf;
+
+    if (r.bed)
+    {
+      r.gs2 = (float)(ctx->rippleg / (ctx->ripples * ctx->ripples));
+      fill_ripple_surf(ctx, h, r.fsurf);
+    }
 
     if (r.deep)
     {
@@ -3326,10 +3364,23 @@ namespace
     return r;
   }
 
-  // the one place where the mode and the walls choose the kernel (the name is ocean::launch_ripple_step's: a call site reads the same
-  // in either mode, with walls or without)
+  // the one place where the mode, the walls and the bed choose the kernel (the name is ocean::launch_ripple_step's: a call site reads
+  // the same in either mode, with walls or without, over a bed or not).  The bed's kernel runs whether walls are on or off: they are in
+  // its depths; the bed and the DEEP mode do not meet (both setters refuse)
   hipError_t launch_ripple_step(RippleStep &r, bool first, hipStream_t stream)
   {
+    if (r.bed)
+    {
+      RippleBedStepArgs b;
+      b.s = r.a.s;
+      b.depth = r.bed;
+      b.surf = r.surf;
+      b.gs2 = r.gs2;
+      std::memcpy(b.fsurf, r.fsurf, sizeof b.fsurf);
+
+      return launch_ripple_bed_step(b, first, stream);
+    }
+
     if (r.wall && r.deep)
     {
       RippleWallDeepStepArgs w = { r.a, r.wall };
@@ -3451,6 +3502,9 @@ int datum_ocean_set_ripple_dispersion(datum_ocean_t ctx, int mode, float g)
   if (!std::isfinite(g) || !(g > 0.0f))
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_dispersion: g must be finite and positive");
 
+  if (mode == DATUM_OCEAN_RIPPLE_DEEP && ctx->ripplebed)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_ripple_dispersion: a ripple bed is set, and the bed and the DEEP mode do not combine (datum_ocean_set_ripple_bed)");
+
   ctx->rippledispersion = mode;
   ctx->rippleg = (double)g;
 
@@ -3505,6 +3559,10 @@ int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
     return rc;
 
   rc = raster_ripple_walls(ctx, a.g, false);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  rc = raster_ripple_bed(ctx, a.g, false);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -5019,8 +5077,12 @@ int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall cons
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   rc = free_ripple_walls(ctx);
-  if (rc != DATUM_OCEAN_OK || count == 0)
+  if (rc != DATUM_OCEAN_OK)
     return rc;
+
+  // (the wall byte enters the bed's depth: with or without walls now, a bed is rastered again)
+  if (count == 0)
+    return raster_ripple_bed(ctx, ripple_grid(ctx), false);
 
   size_t const cells = ripple_cells(ctx), bytes = cells + 2 * RIPPLE_WALL_GUARD;
 
@@ -5044,7 +5106,9 @@ int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall cons
   ctx->ripplewall = ctx->ripplewallblock + RIPPLE_WALL_GUARD;
   ctx->ripplewallcount = count;
 
-  return raster_ripple_walls(ctx, ripple_grid(ctx), true);
+  rc = raster_ripple_walls(ctx, ripple_grid(ctx), true);
+
+  return rc != DATUM_OCEAN_OK ? rc : raster_ripple_bed(ctx, ripple_grid(ctx), false);
 }
 
 int datum_ocean_ripple_walls_device(datum_ocean_t ctx, unsigned char const **plane)
@@ -5089,6 +5153,214 @@ int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host)
     for(int i = 0; i < 2; ++i)
       if (w[i] > 0 && h[j] > 0)
         HIPCHECK(ctx, hipMemcpy2DAsync(host + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i], (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}
+
+/* -- the ripple bed: depth and surf planes beside the ripple layer (ocean_ripple_bed.hip) ------------------------------------------------- */
+
+namespace
+{
+  // bytes of each guard round either plane: the planes keep hipMalloc's alignment to that
+  constexpr size_t RIPPLE_BED_GUARD = 256;
+
+  int free_ripple_bed(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, hipFree(ctx->ripplebedblock));
+    ctx->ripplebedblock = nullptr;
+    ctx->ripplebed = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->ripplesurfblock));
+    ctx->ripplesurfblock = nullptr;
+    ctx->ripplesurf = nullptr;
+    HIPCHECK(ctx, hipFree(ctx->ripplebedmap));
+    ctx->ripplebedmap = nullptr;
+    ctx->ripplebedparams = {};
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // fsurf[q] = 1 / (1 + h surf_gamma (q / 16)^2), in double beside the sponge table's entries: exactly 1 at q = 0
+  void fill_ripple_surf(datum_ocean_ctx const *ctx, float h, float *fsurf)
+  {
+    for(int q = 0; q <= RIPPLE_SURF_LEVELS; ++q)
+    {
+      double const u = (double)q / RIPPLE_SURF_LEVELS;
+
+      fsurf[q] = (float)(1.0 / (1.0 + (double)h * ((double)ctx->ripplebedparams.surf_gamma * (u * u))));
+    }
+  }
+
+  // both planes whole from the handle's map, its parameters and the wall plane at g's origin, on the handle's stream (behind the wall
+  // raster, where there is one); with `zero` the solid cells' state in both buffers too
+  int raster_ripple_bed(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
+  {
+    if (!ctx->ripplebed)
+      return DATUM_OCEAN_OK;
+
+    datum_ocean_ripple_bed const &p = ctx->ripplebedparams;
+
+    RippleBedRasterArgs a;
+    a.depth = ctx->ripplebed;
+    a.surf = ctx->ripplesurf;
+    a.state[0] = ctx->ripplestate[0];
+    a.state[1] = ctx->ripplestate[1];
+    a.map = ctx->ripplebedmap;
+    a.wall = ctx->ripplewall;
+    a.zero = zero ? 1 : 0;
+
+    // (with `zero` the launch writes both state buffers: the ripple bounds' record is no longer that of the current one)
+    ctx->rippleboundscurrent = ctx->rippleboundscurrent && !zero;
+    a.g = g;
+    a.s = (float)ctx->ripples;
+
+    a.b.width = p.width;
+    a.b.height = p.height;
+    a.b.ox = p.origin[0];
+    a.b.oy = p.origin[1];
+    a.b.invt = (float)(1.0 / (double)p.texel);
+    a.b.outside = p.outside;
+    a.b.max_depth = p.max_depth;
+    a.b.dry_depth = p.dry_depth;
+    a.b.surf_depth = p.surf_depth;
+    a.b.invsurf = p.surf_depth > 0.0f ? (float)(1.0 / (double)p.surf_depth) : 0.0f;
+
+    HIPCHECK(ctx, launch_ripple_bed_raster(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_set_ripple_bed(datum_ocean_t ctx, datum_ocean_ripple_bed const *bed, float const *depths_host)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: null handle");
+
+  if (bed)
+  {
+    if (bed->width < 2 || bed->width > DATUM_OCEAN_RIPPLE_BED_MAX_SIDE || bed->height < 2 || bed->height > DATUM_OCEAN_RIPPLE_BED_MAX_SIDE)
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: width and height must lie in [2, DATUM_OCEAN_RIPPLE_BED_MAX_SIDE]");
+
+    if (!depths_host)
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: null depths_host");
+
+    if (!(std::isfinite(bed->texel) && bed->texel > 0.0f))
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: texel must be finite and positive");
+
+    if (!(std::isfinite(bed->origin[0]) && std::isfinite(bed->origin[1]) && std::isfinite(bed->outside)))
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: origin and outside must be finite");
+
+    if (!(std::isfinite(bed->max_depth) && bed->max_depth > 0.0f))
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: max_depth must be finite and positive");
+
+    if (!(bed->dry_depth > 0.0f && bed->dry_depth <= bed->max_depth))
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: dry_depth must lie in (0, max_depth]");
+
+    if (!std::isfinite(bed->surf_depth) || bed->surf_depth < 0.0f || !std::isfinite(bed->surf_gamma) || bed->surf_gamma < 0.0f)
+      return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: surf_depth and surf_gamma must be finite and not negative");
+
+    size_t const texels = (size_t)bed->width * bed->height;
+
+    for(size_t k = 0; k < texels; ++k)
+      if (!std::isfinite(depths_host[k]))
+        return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_bed: a map value is not finite");
+  }
+
+  int rc = check_ripples(ctx, "datum_ocean_set_ripple_bed");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (bed && ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_ripple_bed: the layer's mode is DATUM_OCEAN_RIPPLE_DEEP, and the bed and the DEEP mode do not combine");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  rc = free_ripple_bed(ctx);
+  if (rc != DATUM_OCEAN_OK || !bed)
+    return rc;
+
+  size_t const cells = ripple_cells(ctx), texels = (size_t)bed->width * bed->height;
+  size_t const dbytes = cells * sizeof(float) + 2 * RIPPLE_BED_GUARD, qbytes = cells + 2 * RIPPLE_BED_GUARD;
+
+  hipError_t e = hipMalloc(&ctx->ripplebedblock, dbytes);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(ctx->ripplebedblock, 0xCD, dbytes, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMalloc(&ctx->ripplesurfblock, qbytes);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(ctx->ripplesurfblock, 0xCD, qbytes, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMalloc(&ctx->ripplebedmap, texels * sizeof(float));
+  // (the caller's array may go away behind the call: the copy is waited for)
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(ctx->ripplebedmap, depths_host, texels * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(ctx->stream);
+
+  if (e != hipSuccess)
+  {
+    (void)free_ripple_bed(ctx);
+    return fail(ctx, (int)e, "datum_ocean_set_ripple_bed: hipMalloc");
+  }
+
+  ctx->ripplebed = ctx->ripplebedblock + RIPPLE_BED_GUARD / sizeof(float);
+  ctx->ripplesurf = ctx->ripplesurfblock + RIPPLE_BED_GUARD;
+  ctx->ripplebedparams = *bed;
+
+  return raster_ripple_bed(ctx, ripple_grid(ctx), true);
+}
+
+int datum_ocean_ripple_bed_device(datum_ocean_t ctx, void **depth, void **surf, size_t *cells)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_bed_device: null handle");
+
+  if (depth)
+    *depth = ctx->ripplebed;
+  if (surf)
+    *surf = ctx->ripplesurf;
+  if (cells)
+    *cells = ctx->ripplebed ? ripple_cells(ctx) : 0;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_ripple_bed(datum_ocean_t ctx, float *depth, unsigned char *surf)
+{
+  int rc = check_ripples(ctx, "datum_ocean_read_ripple_bed");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!ctx->ripplebed)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_read_ripple_bed: the bed is off (datum_ocean_set_ripple_bed)");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // window order from the torus, as datum_ocean_read_ripple_walls: up to four rectangles a plane, split where the window wraps in memory
+  int const R = ctx->rippleR;
+  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
+
+  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
+  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
+
+  for(int j = 0; j < 2; ++j)
+    for(int i = 0; i < 2; ++i)
+      if (w[i] > 0 && h[j] > 0)
+      {
+        size_t const to = (size_t)dy[j] * R + dx[i], from = (size_t)sy[j] * R + sx[i];
+
+        if (depth)
+          HIPCHECK(ctx, hipMemcpy2DAsync(depth + to, (size_t)R * sizeof(float), ctx->ripplebed + from, (size_t)R * sizeof(float), (size_t)w[i] * sizeof(float), (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+        if (surf)
+          HIPCHECK(ctx, hipMemcpy2DAsync(surf + to, (size_t)R, ctx->ripplesurf + from, (size_t)R, (size_t)w[i], (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+      }
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 

@@ -448,6 +448,26 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_ripple_bed(void *c, void const *bed, float const *depths)
+  {
+    try
+    {
+      set_ocean_ripple_bed(static_cast<HostContext*>(c)->context, static_cast<OceanRippleBed const*>(bed), depths);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_read_ocean_ripple_bed(void *c, float *depth, unsigned char *surf)
+  {
+    try
+    {
+      read_ocean_ripple_bed(static_cast<HostContext*>(c)->context, depth, surf);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_center_ocean_ripples(void *c, float x, float y)
   {
     try

@@ -1021,6 +1021,22 @@ void read_ocean_ripple_walls(OceanContext &context, unsigned char *plane)
   check(context.hip, datum_ocean_read_ripple_walls(context.hip, plane), "datum_ocean_read_ripple_walls");
 }
 
+void set_ocean_ripple_bed(OceanContext &context, OceanRippleBed const *bed, float const *depths)
+{
+  if (!context.ready)
+    throw runtime_error("set_ocean_ripple_bed: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_set_ripple_bed(context.hip, bed, depths), "datum_ocean_set_ripple_bed");
+}
+
+void read_ocean_ripple_bed(OceanContext &context, float *depth, unsigned char *surf)
+{
+  if (!context.ready)
+    throw runtime_error("read_ocean_ripple_bed: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_read_ripple_bed(context.hip, depth, surf), "datum_ocean_read_ripple_bed");
+}
+
 void center_ocean_ripples(OceanContext &context, Vec2 const &centre)
 {
   if (!context.ready)

@@ -582,6 +582,15 @@ typedef datum_ocean_ripple_wall OceanRippleWall;
 void set_ocean_ripple_walls(OceanContext &context, OceanRippleWall const *walls, size_t count);
 void read_ocean_ripple_walls(OceanContext &context, unsigned char *plane /* [R][R] */);
 
+// the ripple bed (include/datum_ocean_hip.h: "ripple bed", the definition there): still-water depth under the layer from a host map of
+// bed->width x bed->height floats, positive down; waves shoal, refract and break on it.  A null bed turns it off.  WAVE mode only.  The
+// read returns the effective-depth plane and the surf-level plane in window order; either may be null.  Both throw before
+// prepare_ocean_context and while the layer is off
+typedef datum_ocean_ripple_bed OceanRippleBed;
+
+void set_ocean_ripple_bed(OceanContext &context, OceanRippleBed const *bed, float const *depths);
+void read_ocean_ripple_bed(OceanContext &context, float *depth /* [R][R] */, unsigned char *surf /* [R][R] */);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

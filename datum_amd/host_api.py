@@ -119,6 +119,8 @@ def load():
             "datum_host_set_ocean_ripple_dispersion": (I, [P, I, F]),
             "datum_host_set_ocean_ripple_walls": (I, [P, P, ctypes.c_size_t]),
             "datum_host_read_ocean_ripple_walls": (I, [P, P]),
+            "datum_host_set_ocean_ripple_bed": (I, [P, P, P]),
+            "datum_host_read_ocean_ripple_bed": (I, [P, P, P]),
             "datum_host_center_ocean_ripples": (I, [P, F, F]),
             "datum_host_deposit_ocean_ripples": (I, [P, P, ctypes.c_size_t]),
             "datum_host_deposit_ocean_body_ripples": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P, I]),
@@ -432,6 +434,23 @@ class OceanContext:
         out = np.empty((R, R), np.uint8)
         self._check(self.lib.datum_host_read_ocean_ripple_walls(self.c, out.ctypes.data_as(P)))
         return out
+
+    def set_ocean_ripple_bed(self, bed=None, depths=None):
+        """set_ocean_ripple_bed: `bed` a capi.RIPPLE_BED record (OceanRippleBed), `depths` its (height, width) float32 map; None turns the bed off"""
+        if bed is None:
+            self._check(self.lib.datum_host_set_ocean_ripple_bed(self.c, None, None))
+            return
+        b = np.array([bed], capi.RIPPLE_BED).reshape(-1)[:1]
+        d = np.ascontiguousarray(depths, np.float32)
+        if d.size != int(b["width"][0]) * int(b["height"][0]):
+            raise ValueError("set_ocean_ripple_bed: depths must hold width * height values")
+        self._check(self.lib.datum_host_set_ocean_ripple_bed(self.c, b.ctypes.data_as(P), d.ctypes.data_as(P)))
+
+    def read_ocean_ripple_bed(self, R):
+        """read_ocean_ripple_bed: the (R, R) float32 depth plane and the (R, R) uint8 surf plane in window order"""
+        depth, surf = np.empty((R, R), np.float32), np.empty((R, R), np.uint8)
+        self._check(self.lib.datum_host_read_ocean_ripple_bed(self.c, depth.ctypes.data_as(P), surf.ctypes.data_as(P)))
+        return depth, surf
 
     def center_ocean_ripples(self, x, y):
         """center_ocean_ripples: the window's middle becomes the cell of (x, y); entered cells are zeroed"""

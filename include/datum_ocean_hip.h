@@ -65,7 +65,8 @@ extern "C" {
  *      datum_ocean_set_ripple_foam_params, datum_ocean_step_ripple_foam, datum_ocean_reset_ripple_foam, datum_ocean_ripple_foam_device,
  *      datum_ocean_read_ripple_foam, datum_ocean_sample_ripple_foam and datum_ocean_query_ripple_foam; then dispersive ripples,
  *      datum_ocean_set_ripple_dispersion and datum_ocean_ripple_deep_weights; then ripple walls, datum_ocean_set_ripple_walls,
- *      datum_ocean_ripple_walls_device and datum_ocean_read_ripple_walls.
+ *      datum_ocean_ripple_walls_device and datum_ocean_read_ripple_walls; then the ripple bed, datum_ocean_set_ripple_bed,
+ *      datum_ocean_ripple_bed_device and datum_ocean_read_ripple_bed.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -1215,7 +1216,8 @@ int datum_ocean_ripple_deep_weights(float *quadrant49);
  *                          blocking.  DATUM_OCEAN_ESTATE while walls are off.
  * LEFT OUT: moving walls and hull footprints as walls (a wall that moves must displace the water it covers; the wake deposit is the model
  * for hulls); fractional obstruction; walls in the bilinear sample (it blends the wall cell's zero as it is); walls in wake foam and the
- * ripple bounds (they see wall cells as water at rest); a count of deposits lost on wall cells; finite depth; a shoreline. */
+ * ripple bounds (they see wall cells as water at rest); a count of deposits lost on wall cells; finite depth; a shoreline.
+ * (Finite depth and a shoreline are no longer left out: "ripple bed", below.) */
 #define DATUM_OCEAN_RIPPLE_WALL_BOX 0
 #define DATUM_OCEAN_RIPPLE_WALL_ELLIPSE 1
 #define DATUM_OCEAN_RIPPLE_MAX_WALLS 256
@@ -1230,6 +1232,88 @@ typedef struct datum_ocean_ripple_wall
 int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall const *walls, int count);
 int datum_ocean_ripple_walls_device(datum_ocean_t ctx, unsigned char const **plane);
 int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host);
+
+/* -- ripple bed (added at ABI 9; nothing in the reference) --------------------------------------------------------------------------------------
+ * Still-water depth under the ripple layer: waves slow, steepen and bend over a shoal and die on a beach.  OPT-IN: while no bed is set
+ * nothing is allocated, the parents' kernels are launched, and every call keeps its bits in both step modes.  Every reader of the layer
+ * (mesh, query, ray cast, bounds, wake foam, coupled bodies) only reads the state, so the bed in the step serves all of them.
+ * The model is variable-depth shallow water, η_tt = ∇·(g·d·∇η): the wave step's five-point stencil with a coefficient per face.
+ *
+ * THE MAP.  `depths_host` is a HOST array of width × height floats, row-major, [j·width + i]: still-water depth in metres, POSITIVE DOWN
+ * (a value <= 0 is land).  2 <= width, height <= DATUM_OCEAN_RIPPLE_BED_MAX_SIDE = 4096.  Texel (0, 0) stands at world `origin`, texel
+ * (i, j) at origin + (i, j)·texel.  `outside` is the depth that a cell off the map reads.  The handle keeps a device copy of the map.
+ *
+ * THE PLANES.  Two on the layer's torus, world cell (I, J) at the state's place (J mod R)·R + (I mod R):
+ *   d   R × R floats: the effective depth, +0.0f where the cell is SOLID (dry land, or a wall);
+ *   q   R × R bytes: the surf level, 0 .. DATUM_OCEAN_RIPPLE_SURF_LEVELS = 16.
+ * Both are a function of (map, parameters, wall plane, world cell) only: after any datum_ocean_center_ripples they equal that function at
+ * the new origin, cells that entered and a jump of R cells or more included.
+ *
+ * THE RASTER RULE.  For world cell (I, J), s the fp32 cell side, every operator one fp32 operation as written, no contraction, no
+ * division; invt = (float)(1.0 / texel) and invsurf = (float)(1.0 / surf_depth) are rounded once on the host from double:
+ *     x = ((float)I + 0.5f) · s           y = ((float)J + 0.5f) · s                  (the centre, as the wall raster has it)
+ *     u = (x − origin[0]) · invt          v = (y − origin[1]) · invt
+ *     u < 0 or u > width − 1 or v < 0 or v > height − 1:   raw = outside
+ *     else  i = min((int)floorf(u), width − 2), j = min((int)floorf(v), height − 2), wu = u − (float)i, wv = v − (float)j,
+ *           c0 = map[j][i], c1 = map[j][i + 1], c2 = map[j + 1][i], c3 = map[j + 1][i + 1]
+ *           a0 = c1 − c0, a1 = c3 − c2, e0 = c0 + wu·a0, e1 = c2 + wu·a1, raw = e0 + wv·(e1 − e0)     (the ripple sample's patch)
+ *     d = fminf(fmaxf(raw, 0), max_depth);   d < dry_depth -> d = +0;   the cell's wall byte is 1 (walls on) -> d = +0
+ *     q = 0 where d == 0 or surf_depth == 0 or d >= surf_depth, else min(16, (int)floorf((1 − d·invsurf)·16))
+ *
+ * THE SUB-STEP OVER A BED.  The WAVE mode with a bed.  h, fsponge[k], the sponge index, the window test, the first sub-step's
+ * e = η + (float)src · 2^-20, the torus and the memset behind the first launch are datum_ocean_step_ripples', unchanged.  dc is the
+ * cell's depth; for each of the four neighbours, depth dn and height en:
+ *     outside the WINDOW (the depth and the flag of the torus-aliased cell are not consulted):   t = dc·(0 − e)
+ *     the neighbour is solid (dn == 0):                                                         t = 0
+ *     else                                                                                      t = (0.5f·(dc + dn))·(en − e)
+ *     div = (tL + tR) + (tD + tU);   f = fsponge[k]·fsurf[q];   v1 = (η_t + h·(gs2·div))·f;   η' = e + h·v1;   η_t' = v1
+ * gs2 = (float)(g / s²) with g the layer's g (datum_ocean_set_ripple_dispersion's, 9.81 by default);
+ * fsurf[q] = (float)(1 / (1 + h·surf_gamma·(q/16)²)), built on the host in double beside fsponge: breaking as a damping that grows
+ * towards the shore.  With surf_depth == 0 the factor is exactly 1.0f.  A solid cell's new state is (+0.0f, +0.0f); a deposit that lands
+ * on it is lost, uncounted, as on a wall.  WHILE THE BED IS ON, datum_ocean_set_ripple_params' c IS NOT USED BY THE STEP: the speed is
+ * sqrt(g·d) of the place.
+ *
+ * STABILITY.  The face coefficient is the mean of its two cells, so the operator is symmetric on the wet cells and its row sums are at most
+ * 4·max_depth: the wave step's Gershgorin argument holds with c := sqrt(g·max_depth).  While the bed is on, datum_ocean_step_ripples and
+ * datum_ocean_step_bodies_coupled refuse sqrt(g·max_depth)·dt / (substeps·s) above 0.7 where they refused c·dt / (substeps·s).
+ *
+ * DEEP.  The bed and the DEEP mode DO NOT COMBINE (a variable depth is not a convolution): datum_ocean_set_ripple_bed while the mode is
+ * DATUM_OCEAN_RIPPLE_DEEP, and datum_ocean_set_ripple_dispersion(DATUM_OCEAN_RIPPLE_DEEP, ...) while a bed is set, return
+ * DATUM_OCEAN_ESTATE.  Uniform finite depth for DEEP stays left out.
+ *
+ *   set_ripple_bed         a null `bed` turns the bed off and frees everything.  Otherwise the map is copied (blocking, as the wall list
+ *                          is: the caller's array may go away behind the call), then ONE launch on the handle's stream rasters both
+ *                          planes and makes the state of every solid cell (+0, +0) in BOTH state buffers; the ripple bounds' CURRENT mark
+ *                          is cleared; src, the wake-foam plane and everything else are left alone.  DATUM_OCEAN_EINVAL: a null handle,
+ *                          null depths_host, width or height outside [2, 4096], texel not finite or not > 0, origin or outside not
+ *                          finite, max_depth not finite or not > 0, dry_depth not in (0, max_depth], surf_depth or surf_gamma not finite
+ *                          or negative, a map value that is not finite (checked on the host).  DATUM_OCEAN_ESTATE while the layer is off
+ *                          or its mode is DEEP.  datum_ocean_set_ripples with any R drops the bed, as it drops the walls;
+ *                          datum_ocean_reset_ripples keeps it.  datum_ocean_center_ripples rebuilds both planes whole, in one launch
+ *                          behind the wall raster; datum_ocean_set_ripple_walls rasters the bed again, since the wall byte enters d.
+ *   ripple_bed_device      *depth and *surf = the device planes in memory order (R·R floats, R·R bytes), *cells = R·R; null and 0 while
+ *                          the bed is off.  Any of the three may be null.  Stable until the next set_ripple_bed or set_ripples.
+ *   read_ripple_bed        both planes to the HOST in window order, [j][i] for cell (ox + i, oy + j), as datum_ocean_read_ripple_walls;
+ *                          either may be null; blocking.  DATUM_OCEAN_ESTATE while the bed is off.
+ * LEFT OUT: the bed in DEEP, as tanh(k·d) weights; wetting and drying, run-up and non-linear steepening (the shoreline is fixed at
+ * dry_depth); foam from the surf zone; bounds and wake foam treating solid cells as anything but water at rest; the FFT swell feeling the
+ * bed; writing only the entered cells on a scroll; temporal blocking. */
+#define DATUM_OCEAN_RIPPLE_SURF_LEVELS 16
+#define DATUM_OCEAN_RIPPLE_BED_MAX_SIDE 4096
+typedef struct datum_ocean_ripple_bed
+{
+  int width, height;    /* texels of the map, each in [2, DATUM_OCEAN_RIPPLE_BED_MAX_SIDE] */
+  float origin[2];      /* world metres of texel (0, 0) */
+  float texel;          /* the side of a texel in metres, > 0 */
+  float outside;        /* the depth a cell off the map reads */
+  float max_depth;      /* > 0: depths are clamped to it, and it sets the stability bound */
+  float dry_depth;      /* in (0, max_depth]: a cell shallower than this is solid */
+  float surf_depth;     /* >= 0: the surf zone is where d < surf_depth; 0 for none */
+  float surf_gamma;     /* >= 0: the damping rate 1/s at the shoreline end of the surf zone */
+} datum_ocean_ripple_bed;
+int datum_ocean_set_ripple_bed(datum_ocean_t ctx, datum_ocean_ripple_bed const *bed, float const *depths_host);
+int datum_ocean_ripple_bed_device(datum_ocean_t ctx, void **depth, void **surf, size_t *cells);
+int datum_ocean_read_ripple_bed(datum_ocean_t ctx, float *depth, unsigned char *surf);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -113,6 +113,8 @@ SYMBOLS = {
     "datum_ocean_farm_stream_flags": (I, [P, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]),
     "datum_ocean_set_phase_writeback": (I, [P, I]),
     "datum_ocean_phase_writeback": (I, [P, ctypes.POINTER(I)]),
+    "datum_ocean_set_phase_store": (I, [P, I]),
+    "datum_ocean_phase_store": (I, [P, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_uint)]),
     "datum_ocean_set_cascade_group": (I, [P, I]),
     "datum_ocean_cascade_group": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I)]),
     "datum_ocean_set_foam": (I, [P, I]),
@@ -204,6 +206,7 @@ SPECTRUM_FORMATS = {"fp32": 0, "fp16": 1, "fp16h0": 2}
 
 # datum_ocean_set_map_store_policy's values
 MAP_STORE_POLICIES = {"auto": 0, "written through": 1, "streamed": 2}
+PHASE_STORES = {"auto": 0, "plane": 1}
 
 # datum_ocean_set_velocity's modes, and the floats of a velocity query's record
 VELOCITY_MODES = {"off": 0, "on": 1}
@@ -662,6 +665,17 @@ class Ocean:
         e = I(0)
         self._check(self.lib.datum_ocean_phase_writeback(self.h, ctypes.byref(e)))
         return e.value
+
+    def set_phase_store(self, mode):
+        """where the phase is kept: "auto" (default: a symmetric cascade's as a quadrant table) or "plane"; results do not depend on it
+        (datum_ocean_set_phase_store)"""
+        self._check(self.lib.datum_ocean_set_phase_store(self.h, PHASE_STORES[mode] if isinstance(mode, str) else int(mode)))
+
+    def phase_store(self):
+        """(the mode set, the cascades whose phase is a quadrant table at this moment, one bit each)"""
+        m, q = I(), ctypes.c_uint()
+        self._check(self.lib.datum_ocean_phase_store(self.h, ctypes.byref(m), ctypes.byref(q)))
+        return {v: k for k, v in PHASE_STORES.items()}[m.value], q.value
 
     def set_map_store_policy(self, policy):
         """how the column pass stores the maps: "auto" (default), "written through", "streamed" (datum_ocean_set_map_store_policy)"""

@@ -15,6 +15,7 @@
 #include <hip/hip_ext.h>
 
 #include "ocean_layout.h"
+#include "ocean_quadrant.h"
 #include "ocean_writeback.h"
 #include "ocean_kernels.hip"
 #include "ocean_gen.hip"
@@ -55,9 +56,11 @@ struct PassKernel
 // every kernel a step can launch at the handle's resolution (step_kernels), filled and configured once by datum_ocean_create
 struct StepKernels
 {
-  PassKernel row[3][2];               // [DATUM_OCEAN_SPECTRUM_*][a phase outside [0, 2 pi)]
+  PassKernel row[3][3];               // [DATUM_OCEAN_SPECTRUM_*][ROW_PLANE, ROW_WILD (a phase outside [0, 2 pi)), ROW_QUADRANT (the phase from the quadrant tables)]
   PassKernel col[2][2];               // [fp16 work spectrum][maps streamed]; the written-through kernel twice where there is no streamed form
 };
+
+enum { ROW_PLANE = 0, ROW_WILD = 1, ROW_QUADRANT = 2 };
 
 // a device plane the caller can replace with memory of its own (datum_ocean_bind_maps, datum_ocean_bind_foam)
 template<typename T>
@@ -85,6 +88,7 @@ struct CascadeState
 {
   bool uploaded = false;              // holds a state (upload_state, resume_state, rebuild_height)
   bool wild = false;                  // its phase lies outside [0, 2 pi)
+  bool quadrant = false;              // its phase is its quadrant table, not the plane (ocean_quadrant.h: where the truth lives)
   bool scaledirty = false;            // fp16 only: h0 changed since specscale was sized
   bool omegadirty = true;             // the wave scale changed since its dispersion table was built
   float omegamax = 0.0f;              // largest dispersion (table corner)
@@ -111,6 +115,8 @@ struct datum_ocean_ctx
   float2 *h0 = nullptr;
   float2 *seed = nullptr;             // [cascade][N*N] OceanParams::seed, only when the caller uploads it
   float *phase = nullptr;
+  float *qphase = nullptr;            // [cascade][(N/2+1)^2] the phase of the cascades whose CascadeState::quadrant is set
+  int phasestore = DATUM_OCEAN_PHASE_STORE_AUTO;   // datum_ocean_set_phase_store
   void *spec = nullptr;               // cd[cascades][P], or ch[...] with the fp16 spectrum
   bool half = false;                  // DATUM_OCEAN_SPECTRUM_FP16 or _FP16_H0
   bool h0half = false;                // DATUM_OCEAN_SPECTRUM_FP16_H0: the row pass reads h0 as halves ...
@@ -258,6 +264,7 @@ namespace
     a.h0 = ctx->h0;
     a.h0h = ctx->h0half ? ctx->h0h : nullptr;
     a.phase = ctx->phase;
+    a.qphase = ctx->qphase;
     a.spec = ctx->spec;
     a.maps = ctx->maps.get();
     a.tw = ctx->tw;
@@ -306,7 +313,20 @@ namespace
     int groups = 0;                   // launches per pass
     bool streamed = false;            // the maps streamed past the Infinity Cache
     int writeback = 1;                // the row pass stores the phase once its dt list holds this many (ocean_writeback.h)
+    bool quadrant = false;            // the row pass reads and stores the phase in the quadrant tables (ocean_quadrant.h)
   };
+
+  // whether every cascade's phase is its quadrant table: the one condition under which the row pass takes the tables
+  bool every_quadrant(datum_ocean_ctx const *ctx)
+  {
+    for(int c = 0; c < ctx->cascades; ++c)
+    {
+      if (!ctx->cstate[c].quadrant)
+        return false;
+    }
+
+    return true;
+  }
 
   // The phase written back once per this many steps' worth of dt's unless the caller sets an interval (datum_ocean_set_phase_writeback).
   // Measured, parent build and intervals 1 / 2 / 4 / 8 alternated on one device (profiles/phase_writeback_ab.txt, phase_writeback_kernel_trace.txt):
@@ -363,7 +383,10 @@ namespace
 
     int const format = ctx->h0half ? DATUM_OCEAN_SPECTRUM_FP16_H0 : (ctx->half ? DATUM_OCEAN_SPECTRUM_FP16 : DATUM_OCEAN_SPECTRUM_FP32);
 
-    p.row = &ctx->kernels.row[format][wild];
+    // the phase from the quadrant tables where EVERY cascade's phase is its table (displace settles that first: settle_phase_store)
+    p.quadrant = every_quadrant(ctx);
+
+    p.row = &ctx->kernels.row[format][p.quadrant ? ROW_QUADRANT : (wild ? ROW_WILD : ROW_PLANE)];
     p.col = &ctx->kernels.col[ctx->half][p.streamed];
 
     p.writeback = ctx->writebackevery > 0 ? ctx->writebackevery : PHASE_WRITEBACK_EVERY;
@@ -383,12 +406,15 @@ namespace
 
     StepKernels t;
 
-    t.row[DATUM_OCEAN_SPECTRUM_FP32][0] = { k(&ocean_rowpass_kernel<N, false>), R::THREADS, R::LDS, R::GROUPS };
-    t.row[DATUM_OCEAN_SPECTRUM_FP32][1] = { k(&ocean_rowpass_kernel<N, false, true>), R::THREADS, R::LDS, R::GROUPS };
-    t.row[DATUM_OCEAN_SPECTRUM_FP16][0] = { k(&ocean_rowpass_kernel<N, true>), RH::THREADS, RH::LDS, RH::GROUPS };
-    t.row[DATUM_OCEAN_SPECTRUM_FP16][1] = { k(&ocean_rowpass_kernel<N, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
-    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][0] = { k(&ocean_rowpass_kernel<N, true, false, true>), RH::THREADS, RH::LDS, RH::GROUPS };
-    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][1] = { k(&ocean_rowpass_kernel<N, true, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP32][ROW_PLANE] = { k(&ocean_rowpass_kernel<N, false>), R::THREADS, R::LDS, R::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP32][ROW_WILD] = { k(&ocean_rowpass_kernel<N, false, true>), R::THREADS, R::LDS, R::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP32][ROW_QUADRANT] = { k(&ocean_rowpass_kernel<N, false, false, false, true>), R::THREADS, R::LDS, R::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16][ROW_PLANE] = { k(&ocean_rowpass_kernel<N, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16][ROW_WILD] = { k(&ocean_rowpass_kernel<N, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16][ROW_QUADRANT] = { k(&ocean_rowpass_kernel<N, true, false, false, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][ROW_PLANE] = { k(&ocean_rowpass_kernel<N, true, false, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][ROW_WILD] = { k(&ocean_rowpass_kernel<N, true, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
+    t.row[DATUM_OCEAN_SPECTRUM_FP16_H0][ROW_QUADRANT] = { k(&ocean_rowpass_kernel<N, true, false, true, true>), RH::THREADS, RH::LDS, RH::GROUPS };
 
     t.col[0][0] = t.col[0][1] = { colpass_entry<N, false>(), C::THREADS, C::LDS, C::TILES, col_walks<N, false>() };
     t.col[1][0] = t.col[1][1] = { colpass_entry<N, true>(), C::THREADS, C::LDS, C::TILES, col_walks<N, true>() };
@@ -480,6 +506,121 @@ namespace
     return true;
   }
 
+  //|---------------------- where a cascade's phase lives (ocean_quadrant.h) ---
+  // The stored phase of a cascade is its quadrant table while CascadeState::quadrant is set, the plane otherwise; both are behind the
+  // handle's true phase by the same retained dt's (ocean_writeback.h), whose flush acts on whichever it is.
+
+  // the cascades whose phase is their table, bit by bit (ocean_advance_kernel)
+  unsigned int quadrant_mask(datum_ocean_ctx const *ctx)
+  {
+    unsigned int mask = 0;
+
+    for(int c = 0; c < ctx->cascades; ++c)
+      mask |= (unsigned int)ctx->cstate[c].quadrant << c;
+
+    return mask;
+  }
+
+  // The plane of a cascade made current for a call that reads or copies it: table -> plane; the table stays the truth.  The caller has
+  // flushed whatever its reader must see (flush_retained, flush_phase).
+  int materialise(datum_ocean_ctx *ctx, int cascade)
+  {
+    if (!ctx->cstate[cascade].quadrant)
+      return DATUM_OCEAN_OK;
+
+    hipLaunchKernelGGL(ocean_phaseexpand_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->qphase + cascade * quadrant_count(ctx->N), ctx->phase + cascade * plane(ctx), ctx->N);
+    HIPCHECK(ctx, hipGetLastError());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // ... and a cascade moved back to the plane for good: from here on the plane is the truth
+  int leave_quadrant(datum_ocean_ctx *ctx, int cascade)
+  {
+    int rc = materialise(ctx, cascade);
+
+    ctx->cstate[cascade].quadrant = false;
+
+    return rc;
+  }
+
+  // A zero phase, what every state without an uploaded one starts from: both homes filled, and the table the truth unless the handle is
+  // held to the plane
+  int zero_phase(datum_ocean_ctx *ctx, int cascade)
+  {
+    HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * plane(ctx), 0, plane(ctx) * sizeof(float), ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(ctx->qphase + cascade * quadrant_count(ctx->N), 0, quadrant_count(ctx->N) * sizeof(float), ctx->stream));
+
+    ctx->cstate[cascade].quadrant = ctx->phasestore == DATUM_OCEAN_PHASE_STORE_AUTO;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // A phase that has just been written into a cascade's plane (an upload, an adopted parked state, a switch back to the automatic mode):
+  // whether it leaves [0, 2 pi) -- `knownwild` < 0: looked for on the device -- and whether it is symmetric, one word and one read-back for
+  // both; a symmetric one in range moves into the table.  Synchronises the stream.
+  int inspect_phase(datum_ocean_ctx *ctx, int cascade, int knownwild, bool *wild)
+  {
+    size_t const P = plane(ctx);
+    float const *phase = ctx->phase + cascade * P;
+    bool const symmetry = ctx->phasestore == DATUM_OCEAN_PHASE_STORE_AUTO && knownwild <= 0;
+
+    unsigned int flags = 0;
+
+    ctx->cstate[cascade].quadrant = false;
+
+    if (knownwild < 0 || symmetry)
+    {
+      HIPCHECK(ctx, hipMemsetAsync(ctx->absmax, 0, sizeof(unsigned int), ctx->stream));
+
+      // phases outside [0, 2 pi) take the general fmod kernel: looked for on the device, where the array now is
+      if (knownwild < 0)
+        hipLaunchKernelGGL(ocean_phaserange_kernel, dim3(1024), dim3(256), 0, ctx->stream, phase, P, ctx->absmax);
+
+      if (symmetry)
+        hipLaunchKernelGGL(ocean_phasesymmetry_kernel, dim3(1024), dim3(256), 0, ctx->stream, phase, ctx->N, ctx->absmax);
+
+      HIPCHECK(ctx, hipGetLastError());
+      HIPCHECK(ctx, hipMemcpyAsync(&flags, ctx->absmax, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+
+    *wild = (knownwild < 0) ? (flags & 1u) != 0 : knownwild > 0;
+
+    if (symmetry && !*wild && !(flags & 2u))
+    {
+      hipLaunchKernelGGL(ocean_phasecompact_kernel, dim3(512), dim3(256), 0, ctx->stream, phase, ctx->qphase + cascade * quadrant_count(ctx->N), ctx->N);
+      HIPCHECK(ctx, hipGetLastError());
+
+      ctx->cstate[cascade].quadrant = true;
+    }
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // Before a row pass (displace, debug_rowpass): its kernel takes every cascade's phase from one kind of home.  The tables, where every
+  // cascade's phase is its table, none is wild and nothing else reads the stored plane in every step (the literal dispatches, the velocity
+  // passes); otherwise the symmetric cascades are expanded and the plane kernel runs, as in builds before the table.
+  int settle_phase_store(datum_ocean_ctx *ctx)
+  {
+    bool tables = every_quadrant(ctx) && !ctx->literal && ctx->velocitymode == DATUM_OCEAN_VELOCITY_OFF;
+
+    for(int c = 0; c < ctx->cascades; ++c)
+      tables = tables && !ctx->cstate[c].wild;
+
+    if (tables)
+      return DATUM_OCEAN_OK;
+
+    for(int c = 0; c < ctx->cascades; ++c)
+    {
+      int rc = leave_quadrant(ctx, c);
+      if (rc != DATUM_OCEAN_OK)
+        return rc;
+    }
+
+    return DATUM_OCEAN_OK;
+  }
+
   // Store the phase the handle stands at: the dt's the last row pass applied without storing, through the phase-only kernel (the same
   // roundings).  Before anything reads the stored phase, replaces it, or changes what the retained dt's mean (a cascade's dispersion table).
   int flush_retained(datum_ocean_ctx *ctx)
@@ -495,7 +636,7 @@ namespace
 
     StepArgs a = make_args(ctx, l.ndt, l.dt);
 
-    hipLaunchKernelGGL(ocean_advance_kernel, dim3(1024, ctx->cascades), dim3(256), 0, ctx->stream, a, ctx->N);
+    hipLaunchKernelGGL(ocean_advance_kernel, dim3(1024, ctx->cascades), dim3(256), 0, ctx->stream, a, ctx->N, quadrant_mask(ctx));
     HIPCHECK(ctx, hipGetLastError());
 
     ctx->writeback.clear();
@@ -533,7 +674,7 @@ namespace
       }
 
       dim3 grid(1024, ctx->cascades);
-      hipLaunchKernelGGL(ocean_advance_kernel, grid, dim3(256), 0, ctx->stream, a, ctx->N);
+      hipLaunchKernelGGL(ocean_advance_kernel, grid, dim3(256), 0, ctx->stream, a, ctx->N, quadrant_mask(ctx));
       HIPCHECK(ctx, hipGetLastError());
 
       ctx->pending.erase(ctx->pending.begin(), ctx->pending.begin() + n);
@@ -932,6 +1073,7 @@ int datum_ocean_create(datum_ocean_t *out, int device, int resolution, int casca
 
   CREATECHECK(hipMalloc(&ctx->h0, cascades * P * sizeof(float2)));
   CREATECHECK(hipMalloc(&ctx->phase, cascades * P * sizeof(float)));
+  CREATECHECK(hipMalloc(&ctx->qphase, cascades * quadrant_count(resolution) * sizeof(float)));
   CREATECHECK(hipMalloc(&ctx->spec, cascades * P * sizeof(cd)));
   CREATECHECK(hipMalloc(&ctx->absmax, sizeof(unsigned int)));
   CREATECHECK(hipMalloc(&ctx->maps.own, cascades * map_cascade_bytes(resolution)));
@@ -940,6 +1082,11 @@ int datum_ocean_create(datum_ocean_t *out, int device, int resolution, int casca
 
   CREATECHECK(hipMemsetAsync(ctx->h0, 0, cascades * P * sizeof(float2), ctx->stream));
   CREATECHECK(hipMemsetAsync(ctx->phase, 0, cascades * P * sizeof(float), ctx->stream));
+  CREATECHECK(hipMemsetAsync(ctx->qphase, 0, cascades * quadrant_count(resolution) * sizeof(float), ctx->stream));
+
+  // (a zero phase is symmetric: every cascade starts in its table)
+  for(int c = 0; c < cascades; ++c)
+    ctx->cstate[c].quadrant = true;
   CREATECHECK(hipMemsetAsync(ctx->maps.own, 0, cascades * map_cascade_bytes(resolution), ctx->stream));
 
   // exp(+2 pi i k / N), rounded once from double (the reference's table -- ocean.cpp:686-700 -- is per
@@ -1019,6 +1166,7 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->h0);
   (void)hipFree(ctx->seed);
   (void)hipFree(ctx->phase);
+  (void)hipFree(ctx->qphase);
   (void)hipFree(ctx->spec);
   (void)hipFree(ctx->absmax);
   (void)hipFree(ctx->h0h);
@@ -1198,28 +1346,25 @@ int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, fl
 
   HIPCHECK(ctx, hipMemcpyAsync(ctx->h0 + cascade * P, h0, P * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
 
-  unsigned int wild = 0;
+  bool wild = false;
 
   if (phase)
   {
     HIPCHECK(ctx, hipMemcpyAsync(ctx->phase + cascade * P, phase, P * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
 
-    // phases outside [0, 2 pi) take the general fmod kernel: looked for on the device, where the array now is
-    HIPCHECK(ctx, hipMemsetAsync(ctx->absmax, 0, sizeof(unsigned int), ctx->stream));
-    hipLaunchKernelGGL(ocean_phaserange_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->phase + cascade * P, P, ctx->absmax);
-    HIPCHECK(ctx, hipGetLastError());
-    HIPCHECK(ctx, hipMemcpyAsync(&wild, ctx->absmax, sizeof(wild), hipMemcpyDeviceToHost, ctx->stream));
+    rc = inspect_phase(ctx, cascade, -1, &wild);
   }
   else
-    HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * P, 0, P * sizeof(float), ctx->stream));
+    rc = zero_phase(ctx, cascade);
 
-  rc = new_state_foam(ctx, cascade);
+  if (rc == DATUM_OCEAN_OK)
+    rc = new_state_foam(ctx, cascade);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));   // the host buffers are the caller's again
 
-  ctx->cstate[cascade].new_state(wild != 0);
+  ctx->cstate[cascade].new_state(wild);
 
   return DATUM_OCEAN_OK;
 }
@@ -1313,7 +1458,10 @@ int datum_ocean_rebuild_height(datum_ocean_t ctx, int cascade, float wavescale, 
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    HIPCHECK(ctx, hipMemsetAsync(ctx->phase + cascade * P, 0, P * sizeof(float), ctx->stream));
+    rc = zero_phase(ctx, cascade);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
     ctx->cstate[cascade].new_state(false);
   }
 
@@ -1349,6 +1497,8 @@ int datum_ocean_read_state(datum_ocean_t ctx, int cascade, float *phase)
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   int rc = flush_phase(ctx);
+  if (rc == DATUM_OCEAN_OK)
+    rc = materialise(ctx, cascade);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -1382,6 +1532,8 @@ int datum_ocean_park_state(datum_ocean_t ctx, int cascade, void *device_dst, siz
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   int rc = flush_phase(ctx);
+  if (rc == DATUM_OCEAN_OK)
+    rc = materialise(ctx, cascade);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -1418,11 +1570,17 @@ int datum_ocean_resume_state(datum_ocean_t ctx, int cascade, void const *device_
   HIPCHECK(ctx, hipMemcpyAsync(ctx->h0 + cascade * P, device_src, P * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(ctx->phase + cascade * P, static_cast<char const*>(device_src) + P * sizeof(float2), P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
 
-  rc = new_state_foam(ctx, cascade);
+  // (the range is the flag's word; whether the adopted phase is symmetric is looked for on the device: one read-back)
+  bool wild = false;
+
+  rc = inspect_phase(ctx, cascade, (flags & 1) ? 1 : 0, &wild);
+
+  if (rc == DATUM_OCEAN_OK)
+    rc = new_state_foam(ctx, cascade);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  ctx->cstate[cascade].new_state((flags & 1) != 0);
+  ctx->cstate[cascade].new_state(wild);
 
   return DATUM_OCEAN_OK;
 }
@@ -1477,6 +1635,8 @@ int datum_ocean_displace(datum_ocean_t ctx)
     return rc;
 
   rc = size_spectrum_scale(ctx);
+  if (rc == DATUM_OCEAN_OK)
+    rc = settle_phase_store(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
@@ -4444,6 +4604,56 @@ int datum_ocean_phase_writeback(datum_ocean_t ctx, int *every)
   return DATUM_OCEAN_OK;
 }
 
+int datum_ocean_set_phase_store(datum_ocean_t ctx, int mode)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_phase_store: null handle");
+
+  if (mode != DATUM_OCEAN_PHASE_STORE_AUTO && mode != DATUM_OCEAN_PHASE_STORE_PLANE)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_phase_store: unknown mode");
+
+  if (ctx->profiling)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_phase_store: a profile is open (its row-pass samples are with the phase store it began with)");
+
+  if (mode == ctx->phasestore)
+    return DATUM_OCEAN_OK;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  ctx->phasestore = mode;
+
+  // (table and plane are behind the handle's phase by the same retained dt's: neither move needs them flushed)
+  for(int c = 0; c < ctx->cascades; ++c)
+  {
+    int rc = DATUM_OCEAN_OK;
+
+    if (mode == DATUM_OCEAN_PHASE_STORE_PLANE)
+      rc = leave_quadrant(ctx, c);
+    else if (!ctx->cstate[c].wild)
+    {
+      bool wild = false;
+
+      rc = inspect_phase(ctx, c, 0, &wild);
+    }
+
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+  }
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_phase_store(datum_ocean_t ctx, int *mode, unsigned int *quadrants)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_phase_store: null handle");
+
+  if (mode) *mode = ctx->phasestore;
+  if (quadrants) *quadrants = quadrant_mask(ctx);
+
+  return DATUM_OCEAN_OK;
+}
+
 int datum_ocean_abi_version(void)
 {
   return DATUM_OCEAN_ABI_VERSION;
@@ -4798,6 +5008,8 @@ int datum_ocean_debug_sim(datum_ocean_t ctx, int cascade, float *h, float *hx, f
 
   int rc = flush_phase(ctx);
   if (rc == DATUM_OCEAN_OK)
+    rc = materialise(ctx, cascade);
+  if (rc == DATUM_OCEAN_OK)
     rc = ensure_scratch(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
@@ -4845,6 +5057,8 @@ int datum_ocean_debug_rowpass(datum_ocean_t ctx, int cascade, float *c, float *d
   // have left another cascade's values in the slot: the row pass of this one cascade once more -- with the dt's the last displace applied and
   // did not store, if any, and no queued one, so the phase is not stored and the values are those of the last displace -- into slot 0
   rc = size_spectrum_scale(ctx);
+  if (rc == DATUM_OCEAN_OK)
+    rc = settle_phase_store(ctx);
   if (rc != DATUM_OCEAN_OK)
     return rc;
 

@@ -31,6 +31,7 @@
 #include "ocean_fft_core.h"
 #include "ocean_layout.h"
 #include "ocean_phase.h"
+#include "ocean_quadrant.h"
 #include "ocean_writeback.h"
 #include "../../include/datum_ocean_hip.h"
 
@@ -61,7 +62,7 @@ namespace ocean
     float2 const *h0;    // [cascade][N*N]       OceanSet::h0
     unsigned int const *h0h;   // [cascade][N*N]   the same as two IEEE halves times a power of two per cascade (DATUM_OCEAN_SPECTRUM_FP16_H0 only, else null)
     float *phase;        // [cascade][N*N]       OceanSet::phase
-    void *spec;          // [cascade - first][N*N] work spectrum of THIS launch (replaces Spectrum::h, hx, hy), blocked layout: cd, or ch (fp16 variant)
+    void *spec;         // [cascade - first][N*N] work spectrum of THIS launch (replaces Spectrum::h, hx, hy), blocked layout: cd, or ch (fp16 variant)
     float4 *maps;        // [cascade][2*N*N]     displacementmap, 2 layers, 24-byte texels in patches (map_compact_a / map_compact_b)
     cf const *tw;        // [N]                  exp(+2 pi i k / N)
     float const *omega;  // [cascade][(N/2+1)^2] dispersion(k) by (|m - N/2|, |n - N/2|)
@@ -71,6 +72,7 @@ namespace ocean
     int first;           // ... starting with this one (the two passes are launched per group of cascades: ocean_capi, plan_step)
     float dt[MAX_PENDING];
     CascadeConst casc[DATUM_OCEAN_MAX_CASCADES];
+    float *qphase;       // [cascade][(N/2+1)^2] the phase by (|m - N/2|, |n - N/2|), where a cascade's phase is symmetric (ocean_quadrant.h)
 #ifdef OCEAN_STAMPS
     unsigned long long *stamps;   // diagnostic builds only (tools/dbg/stamps.hip): [kernel][workgroup][16] timestamps
 #endif
@@ -221,6 +223,35 @@ namespace ocean
 
     if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0)
       atomicOr(wild, 1u);
+  }
+
+  // is an uploaded or adopted phase plane a function of the quadrant index (ocean_quadrant.h)?  Every element against its representative,
+  // bit for bit; bit 1 of the word ocean_phaserange_kernel sets bit 0 of, so that one read-back fetches both
+  __global__ void ocean_phasesymmetry_kernel(float const *phase, int N, unsigned int *flags)
+  {
+    bool bad = false;
+
+    for(size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < (size_t)N * N; k += (size_t)gridDim.x * blockDim.x)
+      bad |= !quadrant_element_symmetric(phase, N, k);
+
+    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0)
+      atomicOr(flags, 2u);
+  }
+
+  // plane -> table, of a plane that passed the test: every table element from its representative
+  __global__ void ocean_phasecompact_kernel(float const *phase, float *q, int N)
+  {
+    int const Q = quadrant_side(N);
+
+    for(size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < quadrant_count(N); k += (size_t)gridDim.x * blockDim.x)
+      q[k] = phase[quadrant_representative(N, (int)(k / Q), (int)(k % Q))];
+  }
+
+  // table -> plane: phase[y][x] = q[|y - N/2|][|x - N/2|]
+  __global__ void ocean_phaseexpand_kernel(float const *q, float *phase, int N)
+  {
+    for(size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < (size_t)N * N; k += (size_t)gridDim.x * blockDim.x)
+      phase[k] = q[quadrant_index(N, (int)(k / N), (int)(k % N))];
   }
 
   __device__ __forceinline__ float dispersion_lookup(float const *table, int n, int m, int N)
@@ -585,10 +616,15 @@ namespace ocean
   // fewer in flight at 16 points per thread -- from the copy size_spectrum_scale keeps (h0 times a power of two per cascade that brings
   // max |h0| just under 2^15).  Everything up to the store is linear in h0, so that power of two is taken out again together with the
   // work spectrum's own scale: one factor, CascadeConst::rowscale, exact.
-  template<int N, bool H16, bool WILD = false, bool H0H = false>
+  // QPH (never with WILD; the host picks it when every cascade of the handle is symmetric, ocean_quadrant.h): the phase is loaded from the
+  // cascade's quadrant table at the very offsets the dispersion is loaded from -- 4 bytes per point of a 4 N^2-byte plane become L2 hits on
+  // an (N/2 + 1)^2 table, and the plane's address register goes -- and the guarded store goes there too, one writer per element.  The
+  // arithmetic is the plane form's, instruction for instruction.
+  template<int N, bool H16, bool WILD = false, bool H0H = false, bool QPH = false>
   __global__ void OCEAN_LDS_UNPAIRED __launch_bounds__((RowCfg<N, H16>::THREADS), (RowCfg<N, H16>::MIN_WAVES)) ocean_rowpass_kernel(StepArgs a)
   {
     static_assert(H16 || !H0H, "h0 as halves goes with the fp16-stored work spectrum");
+    static_assert(!(QPH && WILD), "a symmetric cascade that becomes wild is expanded and takes the plane form");
 
     typedef RowCfg<N, H16> C;
     typedef Plan<N, C::E> P;
@@ -668,19 +704,29 @@ namespace ocean
       int const cascade = a.first + item / G;
       int const y = row_of(item);
 
-      constexpr size_t QUAD = (size_t)(N / 2 + 1) * (N / 2 + 1);
+      constexpr size_t QUAD = quadrant_count(N);
 
       __amdgpu_buffer_rsrc_t romega = make_rsrc(a.omega + cascade * QUAD, QUAD * sizeof(float));
-      __amdgpu_buffer_rsrc_t rphase = make_rsrc(a.phase + cascade * plane, plane * sizeof(float));
+      __amdgpu_buffer_rsrc_t rphase = QPH ? make_rsrc(a.qphase + cascade * QUAD, QUAD * sizeof(float)) : make_rsrc(a.phase + cascade * plane, plane * sizeof(float));
       __amdgpu_buffer_rsrc_t rh0 = H0H ? make_rsrc(a.h0h + cascade * plane, plane * sizeof(unsigned int)) : make_rsrc(a.h0 + cascade * plane, plane * sizeof(float2));
 
       int const e0 = y * N + t;
       int const m0 = (N - 1 - y) * N + (N - 1 - t - T * (E - 1));
 
+      // dispersion_lookup (ocean_omega_kernel's quadrant table) through the buffer path.  |x - N/2| of slot s is N/2 - t - T s in the
+      // lower half of the slots and t + T (s - E/2) in the upper: two per-thread offsets and compile-time steps, not one address
+      // register per slot (ocean_quadrant.h; the quadrant phase lies at the same offsets of its own table)
+      // (formed where they are used: ahead of the plane form's loads they cost its 512^2 instantiation six registers and a wave per SIMD)
+      auto lower_of = [&] { return quadrant_lower(N, T, E, abs(y - N / 2), t) * 4; };       // slot E/2 - 1, the lowest address of the lower half
+      auto upper_of = [&] { return quadrant_upper(N, abs(y - N / 2), t) * 4; };             // slot E/2
+
       #pragma unroll
       for(int s = 0; s < E; ++s)
       {
-        in.ph[s] = buf_load_f32(rphase, e0 * 4, T * s * 4);
+        if constexpr (QPH)
+          in.ph[s] = buf_load_f32(rphase, (s < E / 2) ? lower_of() : upper_of(), quadrant_step(T, E, s) * 4);
+        else
+          in.ph[s] = buf_load_f32(rphase, e0 * 4, T * s * 4);
 
         if constexpr (H0H)
         {
@@ -696,16 +742,11 @@ namespace ocean
 
       if (advance)
       {
-        // dispersion_lookup (ocean_omega_kernel's quadrant table) through the buffer path.  |x - N/2| of slot s is N/2 - t - T s in the
-        // lower half of the slots and t + T (s - E/2) in the upper: two per-thread offsets and compile-time steps, not one address
-        // register per slot
-        int const i = abs(y - N / 2);
-        int const lower = (i * (N / 2 + 1) + N / 2 - t - T * (E / 2 - 1)) * 4;       // slot E/2 - 1, the lowest address of the lower half
-        int const upper = (i * (N / 2 + 1) + t) * 4;                                 // slot E/2
+        int const lower = lower_of(), upper = upper_of();
 
         #pragma unroll
         for(int s = 0; s < E; ++s)
-          in.om[s] = (s < E / 2) ? buf_load_f32(romega, lower, T * (E / 2 - 1 - s) * 4) : buf_load_f32(romega, upper, T * (s - E / 2) * 4);
+          in.om[s] = buf_load_f32(romega, (s < E / 2) ? lower : upper, quadrant_step(T, E, s) * 4);
       }
     };
 
@@ -740,7 +781,9 @@ namespace ocean
 
       CascadeConst const cc = a.casc[cascade];
 
-      __amdgpu_buffer_rsrc_t rphase = make_rsrc(a.phase + cascade * plane, plane * sizeof(float));
+      constexpr size_t QUAD = quadrant_count(N);
+
+      __amdgpu_buffer_rsrc_t rphase = QPH ? make_rsrc(a.qphase + cascade * QUAD, QUAD * sizeof(float)) : make_rsrc(a.phase + cascade * plane, plane * sizeof(float));
       // (the work spectrum is per LAUNCH: slot cascade - first.  Every cascade group writes and reads the same slots, which therefore stay in the
       // Infinity Cache from one group to the next instead of going out to HBM and back once per cascade)
       __amdgpu_buffer_rsrc_t rspec = make_rsrc(static_cast<SV*>(a.spec) + (cascade - a.first) * plane, plane * sizeof(SV));
@@ -778,7 +821,8 @@ namespace ocean
         }
 
         // (not on every step: a row pass that does not store is handed the same dt's again by the next one, ocean_writeback.h)
-        if (a.storephase)
+        // (the quadrant form stores behind the barrier below: a table element is loaded by up to four threads of the workgroup)
+        if (!QPH && a.storephase)
         {
           #pragma unroll
           for(int s = 0; s < E; ++s)
@@ -815,6 +859,25 @@ namespace ocean
         swap_out[N] = h[0];
 
       __syncthreads();
+
+      // The quadrant form's store.  A table row belongs to ONE workgroup -- rows y and N - y are its pair -- but inside it an element is
+      // loaded by the threads of x and N - x in both rows and stored by one of them: the store waits until every thread of the workgroup
+      // has used what it loaded, which the barrier above says (each wrote its swap line from it).  One writer per element
+      // (ocean_quadrant.h): one row of the pair, the upper half of its slots, and x = 0 on top.
+      if constexpr (QPH)
+      {
+        if (advance && a.storephase && quadrant_row_stores(p, half))
+        {
+          int const upper = quadrant_upper(N, abs(y - N / 2), t) * 4;
+
+          #pragma unroll
+          for(int s = E / 2; s < E; ++s)
+            buf_store_f32_aux<PHASE_STORE_AUX>(ph[s], rphase, upper, quadrant_step(T, E, s) * 4);
+
+          if (quadrant_slot_stores(E, t, 0))
+            buf_store_f32_aux<PHASE_STORE_AUX>(ph[0], rphase, quadrant_lower(N, T, E, abs(y - N / 2), t) * 4, quadrant_step(T, E, 0) * 4);
+        }
+      }
 
       OCEAN_STAMP(2);
 
@@ -1410,13 +1473,34 @@ namespace ocean
   //|---------------------- phase-only advance --------------------------------
   // used when more than MAX_PENDING updates are queued between two displace calls
 
-  __global__ void ocean_advance_kernel(StepArgs a, int N)
+  // `quadrants`: the cascades whose phase is their quadrant table (ocean_quadrant.h), bit by bit: there the table is advanced, element k by
+  // the dispersion's element k -- the products and fmods every point of the plane with that index would be given
+  __global__ void ocean_advance_kernel(StepArgs a, int N, unsigned int quadrants)
   {
     int const cascade = blockIdx.y;
     size_t const plane = (size_t)N * N;
 
+    float const *table = a.omega + (size_t)cascade * quadrant_count(N);
+
+    if ((quadrants >> cascade) & 1)
+    {
+      float *q = a.qphase + (size_t)cascade * quadrant_count(N);
+
+      for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < quadrant_count(N); i += (size_t)gridDim.x * blockDim.x)
+      {
+        float omega = table[i];
+
+        float p = q[i];
+        for(int k = 0; k < a.ndt; ++k)
+          p = advance_phase(p, omega * a.dt[k]);
+
+        q[i] = p;
+      }
+
+      return;
+    }
+
     float *phase = a.phase + cascade * plane;
-    float const *table = a.omega + (size_t)cascade * (N / 2 + 1) * (N / 2 + 1);
 
     for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (size_t)gridDim.x * blockDim.x)
     {

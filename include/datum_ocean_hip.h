@@ -66,7 +66,8 @@ extern "C" {
  *      datum_ocean_read_ripple_foam, datum_ocean_sample_ripple_foam and datum_ocean_query_ripple_foam; then dispersive ripples,
  *      datum_ocean_set_ripple_dispersion and datum_ocean_ripple_deep_weights; then ripple walls, datum_ocean_set_ripple_walls,
  *      datum_ocean_ripple_walls_device and datum_ocean_read_ripple_walls; then the ripple bed, datum_ocean_set_ripple_bed,
- *      datum_ocean_ripple_bed_device and datum_ocean_read_ripple_bed.
+ *      datum_ocean_ripple_bed_device and datum_ocean_read_ripple_bed; then the phase's store, datum_ocean_set_phase_store and
+ *      datum_ocean_phase_store.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -208,6 +209,22 @@ int datum_ocean_map_store_policy(datum_ocean_t ctx, int *policy, int *streamed);
  * beginning of an interval).  The getter reports the interval in use. */
 int datum_ocean_set_phase_writeback(datum_ocean_t ctx, int every);
 int datum_ocean_phase_writeback(datum_ocean_t ctx, int *every);
+
+/* Where the module keeps the phase (added at ABI 9 without a bump; a consumer detects the two entry points by symbol).  update_ocean's
+ * dispersion depends on (|y - N/2|, |x - N/2|) alone, so a phase that is a function of that index -- the zero phase of datum_ocean_create, of
+ * datum_ocean_upload_state without a phase and of datum_ocean_rebuild_height, or an uploaded or resumed one that a device-side test finds
+ * symmetric bit for bit -- stays one under every datum_ocean_update, whatever its dt.  AUTO (default): such a cascade's phase is kept as an
+ * (N/2 + 1)^2 table and, where that holds for every cascade of the handle, none of them is outside [0, 2 pi), and neither the literal mode
+ * nor the velocity plane is on, the row pass reads the table instead of the N^2 plane: the same values from a quarter of the bytes.
+ * PLANE: always the plane, the behaviour of earlier builds.  Results do not depend on the mode, bit for bit, and WHAT A CALLER MAY ASSUME
+ * above holds as it stands: every call that returns, copies, replaces or re-interprets the phase sees the plane it would have seen.
+ * datum_ocean_resume_state now waits for the stream (it reads the test's result back).  DATUM_OCEAN_ESTATE while a profile is open.  The
+ * getter reports the mode and, one bit per cascade, the cascades whose phase is a table at this moment: the next row pass reads the tables
+ * if the bits of all cascades are set after the datum_ocean_displace that ran it. */
+#define DATUM_OCEAN_PHASE_STORE_AUTO 0
+#define DATUM_OCEAN_PHASE_STORE_PLANE 1
+int datum_ocean_set_phase_store(datum_ocean_t ctx, int mode);
+int datum_ocean_phase_store(datum_ocean_t ctx, int *mode, unsigned int *quadrants);
 
 int datum_ocean_upload_state(datum_ocean_t ctx, int cascade, float const *h0, float const *phase);
 int datum_ocean_read_state(datum_ocean_t ctx, int cascade, float *phase);

@@ -71,6 +71,48 @@ struct BindablePlane
   T *get() const { return bound ? bound : own; }   // the plane in use
 };
 
+// bytes of each guard round a plane of the ripple layer's: the plane keeps hipMalloc's alignment to that
+constexpr size_t RIPPLE_GUARD_BYTES = 256;
+
+// a device plane of the ripple layer's between two guards of 0xCD bytes, filled once and never written again: no kernel's resource covers
+// the guards, and a test finds them whole.  Nothing is allocated, and get() is null, while the plane is off
+// (in the module's own namespace: its functions are no symbols of the library)
+namespace
+{
+  template<typename T>
+  struct GuardedPlane
+  {
+    T *block = nullptr;                 // the allocation: a guard, the plane, a guard
+    T *plane = nullptr;
+    T *get() const { return plane; }
+
+    static_assert(RIPPLE_GUARD_BYTES % sizeof(T) == 0, "a guard is a whole number of cells");
+
+    // the fill goes on `stream`; after a failure the caller releases
+    hipError_t allocate(size_t cells, hipStream_t stream)
+    {
+      size_t const bytes = cells * sizeof(T) + 2 * RIPPLE_GUARD_BYTES;
+
+      hipError_t e = hipMalloc(&block, bytes);
+      if (e == hipSuccess)
+        e = hipMemsetAsync(block, 0xCD, bytes, stream);
+      if (e == hipSuccess)
+        plane = block + RIPPLE_GUARD_BYTES / sizeof(T);
+
+      return e;
+    }
+
+    hipError_t release()
+    {
+      hipError_t const e = hipFree(block);
+      if (e == hipSuccess)
+        block = plane = nullptr;
+
+      return e;
+    }
+  };
+}
+
 // a device buffer of a host entry point's (read_*) staging, grown on demand
 struct Staging
 {
@@ -168,8 +210,7 @@ struct datum_ocean_ctx
   int rippleR = 0;                    // cells per side, 0 = off
   double ripples = 0.0;               // cell side, metres
   int rippleox = 0, rippleoy = 0;     // the window's origin, cells
-  float2 *ripplestate[2] = { nullptr, nullptr };
-  float2 *ripplestateblock[2] = { nullptr, nullptr };   // their allocations: a guard, the buffer, a guard (0xCD bytes; no kernel's resource covers the guards)
+  GuardedPlane<float2> ripplestate[2];   // the two state buffers: R x R cells of (height, rate) on the layer's torus
   int ripplecurrent = 0;              // the state buffer the next sub-step reads
   int *ripplesrc = nullptr;           // pending deposits
   double ripplec = 2.0, ripplegamma = 0.05, ripplespongegamma = 4.0;   // datum_ocean_set_ripple_params
@@ -184,21 +225,17 @@ struct datum_ocean_ctx
   bool rippleboundscurrent = false;   // the record is that of the current state buffer: set by reduce_ripple_bounds, cleared by every call that writes a state buffer
 
   // wake foam (datum_ocean_set_ripple_foam): nothing is allocated while ripplefoam is null; freed with the layer
-  float *ripplefoamblock = nullptr;   // the allocation: a guard, the plane, a guard (the guards hold 0xCD bytes; no kernel's resource covers them)
-  float *ripplefoam = nullptr;        // the plane: R x R coverage on the layer's torus
+  GuardedPlane<float> ripplefoam;     // the plane: R x R coverage on the layer's torus
   float ripplefoamt1 = 0.04f, ripplefoamk1 = 10.0f, ripplefoamt2 = 0.5f, ripplefoamk2 = 2.0f, ripplefoamdecay = 0.5f;   // datum_ocean_set_ripple_foam_params
 
   // ripple walls (datum_ocean_set_ripple_walls): nothing is allocated while ripplewall is null; freed with the layer
-  unsigned char *ripplewallblock = nullptr;             // the allocation: a guard, the plane, a guard (256 bytes of 0xCD each; no kernel's resource covers them)
-  unsigned char *ripplewall = nullptr;                  // the plane: R x R bytes on the layer's torus, 1 = wall
+  GuardedPlane<unsigned char> ripplewall;               // the plane: R x R bytes on the layer's torus, 1 = wall
   datum_ocean_ripple_wall *ripplewalllist = nullptr;    // the handle's copy of the records, on the device
   int ripplewallcount = 0;
 
   // the ripple bed (datum_ocean_set_ripple_bed): nothing is allocated while ripplebed is null; freed with the layer
-  float *ripplebedblock = nullptr;                      // the allocation: a guard, the depth plane, a guard (256 bytes of 0xCD each; no kernel's resource covers them)
-  float *ripplebed = nullptr;                           // the depth plane: R x R floats on the layer's torus, +0 = solid
-  unsigned char *ripplesurfblock = nullptr;             // a guard, the surf plane, a guard
-  unsigned char *ripplesurf = nullptr;                  // the surf plane: R x R bytes, 0 .. DATUM_OCEAN_RIPPLE_SURF_LEVELS
+  GuardedPlane<float> ripplebed;                        // the depth plane: R x R floats on the layer's torus, +0 = solid
+  GuardedPlane<unsigned char> ripplesurf;               // the surf plane: R x R bytes, 0 .. DATUM_OCEAN_RIPPLE_SURF_LEVELS
   float *ripplebedmap = nullptr;                        // the handle's copy of the map, on the device
   datum_ocean_ripple_bed ripplebedparams = {};
 
@@ -241,6 +278,14 @@ namespace
     (void)hipGetLastError();   // the runtime's sticky last-error must not leak into a later, unrelated call
 
     return code;
+  }
+
+  // a refusal a shared check words for the call it serves: the text is exactly name + text
+  int fail(datum_ocean_ctx *ctx, int code, char const *name, char const *text)
+  {
+    std::string const head = name;
+
+    return fail(ctx, code, (head + text).c_str());
   }
 
   #define HIPCHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, (int)e_, #call); } while(0)
@@ -1179,15 +1224,15 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)hipFree(ctx->foam.own);
   (void)hipFree(ctx->velocity.own);
   (void)hipFree(ctx->velocitywork);
-  (void)hipFree(ctx->ripplestateblock[0]);
-  (void)hipFree(ctx->ripplestateblock[1]);
+  (void)ctx->ripplestate[0].release();
+  (void)ctx->ripplestate[1].release();
   (void)hipFree(ctx->ripplesrc);
   (void)hipFree(ctx->rippleboundsblock);
-  (void)hipFree(ctx->ripplefoamblock);
-  (void)hipFree(ctx->ripplewallblock);
+  (void)ctx->ripplefoam.release();
+  (void)ctx->ripplewall.release();
   (void)hipFree(ctx->ripplewalllist);
-  (void)hipFree(ctx->ripplebedblock);
-  (void)hipFree(ctx->ripplesurfblock);
+  (void)ctx->ripplebed.release();
+  (void)ctx->ripplesurf.release();
   (void)hipFree(ctx->ripplebedmap);
 
   for(Staging &st : ctx->staging)
@@ -2428,16 +2473,14 @@ namespace
   // the arrays of a one-point-per-thread query; `name` goes into the error text
   int check_points(datum_ocean_ctx *ctx, void const *points, size_t count, void const *samples, char const *name)
   {
-    std::string const what = name;
-
     if (count > 0 && (!points || !samples))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or samples").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null points or samples");
 
     if (((uintptr_t)points & 7) || ((uintptr_t)samples & 15))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and samples 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": points must be 8-byte and samples 16-byte aligned");
 
     if (count > (size_t)INT32_MAX)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": count above INT32_MAX").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": count above INT32_MAX");
 
     return DATUM_OCEAN_OK;
   }
@@ -2445,16 +2488,14 @@ namespace
   // the argument checks both single-cascade entry points share
   int check_surface_args(datum_ocean_ctx *ctx, int cascade, datum_ocean_set const *set, int iterations, void const *points, size_t count, void const *samples, char const *name)
   {
-    std::string const what = name;
-
     if (!ctx || !set)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle or set").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null handle or set");
 
     if (cascade < 0 || cascade >= ctx->cascades)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": cascade out of range");
 
     if (iterations < 0 || iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]");
 
     return check_points(ctx, points, count, samples, name);
   }
@@ -2530,20 +2571,18 @@ namespace
   // the list's checks, shared by every entry point that takes one; `name` goes into the error text
   int check_blend_list(datum_ocean_ctx *ctx, Query const &q, char const *name)
   {
-    std::string const what = name;
-
     if (!ctx)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null handle").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null handle");
 
     if (!q.cascades)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null cascade list").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null cascade list");
 
     if (q.count < 1 || q.count > DATUM_OCEAN_MAX_CASCADES)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": count outside [1, DATUM_OCEAN_MAX_CASCADES]").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": count outside [1, DATUM_OCEAN_MAX_CASCADES]");
 
     for(int i = 0; i < q.count; ++i)
       if (q.cascades[i] < 0 || q.cascades[i] >= ctx->cascades)
-        return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": cascade out of range").c_str());
+        return fail(ctx, DATUM_OCEAN_EINVAL, name, ": cascade out of range");
 
     return DATUM_OCEAN_OK;
   }
@@ -2555,13 +2594,11 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (!q.set)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null set").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null set");
 
     if (q.iterations < 0 || q.iterations > DATUM_OCEAN_SURFACE_MAX_ITERATIONS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": iterations outside [0, DATUM_OCEAN_SURFACE_MAX_ITERATIONS]");
 
     return DATUM_OCEAN_OK;
   }
@@ -2605,20 +2642,18 @@ namespace
   // what the several-cascade mesh calls check; `name` goes into the error text
   int check_gen_blend_args(datum_ocean_ctx *ctx, Query const &q, int sizex, int sizey, void const *vertices, char const *name)
   {
-    std::string const what = name;
-
     if (!ctx || !q.set || !vertices)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null argument").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null argument");
 
     int rc = check_blend_list(ctx, q, name);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
     if (sizex < 2 || sizey < 2)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": mesh must be at least 2 x 2").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": mesh must be at least 2 x 2");
 
     if ((uintptr_t)vertices & 15)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": vertex buffer must be 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": vertex buffer must be 16-byte aligned");
 
     return DATUM_OCEAN_OK;
   }
@@ -2753,13 +2788,11 @@ namespace
   // what read_velocity and the two queries refuse; `name` goes into the error text
   int check_velocity_state(datum_ocean_ctx *ctx, char const *name)
   {
-    std::string const what = name;
-
     if (ctx->velocitymode == DATUM_OCEAN_VELOCITY_OFF)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": velocity is off (datum_ocean_set_velocity)").c_str());
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": velocity is off (datum_ocean_set_velocity)");
 
     if (!ctx->velocitycurrent)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": no datum_ocean_displace since velocity was switched on").c_str());
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": no datum_ocean_displace since velocity was switched on");
 
     return DATUM_OCEAN_OK;
   }
@@ -2947,16 +2980,14 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if ((b.nbodies > 0 && (!b.bodies || !b.records)) || (b.nprobes > 0 && !b.probes))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null bodies, probes or records").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null bodies, probes or records");
 
     if (((uintptr_t)b.bodies & 15) || ((uintptr_t)b.probes & 15) || ((uintptr_t)b.records & 15))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": bodies, probes and records must be 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": bodies, probes and records must be 16-byte aligned");
 
     if (b.nbodies > (size_t)INT32_MAX || b.nprobes > (size_t)INT32_MAX)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": nbodies or nprobes above INT32_MAX").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": nbodies or nprobes above INT32_MAX");
 
     return DATUM_OCEAN_OK;
   }
@@ -3089,13 +3120,11 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (b.nbodies > 0 && !b.motions)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null motions").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null motions");
 
     if ((uintptr_t)b.motions & 15)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": motions must be 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": motions must be 16-byte aligned");
 
     return check_velocity_state(ctx, name);
   }
@@ -3172,19 +3201,17 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (b.nbodies > 0 && (!b.motions || !b.props))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null motions or props").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null motions or props");
 
     if (((uintptr_t)b.motions & 15) || ((uintptr_t)b.props & 15))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": motions and props must be 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": motions and props must be 16-byte aligned");
 
     if (substeps < 1 || substeps > DATUM_OCEAN_STEP_MAX_SUBSTEPS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": substeps outside [1, DATUM_OCEAN_STEP_MAX_SUBSTEPS]").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": substeps outside [1, DATUM_OCEAN_STEP_MAX_SUBSTEPS]");
 
     if (!std::isfinite(dt))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt is not finite").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": dt is not finite");
 
     return check_velocity_state(ctx, name);
   }
@@ -3255,22 +3282,177 @@ int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int cou
 
 }   // extern "C"
 
-/* -- the ripple layer (ocean_ripple.hip) ------------------------------------------------------------------------------------------ */
+/* -- the ripple layer's planes: the window read, and the wake foam's, the walls' and the bed's share of the layer's own calls --------------- */
 
 namespace
 {
   size_t ripple_cells(datum_ocean_ctx const *ctx) { return (size_t)ctx->rippleR * ctx->rippleR; }
 
+  // a plane of the layer's in window order, from the torus in memory: the copies of ripple_window's rectangles, on the handle's stream
+  // (the caller waits)
+  template<typename T>
+  int read_ripple_window(datum_ocean_ctx *ctx, T const *plane, T *host)
+  {
+    size_t const pitch = (size_t)ctx->rippleR * sizeof(T);
+
+    RippleRect rect[4];
+
+    int const n = ripple_window(ctx->rippleox, ctx->rippleoy, ctx->rippleR, rect);
+
+    for(int k = 0; k < n; ++k)
+      HIPCHECK(ctx, hipMemcpy2DAsync(host + rect[k].to, pitch, plane + rect[k].from, pitch, (size_t)rect[k].w * sizeof(T), (size_t)rect[k].h, hipMemcpyDeviceToHost, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // wake foam's share of set_ripples, reset_ripples and center_ripples: each does nothing while the foam is off
+
+  int free_ripple_foam(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, ctx->ripplefoam.release());
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // no foam anywhere, on the handle's stream
+  int clear_ripple_foam(datum_ocean_ctx *ctx)
+  {
+    if (ctx->ripplefoam.get())
+      HIPCHECK(ctx, hipMemsetAsync(ctx->ripplefoam.get(), 0, ripple_cells(ctx) * sizeof(float), ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the window moved from (oldx, oldy) to g's origin: the cells that entered hold no foam
+  int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy)
+  {
+    if (!ctx->ripplefoam.get())
+      return DATUM_OCEAN_OK;
+
+    RippleFoamScrollArgs a;
+    a.foam = ctx->ripplefoam.get();
+    a.g = g;
+    a.oldx = oldx;
+    a.oldy = oldy;
+
+    HIPCHECK(ctx, launch_ripple_foam_scroll(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // what the walls' raster and the bed's take alike: the grid, the cell side and the two state buffers, which the launch writes with
+  // `zero` (the ripple bounds' record is then no longer that of the current one)
+  template<typename Args>
+  void fill_ripple_raster(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero, Args &a)
+  {
+    a.state[0] = ctx->ripplestate[0].get();
+    a.state[1] = ctx->ripplestate[1].get();
+    a.zero = zero ? 1 : 0;
+    a.g = g;
+    a.s = (float)ctx->ripples;
+
+    ctx->rippleboundscurrent = ctx->rippleboundscurrent && !zero;
+  }
+
+  // the walls' share of set_ripples and center_ripples: each does nothing while walls are off
+
+  int free_ripple_walls(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, ctx->ripplewall.release());
+    HIPCHECK(ctx, hipFree(ctx->ripplewalllist));
+    ctx->ripplewalllist = nullptr;
+    ctx->ripplewallcount = 0;
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the whole plane from the handle's list at g's origin, on the handle's stream; with `zero` the wall cells' state in both buffers too
+  int raster_ripple_walls(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
+  {
+    if (!ctx->ripplewall.get())
+      return DATUM_OCEAN_OK;
+
+    RippleWallRasterArgs a;
+    a.wall = ctx->ripplewall.get();
+    a.walls = ctx->ripplewalllist;
+    a.count = ctx->ripplewallcount;
+    fill_ripple_raster(ctx, g, zero, a);
+
+    HIPCHECK(ctx, launch_ripple_wall_raster(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the bed's share of set_ripples, center_ripples and set_ripple_walls: each does nothing while the bed is off
+
+  int free_ripple_bed(datum_ocean_ctx *ctx)
+  {
+    HIPCHECK(ctx, ctx->ripplebed.release());
+    HIPCHECK(ctx, ctx->ripplesurf.release());
+    HIPCHECK(ctx, hipFree(ctx->ripplebedmap));
+    ctx->ripplebedmap = nullptr;
+    ctx->ripplebedparams = {};
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // the bed's share of a sub-step's arguments, the surf table for a sub-step of length h, rounded once from double:
+  // fsurf[q] = 1 / (1 + h surf_gamma (q / 16)^2), beside the sponge table's entries: exactly 1 at q = 0
+  void fill_ripple_surf(datum_ocean_ctx const *ctx, float h, float *fsurf)
+  {
+    for(int q = 0; q <= RIPPLE_SURF_LEVELS; ++q)
+    {
+      double const u = (double)q / RIPPLE_SURF_LEVELS;
+
+      fsurf[q] = (float)(1.0 / (1.0 + (double)h * ((double)ctx->ripplebedparams.surf_gamma * (u * u))));
+    }
+  }
+
+  // both planes whole from the handle's map, its parameters and the wall plane at g's origin, on the handle's stream (behind the wall
+  // raster, where there is one); with `zero` the solid cells' state in both buffers too
+  int raster_ripple_bed(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
+  {
+    if (!ctx->ripplebed.get())
+      return DATUM_OCEAN_OK;
+
+    datum_ocean_ripple_bed const &p = ctx->ripplebedparams;
+
+    RippleBedRasterArgs a;
+    a.depth = ctx->ripplebed.get();
+    a.surf = ctx->ripplesurf.get();
+    a.map = ctx->ripplebedmap;
+    a.wall = ctx->ripplewall.get();
+    fill_ripple_raster(ctx, g, zero, a);
+
+    a.b.width = p.width;
+    a.b.height = p.height;
+    a.b.ox = p.origin[0];
+    a.b.oy = p.origin[1];
+    a.b.invt = (float)(1.0 / (double)p.texel);
+    a.b.outside = p.outside;
+    a.b.max_depth = p.max_depth;
+    a.b.dry_depth = p.dry_depth;
+    a.b.surf_depth = p.surf_depth;
+    a.b.invsurf = p.surf_depth > 0.0f ? (float)(1.0 / (double)p.surf_depth) : 0.0f;
+
+    HIPCHECK(ctx, launch_ripple_bed_raster(a, ctx->stream));
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+/* -- the ripple layer (ocean_ripple.hip) ------------------------------------------------------------------------------------------ */
+
+namespace
+{
   // what every call that needs the layer refuses; `name` goes into the error text
   int check_ripples(datum_ocean_ctx *ctx, char const *name)
   {
-    std::string const what = name;
-
     if (!ctx)
-      return fail(nullptr, DATUM_OCEAN_EINVAL, (what + ": null handle").c_str());
+      return fail(nullptr, DATUM_OCEAN_EINVAL, name, ": null handle");
 
     if (ctx->rippleR == 0)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": the ripple layer is off (datum_ocean_set_ripples)").c_str());
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": the ripple layer is off (datum_ocean_set_ripples)");
 
     return DATUM_OCEAN_OK;
   }
@@ -3284,26 +3466,6 @@ namespace
     g.invs = (float)(1.0 / ctx->ripples);
     return g;
   }
-
-  // wake foam's share of set_ripples, reset_ripples and center_ripples ("wake foam", below): each does nothing while the foam is off
-  int free_ripple_foam(datum_ocean_ctx *ctx);
-  int clear_ripple_foam(datum_ocean_ctx *ctx);
-  int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy);
-
-  // the walls' share of set_ripples and center_ripples ("ripple walls", below): each does nothing while walls are off
-  int free_ripple_walls(datum_ocean_ctx *ctx);
-  int raster_ripple_walls(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero);
-
-  // the bed's share of set_ripples, center_ripples and set_ripple_walls ("ripple bed", below): each does nothing while the bed is off
-  int free_ripple_bed(datum_ocean_ctx *ctx);
-  int raster_ripple_bed(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero);
-
-  // the bed's share of a sub-step's arguments: the surf table for a sub-step of length h, rounded once from double
-  void fill_ripple_surf(datum_ocean_ctx const *ctx, float h, float *fsurf);
-
-  // the two state buffers between their guards ("the ripple layer's state buffers", below)
-  hipError_t alloc_ripple_state(datum_ocean_ctx *ctx, size_t cells);
-  int free_ripple_state(datum_ocean_ctx *ctx);
 
   int free_ripples(datum_ocean_ctx *ctx)
   {
@@ -3319,10 +3481,8 @@ namespace
     if (rcb != DATUM_OCEAN_OK)
       return rcb;
 
-    int const rcs = free_ripple_state(ctx);
-    if (rcs != DATUM_OCEAN_OK)
-      return rcs;
-
+    HIPCHECK(ctx, ctx->ripplestate[0].release());
+    HIPCHECK(ctx, ctx->ripplestate[1].release());
     HIPCHECK(ctx, hipFree(ctx->ripplesrc));
     ctx->ripplesrc = nullptr;
     HIPCHECK(ctx, hipFree(ctx->rippleboundsblock));
@@ -3340,8 +3500,8 @@ namespace
 
     ctx->rippleboundscurrent = false;
 
-    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[0], 0, cells * sizeof(float2), ctx->stream));
-    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[1], 0, cells * sizeof(float2), ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[0].get(), 0, cells * sizeof(float2), ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(ctx->ripplestate[1].get(), 0, cells * sizeof(float2), ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(ctx->ripplesrc, 0, cells * sizeof(int), ctx->stream));
 
     return DATUM_OCEAN_OK;
@@ -3351,7 +3511,7 @@ namespace
   int run_ripple_samples(datum_ocean_ctx *ctx, void const *points, size_t n, void *out)
   {
     RippleSampleArgs a;
-    a.state = ctx->ripplestate[ctx->ripplecurrent];
+    a.state = ctx->ripplestate[ctx->ripplecurrent].get();
     a.points = static_cast<float2 const*>(points);
     a.samples = static_cast<float4*>(out);
     a.g = ripple_grid(ctx);
@@ -3369,16 +3529,14 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (n > 0 && !impulses)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null impulses").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null impulses");
 
     if ((uintptr_t)impulses & 15)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": impulses must be 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": impulses must be 16-byte aligned");
 
     if (n > (size_t)INT32_MAX / 16)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX / 16").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": n above INT32_MAX / 16");
 
     return DATUM_OCEAN_OK;
   }
@@ -3405,7 +3563,7 @@ namespace
       return rc;
 
     if (!std::isfinite(dt))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (std::string(name) + ": dt is not finite").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": dt is not finite");
 
     return check_body_drag_args(ctx, q, b, name);
   }
@@ -3428,7 +3586,7 @@ namespace
   // sqrt(g max_depth)
   double ripple_courant(datum_ocean_ctx const *ctx, float h)
   {
-    double const c = ctx->ripplebed ? std::sqrt(ctx->rippleg * (double)ctx->ripplebedparams.max_depth) : ctx->ripplec;
+    double const c = ctx->ripplebed.get() ? std::sqrt(ctx->rippleg * (double)ctx->ripplebedparams.max_depth) : ctx->ripplec;
 
     return c * (double)h / ctx->ripples;
   }
@@ -3458,15 +3616,13 @@ namespace
   // the stability rule of the layer's mode for a sub-step of length h; `wave` is what a refusal in the WAVE mode says behind the call's name
   int check_ripple_stability(datum_ocean_ctx *ctx, float h, char const *name, char const *wave)
   {
-    std::string const what = name;
-
     if (ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP)
     {
       if (ripple_deep_bound(ctx, h) > 1.9)
-        return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt / substeps * sqrt(g * sum|F| / s) above 1.9, the DEEP step's stability bound of 2 with a margin").c_str());
+        return fail(ctx, DATUM_OCEAN_EINVAL, name, ": dt / substeps * sqrt(g * sum|F| / s) above 1.9, the DEEP step's stability bound of 2 with a margin");
     }
     else if (ripple_courant(ctx, h) > 0.7)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + wave).c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, wave);
 
     return DATUM_OCEAN_OK;
   }
@@ -3491,9 +3647,9 @@ namespace
   {
     RippleStep r = {};
     r.deep = ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP;
-    r.wall = ctx->ripplewall;
-    r.bed = ctx->ripplebed;
-    r.surf = ctx->ripplesurf;
+    r.wall = ctx->ripplewall.get();
+    r.bed = ctx->ripplebed.get();
+    r.surf = ctx->ripplesurf.get();
 
     if (r.bed)
     {
@@ -3564,16 +3720,14 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (n > 0 && (!points || !out))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or out").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null points or out");
 
     if (((uintptr_t)points & 7) || ((uintptr_t)out & 15))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and out 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": points must be 8-byte and out 16-byte aligned");
 
     if (n > (size_t)INT32_MAX / 16)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX / 16").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": n above INT32_MAX / 16");
 
     return DATUM_OCEAN_OK;
   }
@@ -3602,7 +3756,9 @@ int datum_ocean_set_ripples(datum_ocean_t ctx, int R, float s)
 
   size_t const cells = (size_t)R * R;
 
-  hipError_t e = alloc_ripple_state(ctx, cells);
+  hipError_t e = ctx->ripplestate[0].allocate(cells, ctx->stream);
+  if (e == hipSuccess)
+    e = ctx->ripplestate[1].allocate(cells, ctx->stream);
   if (e == hipSuccess)
     e = hipMalloc(&ctx->ripplesrc, cells * sizeof(int));
 
@@ -3662,7 +3818,7 @@ int datum_ocean_set_ripple_dispersion(datum_ocean_t ctx, int mode, float g)
   if (!std::isfinite(g) || !(g > 0.0f))
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_dispersion: g must be finite and positive");
 
-  if (mode == DATUM_OCEAN_RIPPLE_DEEP && ctx->ripplebed)
+  if (mode == DATUM_OCEAN_RIPPLE_DEEP && ctx->ripplebed.get())
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_ripple_dispersion: a ripple bed is set, and the bed and the DEEP mode do not combine (datum_ocean_set_ripple_bed)");
 
   ctx->rippledispersion = mode;
@@ -3701,8 +3857,8 @@ int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   RippleScrollArgs a;
-  a.state[0] = ctx->ripplestate[0];
-  a.state[1] = ctx->ripplestate[1];
+  a.state[0] = ctx->ripplestate[0].get();
+  a.state[1] = ctx->ripplestate[1].get();
   a.src = ctx->ripplesrc;
   a.oldx = g.ox;
   a.oldy = g.oy;
@@ -3754,7 +3910,7 @@ int datum_ocean_ripples_device(datum_ocean_t ctx, void **device_ptr, size_t *byt
   if (!device_ptr)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripples_device: null argument");
 
-  *device_ptr = ctx->ripplestate[ctx->ripplecurrent];
+  *device_ptr = ctx->ripplestate[ctx->ripplecurrent].get();
 
   if (bytes)
     *bytes = ripple_cells(ctx) * sizeof(float2);
@@ -3777,23 +3933,9 @@ int datum_ocean_read_ripples(datum_ocean_t ctx, float *state)
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // window order from the torus: up to four rectangles, split where the window wraps in memory
-  int const R = ctx->rippleR;
-  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
-
-  float2 const *src = ctx->ripplestate[ctx->ripplecurrent];
-  float2 *dst = reinterpret_cast<float2*>(state);
-
-  size_t const pitch = (size_t)R * sizeof(float2);
-
-  // (window columns [0, R - mx) are memory columns [mx, R), the rest memory columns [0, mx); rows likewise)
-  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
-  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
-
-  for(int j = 0; j < 2; ++j)
-    for(int i = 0; i < 2; ++i)
-      if (w[i] > 0 && h[j] > 0)
-        HIPCHECK(ctx, hipMemcpy2DAsync(dst + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i] * sizeof(float2), (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+  rc = read_ripple_window(ctx, ctx->ripplestate[ctx->ripplecurrent].get(), reinterpret_cast<float2*>(state));
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
@@ -3828,8 +3970,8 @@ int datum_ocean_step_ripples(datum_ocean_t ctx, float dt, int substeps)
 
   for(int i = 0; i < substeps; ++i)
   {
-    r.a.s.in = ctx->ripplestate[ctx->ripplecurrent];
-    r.a.s.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
+    r.a.s.in = ctx->ripplestate[ctx->ripplecurrent].get();
+    r.a.s.out = ctx->ripplestate[ctx->ripplecurrent ^ 1].get();
 
     HIPCHECK(ctx, launch_ripple_step(r, i == 0, ctx->stream));
 
@@ -3954,28 +4096,26 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (call.steps < 1 || call.steps > DATUM_OCEAN_RAY_MAX_STEPS)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": steps outside [1, DATUM_OCEAN_RAY_MAX_STEPS]").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": steps outside [1, DATUM_OCEAN_RAY_MAX_STEPS]");
 
     if (call.refine < 0 || call.refine > DATUM_OCEAN_RAY_MAX_REFINE)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": refine outside [0, DATUM_OCEAN_RAY_MAX_REFINE]").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": refine outside [0, DATUM_OCEAN_RAY_MAX_REFINE]");
 
     if (call.n > 0 && (!call.rays || !call.records))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null rays or records").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null rays or records");
 
     if (((uintptr_t)call.rays & 15) || ((uintptr_t)call.records & 15))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": rays and records must be 16-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": rays and records must be 16-byte aligned");
 
     if (call.n > (size_t)INT32_MAX)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": n above INT32_MAX");
 
     if (v.bounded && !ctx->boundscurrent)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": the bounds are not current (datum_ocean_reduce_bounds after the last displace or bind_maps)").c_str());
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": the bounds are not current (datum_ocean_reduce_bounds after the last displace or bind_maps)");
 
     if (v.bounded && v.rippled && !ctx->rippleboundscurrent)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (what + ": the ripple bounds are not current (datum_ocean_reduce_ripple_bounds after the last call that stepped, moved, reset or set the layer)").c_str());
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": the ripple bounds are not current (datum_ocean_reduce_ripple_bounds after the last call that stepped, moved, reset or set the layer)");
 
     return DATUM_OCEAN_OK;
   }
@@ -4235,10 +4375,8 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (!std::isfinite(dt) || dt < 0.0f)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": dt is not finite or is negative").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": dt is not finite or is negative");
 
     rc = check_step_args(ctx, q, b, dt, substeps, name);
     if (rc != DATUM_OCEAN_OK)
@@ -4269,15 +4407,15 @@ namespace
     {
       if (b.nbodies > 0)
       {
-        a.state = ctx->ripplestate[ctx->ripplecurrent];
+        a.state = ctx->ripplestate[ctx->ripplecurrent].get();
         a.first = i == 0;
 
         HIPCHECK(ctx, launch_couple(a, ctx->stream));
       }
 
       // datum_ocean_step_ripples(h, 1): the first form takes the deposits in, and no kernel clears src
-      r.a.s.in = ctx->ripplestate[ctx->ripplecurrent];
-      r.a.s.out = ctx->ripplestate[ctx->ripplecurrent ^ 1];
+      r.a.s.in = ctx->ripplestate[ctx->ripplecurrent].get();
+      r.a.s.out = ctx->ripplestate[ctx->ripplecurrent ^ 1].get();
 
       HIPCHECK(ctx, launch_ripple_step(r, true, ctx->stream));
 
@@ -4339,7 +4477,7 @@ namespace
   RippledLayer rippled_layer(datum_ocean_ctx const *ctx)
   {
     RippledLayer l;
-    l.state = ctx->ripplestate[ctx->ripplecurrent];
+    l.state = ctx->ripplestate[ctx->ripplecurrent].get();
     l.g = ripple_grid(ctx);
     return l;
   }
@@ -5169,90 +5307,7 @@ int datum_ocean_algorithmic_bytes(datum_ocean_t ctx, double *rowpass_bytes, doub
 
 }
 
-/* -- the ripple layer's state buffers: each between two guards ------------------------------------------------------------------------------ */
-
-namespace
-{
-  // 32 cells, 256 bytes, of 0xCD bytes before and after each state buffer, filled once: the buffers keep hipMalloc's alignment, the step
-  // kernels' resources cover exactly the buffers, and a test finds the guards whole (tests/test_gpu_ripple_deep.py)
-  constexpr size_t RIPPLE_STATE_GUARD = 32;
-
-  hipError_t alloc_ripple_state(datum_ocean_ctx *ctx, size_t cells)
-  {
-    size_t const bytes = (cells + 2 * RIPPLE_STATE_GUARD) * sizeof(float2);
-
-    for(int i = 0; i < 2; ++i)
-    {
-      hipError_t e = hipMalloc(&ctx->ripplestateblock[i], bytes);
-
-      if (e == hipSuccess)
-        e = hipMemsetAsync(ctx->ripplestateblock[i], 0xCD, bytes, ctx->stream);
-
-      if (e != hipSuccess)
-        return e;
-
-      ctx->ripplestate[i] = ctx->ripplestateblock[i] + RIPPLE_STATE_GUARD;
-    }
-
-    return hipSuccess;
-  }
-
-  int free_ripple_state(datum_ocean_ctx *ctx)
-  {
-    for(int i = 0; i < 2; ++i)
-    {
-      HIPCHECK(ctx, hipFree(ctx->ripplestateblock[i]));
-      ctx->ripplestateblock[i] = nullptr;
-      ctx->ripplestate[i] = nullptr;
-    }
-
-    return DATUM_OCEAN_OK;
-  }
-}
-
 /* -- ripple walls: a byte plane beside the ripple layer (ocean_ripple_wall.hip) ------------------------------------------------------------ */
-
-namespace
-{
-  // bytes of each guard round the plane: the plane keeps hipMalloc's alignment to that
-  constexpr size_t RIPPLE_WALL_GUARD = 256;
-
-  int free_ripple_walls(datum_ocean_ctx *ctx)
-  {
-    HIPCHECK(ctx, hipFree(ctx->ripplewallblock));
-    ctx->ripplewallblock = nullptr;
-    ctx->ripplewall = nullptr;
-    HIPCHECK(ctx, hipFree(ctx->ripplewalllist));
-    ctx->ripplewalllist = nullptr;
-    ctx->ripplewallcount = 0;
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // the whole plane from the handle's list at g's origin, on the handle's stream; with `zero` the wall cells' state in both buffers too
-  int raster_ripple_walls(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
-  {
-    if (!ctx->ripplewall)
-      return DATUM_OCEAN_OK;
-
-    RippleWallRasterArgs a;
-    a.wall = ctx->ripplewall;
-    a.state[0] = ctx->ripplestate[0];
-    a.state[1] = ctx->ripplestate[1];
-    a.walls = ctx->ripplewalllist;
-    a.count = ctx->ripplewallcount;
-    a.zero = zero ? 1 : 0;
-
-    // (with `zero` the launch writes both state buffers: the ripple bounds' record is no longer that of the current one)
-    ctx->rippleboundscurrent = ctx->rippleboundscurrent && !zero;
-    a.g = g;
-    a.s = (float)ctx->ripples;
-
-    HIPCHECK(ctx, launch_ripple_wall_raster(a, ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
-}
 
 extern "C"
 {
@@ -5298,11 +5353,7 @@ int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall cons
   if (count == 0)
     return raster_ripple_bed(ctx, ripple_grid(ctx), false);
 
-  size_t const cells = ripple_cells(ctx), bytes = cells + 2 * RIPPLE_WALL_GUARD;
-
-  hipError_t e = hipMalloc(&ctx->ripplewallblock, bytes);
-  if (e == hipSuccess)
-    e = hipMemsetAsync(ctx->ripplewallblock, 0xCD, bytes, ctx->stream);
+  hipError_t e = ctx->ripplewall.allocate(ripple_cells(ctx), ctx->stream);
   if (e == hipSuccess)
     e = hipMalloc(&ctx->ripplewalllist, (size_t)count * sizeof(datum_ocean_ripple_wall));
   // (the caller's array may go away behind the call: the copy is waited for)
@@ -5317,7 +5368,6 @@ int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall cons
     return fail(ctx, (int)e, "datum_ocean_set_ripple_walls: hipMalloc");
   }
 
-  ctx->ripplewall = ctx->ripplewallblock + RIPPLE_WALL_GUARD;
   ctx->ripplewallcount = count;
 
   rc = raster_ripple_walls(ctx, ripple_grid(ctx), true);
@@ -5333,7 +5383,7 @@ int datum_ocean_ripple_walls_device(datum_ocean_t ctx, unsigned char const **pla
   if (!plane)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_walls_device: null argument");
 
-  *plane = ctx->ripplewall;
+  *plane = ctx->ripplewall.get();
 
   return DATUM_OCEAN_OK;
 }
@@ -5344,7 +5394,7 @@ int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host)
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  if (!ctx->ripplewall)
+  if (!ctx->ripplewall.get())
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_read_ripple_walls: walls are off (datum_ocean_set_ripple_walls)");
 
   if (!host)
@@ -5352,21 +5402,9 @@ int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host)
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // window order from the torus, as datum_ocean_read_ripple_foam: up to four rectangles, split where the window wraps in memory
-  int const R = ctx->rippleR;
-  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
-
-  unsigned char const *src = ctx->ripplewall;
-
-  size_t const pitch = (size_t)R;
-
-  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
-  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
-
-  for(int j = 0; j < 2; ++j)
-    for(int i = 0; i < 2; ++i)
-      if (w[i] > 0 && h[j] > 0)
-        HIPCHECK(ctx, hipMemcpy2DAsync(host + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i], (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+  rc = read_ripple_window(ctx, ctx->ripplewall.get(), host);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
@@ -5376,77 +5414,6 @@ int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host)
 }
 
 /* -- the ripple bed: depth and surf planes beside the ripple layer (ocean_ripple_bed.hip) ------------------------------------------------- */
-
-namespace
-{
-  // bytes of each guard round either plane: the planes keep hipMalloc's alignment to that
-  constexpr size_t RIPPLE_BED_GUARD = 256;
-
-  int free_ripple_bed(datum_ocean_ctx *ctx)
-  {
-    HIPCHECK(ctx, hipFree(ctx->ripplebedblock));
-    ctx->ripplebedblock = nullptr;
-    ctx->ripplebed = nullptr;
-    HIPCHECK(ctx, hipFree(ctx->ripplesurfblock));
-    ctx->ripplesurfblock = nullptr;
-    ctx->ripplesurf = nullptr;
-    HIPCHECK(ctx, hipFree(ctx->ripplebedmap));
-    ctx->ripplebedmap = nullptr;
-    ctx->ripplebedparams = {};
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // fsurf[q] = 1 / (1 + h surf_gamma (q / 16)^2), in double beside the sponge table's entries: exactly 1 at q = 0
-  void fill_ripple_surf(datum_ocean_ctx const *ctx, float h, float *fsurf)
-  {
-    for(int q = 0; q <= RIPPLE_SURF_LEVELS; ++q)
-    {
-      double const u = (double)q / RIPPLE_SURF_LEVELS;
-
-      fsurf[q] = (float)(1.0 / (1.0 + (double)h * ((double)ctx->ripplebedparams.surf_gamma * (u * u))));
-    }
-  }
-
-  // both planes whole from the handle's map, its parameters and the wall plane at g's origin, on the handle's stream (behind the wall
-  // raster, where there is one); with `zero` the solid cells' state in both buffers too
-  int raster_ripple_bed(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
-  {
-    if (!ctx->ripplebed)
-      return DATUM_OCEAN_OK;
-
-    datum_ocean_ripple_bed const &p = ctx->ripplebedparams;
-
-    RippleBedRasterArgs a;
-    a.depth = ctx->ripplebed;
-    a.surf = ctx->ripplesurf;
-    a.state[0] = ctx->ripplestate[0];
-    a.state[1] = ctx->ripplestate[1];
-    a.map = ctx->ripplebedmap;
-    a.wall = ctx->ripplewall;
-    a.zero = zero ? 1 : 0;
-
-    // (with `zero` the launch writes both state buffers: the ripple bounds' record is no longer that of the current one)
-    ctx->rippleboundscurrent = ctx->rippleboundscurrent && !zero;
-    a.g = g;
-    a.s = (float)ctx->ripples;
-
-    a.b.width = p.width;
-    a.b.height = p.height;
-    a.b.ox = p.origin[0];
-    a.b.oy = p.origin[1];
-    a.b.invt = (float)(1.0 / (double)p.texel);
-    a.b.outside = p.outside;
-    a.b.max_depth = p.max_depth;
-    a.b.dry_depth = p.dry_depth;
-    a.b.surf_depth = p.surf_depth;
-    a.b.invsurf = p.surf_depth > 0.0f ? (float)(1.0 / (double)p.surf_depth) : 0.0f;
-
-    HIPCHECK(ctx, launch_ripple_bed_raster(a, ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
-}
 
 extern "C"
 {
@@ -5501,15 +5468,10 @@ int datum_ocean_set_ripple_bed(datum_ocean_t ctx, datum_ocean_ripple_bed const *
     return rc;
 
   size_t const cells = ripple_cells(ctx), texels = (size_t)bed->width * bed->height;
-  size_t const dbytes = cells * sizeof(float) + 2 * RIPPLE_BED_GUARD, qbytes = cells + 2 * RIPPLE_BED_GUARD;
 
-  hipError_t e = hipMalloc(&ctx->ripplebedblock, dbytes);
+  hipError_t e = ctx->ripplebed.allocate(cells, ctx->stream);
   if (e == hipSuccess)
-    e = hipMemsetAsync(ctx->ripplebedblock, 0xCD, dbytes, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMalloc(&ctx->ripplesurfblock, qbytes);
-  if (e == hipSuccess)
-    e = hipMemsetAsync(ctx->ripplesurfblock, 0xCD, qbytes, ctx->stream);
+    e = ctx->ripplesurf.allocate(cells, ctx->stream);
   if (e == hipSuccess)
     e = hipMalloc(&ctx->ripplebedmap, texels * sizeof(float));
   // (the caller's array may go away behind the call: the copy is waited for)
@@ -5524,8 +5486,6 @@ int datum_ocean_set_ripple_bed(datum_ocean_t ctx, datum_ocean_ripple_bed const *
     return fail(ctx, (int)e, "datum_ocean_set_ripple_bed: hipMalloc");
   }
 
-  ctx->ripplebed = ctx->ripplebedblock + RIPPLE_BED_GUARD / sizeof(float);
-  ctx->ripplesurf = ctx->ripplesurfblock + RIPPLE_BED_GUARD;
   ctx->ripplebedparams = *bed;
 
   return raster_ripple_bed(ctx, ripple_grid(ctx), true);
@@ -5537,11 +5497,11 @@ int datum_ocean_ripple_bed_device(datum_ocean_t ctx, void **depth, void **surf, 
     return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_bed_device: null handle");
 
   if (depth)
-    *depth = ctx->ripplebed;
+    *depth = ctx->ripplebed.get();
   if (surf)
-    *surf = ctx->ripplesurf;
+    *surf = ctx->ripplesurf.get();
   if (cells)
-    *cells = ctx->ripplebed ? ripple_cells(ctx) : 0;
+    *cells = ctx->ripplebed.get() ? ripple_cells(ctx) : 0;
 
   return DATUM_OCEAN_OK;
 }
@@ -5552,29 +5512,17 @@ int datum_ocean_read_ripple_bed(datum_ocean_t ctx, float *depth, unsigned char *
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
-  if (!ctx->ripplebed)
+  if (!ctx->ripplebed.get())
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_read_ripple_bed: the bed is off (datum_ocean_set_ripple_bed)");
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // window order from the torus, as datum_ocean_read_ripple_walls: up to four rectangles a plane, split where the window wraps in memory
-  int const R = ctx->rippleR;
-  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
-
-  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
-  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
-
-  for(int j = 0; j < 2; ++j)
-    for(int i = 0; i < 2; ++i)
-      if (w[i] > 0 && h[j] > 0)
-      {
-        size_t const to = (size_t)dy[j] * R + dx[i], from = (size_t)sy[j] * R + sx[i];
-
-        if (depth)
-          HIPCHECK(ctx, hipMemcpy2DAsync(depth + to, (size_t)R * sizeof(float), ctx->ripplebed + from, (size_t)R * sizeof(float), (size_t)w[i] * sizeof(float), (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
-        if (surf)
-          HIPCHECK(ctx, hipMemcpy2DAsync(surf + to, (size_t)R, ctx->ripplesurf + from, (size_t)R, (size_t)w[i], (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
-      }
+  if (depth)
+    rc = read_ripple_window(ctx, ctx->ripplebed.get(), depth);
+  if (rc == DATUM_OCEAN_OK && surf)
+    rc = read_ripple_window(ctx, ctx->ripplesurf.get(), surf);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
@@ -5587,44 +5535,6 @@ int datum_ocean_read_ripple_bed(datum_ocean_t ctx, float *depth, unsigned char *
 
 namespace
 {
-  // floats of each guard round the plane: 256 bytes, so the plane keeps hipMalloc's alignment to that
-  constexpr size_t RIPPLE_FOAM_GUARD = 64;
-
-  int free_ripple_foam(datum_ocean_ctx *ctx)
-  {
-    HIPCHECK(ctx, hipFree(ctx->ripplefoamblock));
-    ctx->ripplefoamblock = nullptr;
-    ctx->ripplefoam = nullptr;
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // no foam anywhere, on the handle's stream
-  int clear_ripple_foam(datum_ocean_ctx *ctx)
-  {
-    if (ctx->ripplefoam)
-      HIPCHECK(ctx, hipMemsetAsync(ctx->ripplefoam, 0, ripple_cells(ctx) * sizeof(float), ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
-
-  // the window moved from (oldx, oldy) to g's origin: the cells that entered hold no foam
-  int scroll_ripple_foam(datum_ocean_ctx *ctx, RippleGrid const &g, int oldx, int oldy)
-  {
-    if (!ctx->ripplefoam)
-      return DATUM_OCEAN_OK;
-
-    RippleFoamScrollArgs a;
-    a.foam = ctx->ripplefoam;
-    a.g = g;
-    a.oldx = oldx;
-    a.oldy = oldy;
-
-    HIPCHECK(ctx, launch_ripple_foam_scroll(a, ctx->stream));
-
-    return DATUM_OCEAN_OK;
-  }
-
   // what every call that needs the plane refuses, the layer first; `name` goes into the error text
   int check_ripple_foam(datum_ocean_ctx *ctx, char const *name)
   {
@@ -5632,8 +5542,8 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    if (!ctx->ripplefoam)
-      return fail(ctx, DATUM_OCEAN_ESTATE, (std::string(name) + ": the wake foam is off (datum_ocean_set_ripple_foam)").c_str());
+    if (!ctx->ripplefoam.get())
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": the wake foam is off (datum_ocean_set_ripple_foam)");
 
     return DATUM_OCEAN_OK;
   }
@@ -5644,16 +5554,14 @@ namespace
     if (rc != DATUM_OCEAN_OK)
       return rc;
 
-    std::string const what = name;
-
     if (n > 0 && (!points || !out))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": null points or out").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null points or out");
 
     if (((uintptr_t)points & 7) || ((uintptr_t)out & 3))
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": points must be 8-byte and out 4-byte aligned").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": points must be 8-byte and out 4-byte aligned");
 
     if (n > (size_t)INT32_MAX / 16)
-      return fail(ctx, DATUM_OCEAN_EINVAL, (what + ": n above INT32_MAX / 16").c_str());
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": n above INT32_MAX / 16");
 
     return DATUM_OCEAN_OK;
   }
@@ -5662,7 +5570,7 @@ namespace
   int run_ripple_foam_samples(datum_ocean_ctx *ctx, void const *points, size_t n, void *out)
   {
     RippleFoamSampleArgs a;
-    a.foam = ctx->ripplefoam;
+    a.foam = ctx->ripplefoam.get();
     a.points = static_cast<float2 const*>(points);
     a.samples = static_cast<float*>(out);
     a.g = ripple_grid(ctx);
@@ -5690,19 +5598,13 @@ int datum_ocean_set_ripple_foam(datum_ocean_t ctx, int on)
   if (rc != DATUM_OCEAN_OK || !on)
     return rc;
 
-  size_t const bytes = (ripple_cells(ctx) + 2 * RIPPLE_FOAM_GUARD) * sizeof(float);
-
-  hipError_t e = hipMalloc(&ctx->ripplefoamblock, bytes);
-  if (e == hipSuccess)
-    e = hipMemsetAsync(ctx->ripplefoamblock, 0xCD, bytes, ctx->stream);
+  hipError_t const e = ctx->ripplefoam.allocate(ripple_cells(ctx), ctx->stream);
 
   if (e != hipSuccess)
   {
     (void)free_ripple_foam(ctx);
     return fail(ctx, (int)e, "datum_ocean_set_ripple_foam: hipMalloc");
   }
-
-  ctx->ripplefoam = ctx->ripplefoamblock + RIPPLE_FOAM_GUARD;
 
   rc = clear_ripple_foam(ctx);
   if (rc != DATUM_OCEAN_OK)
@@ -5749,8 +5651,8 @@ int datum_ocean_step_ripple_foam(datum_ocean_t ctx, float dt)
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
   RippleFoamArgs a;
-  a.state = ctx->ripplestate[ctx->ripplecurrent];
-  a.foam = ctx->ripplefoam;
+  a.state = ctx->ripplestate[ctx->ripplecurrent].get();
+  a.foam = ctx->ripplefoam.get();
   a.g = ripple_grid(ctx);
   a.p.hinv = 0.5f * a.g.invs;
   a.p.t1 = ctx->ripplefoamt1;
@@ -5784,7 +5686,7 @@ int datum_ocean_ripple_foam_device(datum_ocean_t ctx, void **device_ptr, size_t 
   if (!device_ptr)
     return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_foam_device: null argument");
 
-  *device_ptr = ctx->ripplefoam;
+  *device_ptr = ctx->ripplefoam.get();
 
   if (bytes)
     *bytes = ripple_cells(ctx) * sizeof(float);
@@ -5807,21 +5709,9 @@ int datum_ocean_read_ripple_foam(datum_ocean_t ctx, float *plane)
 
   HIPCHECK(ctx, hipSetDevice(ctx->device));
 
-  // window order from the torus, as datum_ocean_read_ripples: up to four rectangles, split where the window wraps in memory
-  int const R = ctx->rippleR;
-  int const mx = ripple_wrap(ctx->rippleox, R), my = ripple_wrap(ctx->rippleoy, R);
-
-  float const *src = ctx->ripplefoam;
-
-  size_t const pitch = (size_t)R * sizeof(float);
-
-  int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
-  int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
-
-  for(int j = 0; j < 2; ++j)
-    for(int i = 0; i < 2; ++i)
-      if (w[i] > 0 && h[j] > 0)
-        HIPCHECK(ctx, hipMemcpy2DAsync(plane + (size_t)dy[j] * R + dx[i], pitch, src + (size_t)sy[j] * R + sx[i], pitch, (size_t)w[i] * sizeof(float), (size_t)h[j], hipMemcpyDeviceToHost, ctx->stream));
+  rc = read_ripple_window(ctx, ctx->ripplefoam.get(), plane);
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
 
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
@@ -5858,7 +5748,8 @@ int datum_ocean_query_ripple_foam(datum_ocean_t ctx, float const *points, size_t
 
 namespace
 {
-  // the block of datum_ocean_reduce_ripple_bounds in float4s: guard, partials, guard, record, guard (2 float4 = 32 bytes each but the partials)
+  // the block of datum_ocean_reduce_ripple_bounds in float4s: guard, partials, guard, record, guard (2 float4 = 32 bytes each but the partials).
+  // No GuardedPlane: that is one region between 256-byte guards, this is two regions in one allocation with a guard between them too
   constexpr size_t RIPPLE_BOUNDS_GUARD = 2;
 
   float4 *ripple_bounds_partials(datum_ocean_ctx const *ctx) { return ctx->rippleboundsblock + RIPPLE_BOUNDS_GUARD; }
@@ -5895,7 +5786,7 @@ namespace
     }
 
     RippleBoundsArgs a;
-    a.state = reinterpret_cast<float4 const*>(ctx->ripplestate[ctx->ripplecurrent]);
+    a.state = reinterpret_cast<float4 const*>(ctx->ripplestate[ctx->ripplecurrent].get());
     a.partials = ripple_bounds_partials(ctx);
     a.record = ripple_bounds_record(ctx);
     a.pairs = (int)(ripple_cells(ctx) / 2);

@@ -38,6 +38,29 @@ namespace ocean
     return ripple_wrap(J, R) * R + ripple_wrap(I, R);
   }
 
+  // The window at origin (ox, oy) as it lies in memory, for a host that copies a plane out in window order: window columns [0, R - mx)
+  // are memory columns [mx, R) and the rest memory columns [0, mx), mx = ox mod R; rows likewise.  One to four rectangles, split where
+  // the window wraps, none empty: cell offsets into the plane in memory (from) and into the R x R window (to), width and height in
+  // cells.  Returns their number.  No kernel calls it
+  struct RippleRect { int from, to, w, h; };
+
+  inline int ripple_window(int ox, int oy, int R, RippleRect rect[4])
+  {
+    int const mx = ripple_wrap(ox, R), my = ripple_wrap(oy, R);
+
+    int const w[2] = { R - mx, mx }, h[2] = { R - my, my };
+    int const sx[2] = { mx, 0 }, sy[2] = { my, 0 }, dx[2] = { 0, R - mx }, dy[2] = { 0, R - my };
+
+    int n = 0;
+
+    for(int j = 0; j < 2; ++j)
+      for(int i = 0; i < 2; ++i)
+        if (w[i] > 0 && h[j] > 0)
+          rect[n++] = RippleRect{ sy[j] * R + sx[i], dy[j] * R + dx[i], w[i], h[j] };
+
+    return n;
+  }
+
   // ox <= I < ox + R and the same for J (the difference taken modulo 2^32: no I, ox below 2^30 + R in size can alias)
   OB_HD bool ripple_inside(RippleGrid const &g, int I, int J)
   {

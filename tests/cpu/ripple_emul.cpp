@@ -43,6 +43,24 @@ int ripple_emul_index(int I, int J, int R) { return ripple_index(I, J, R); }
 int ripple_emul_inside(int R, int ox, int oy, int I, int J) { return ripple_inside(grid(R, ox, oy, 1.0f), I, J) ? 1 : 0; }
 int ripple_emul_sponge(int wx, int wy, int R, int B) { return ripple_sponge(wx, wy, R, B); }
 
+// the window's rectangles in memory, rects [4][4]: from, to, w, h of each; returns their number
+int ripple_emul_window(int ox, int oy, int R, int *rects)
+{
+  RippleRect rect[4];
+
+  int const n = ripple_window(ox, oy, R, rect);
+
+  for(int k = 0; k < n; ++k)
+  {
+    rects[4 * k] = rect[k].from;
+    rects[4 * k + 1] = rect[k].to;
+    rects[4 * k + 2] = rect[k].w;
+    rects[4 * k + 3] = rect[k].h;
+  }
+
+  return n;
+}
+
 // one sub-step over the layer in MEMORY order, as the kernel walks it: in, out [R*R][2], src [R*R], f [B + 1]
 void ripple_emul_substep(float const *in, float *out, int const *src, int R, int ox, int oy, int B, float h, float c2s2, float const *f, int first)
 {

@@ -140,9 +140,41 @@ def test_the_kernels_call_the_header():
     for fn in ("ocean_ripple.h", "ripple_update(", "ripple_splat(", "ripple_sample(", "wake_terms(", "body_tree("):
         assert fn in emul, fn
     section = host.split("/* -- the ripple layer (ocean_ripple.hip)")[1].split("/* -- ray casts")[0]
-    assert section.count("hipMemsetAsync(") == 4 and section.count(", ctx->stream)") == 11
+    # (the read-back's copies are read_ripple_window's, ahead of the section; the two state buffers' fills name the stream here)
+    assert section.count("hipMemsetAsync(") == 4 and section.count(", ctx->stream)") == 12
+    assert section.count("read_ripple_window(ctx, ") == 1 and section.count(".allocate(cells, ctx->stream)") == 2
     # (the wake's host twin copies its arrays in and out through the body calls' shared staging, which names the handle's stream as well)
     staging = host.split("/* -- body buoyancy (ocean_body.hip)")[1].split("/* -- body drag")[0]
     assert section.count("stage_batch(") == 1 and section.count("fetch_batch(") == 1 and len(re.findall(r"hipMemcpyAsync\([^;]*, ctx->stream\)\);", staging)) == staging.count("hipMemcpyAsync(") == 4
     for word in ("hipMemset(", "hipMemcpy(", "hipDeviceSynchronize", ", 0)", "nullptr)"):
         assert word not in section.replace("fail(nullptr", ""), word
+
+
+def test_guarded_planes_and_the_window_read_stand_once():
+    """ocean_capi.hip: a plane between its 0xCD guards is GuardedPlane, stated once beside the bounds block's own guards; the window-order
+    read is read_ripple_window, the file's one user of the 2D copy; the helpers the layer's section calls stand ahead of it, so nothing is
+    declared ahead of its definition; and a refusal under a shared check's name is fail(ctx, code, name, text)"""
+    host, header = read_csrc("ocean_capi.hip"), read_csrc("ocean_ripple.h")
+    assert host.count("hipMemcpy2DAsync(") == 1 and host.count("int read_ripple_window(") == 1 and host.count("read_ripple_window(ctx, ") == 5
+    assert len(re.findall(r"hipMemsetAsync\([^;]*0xCD[^;]*\)", host)) == 2
+    assert re.findall(r"constexpr \w+ (\w*GUARD\w*) =", host) == ["RIPPLE_GUARD_BYTES", "RIPPLE_BOUNDS_GUARD"] and "RIPPLE_GUARD_BYTES = 256;" in host
+    assert host.count("struct GuardedPlane") == 1 and len(re.findall(r"GuardedPlane<[\w ]+> ripple(state\[2\]|foam|wall|bed|surf);", host)) == 5
+    assert len(re.findall(r"\.allocate\(\w+\(?\w*\)?, ctx->stream\)", host)) == 6 and host.count(".release()") == 12
+    for gone in ("(what + ", "std::string(name) +", "ripplestateblock", "ripplefoamblock", "ripplewallblock", "ripplebedblock", "ripplesurfblock"):
+        assert gone not in host, gone
+    assert host.count("int fail(datum_ocean_ctx *ctx, int code, char const *name, char const *text)") == 1
+    # the shared helpers: ahead of the layer's section, each defined once and declared nowhere else, everything on the handle's stream
+    planes = host.split("/* -- the ripple layer's planes")[1].split("/* -- the ripple layer (ocean_ripple.hip)")[0]
+    for fn in ("int free_ripple_foam(", "int clear_ripple_foam(", "int scroll_ripple_foam(", "int free_ripple_walls(", "int raster_ripple_walls(",
+               "int free_ripple_bed(", "int raster_ripple_bed(", "void fill_ripple_surf(", "void fill_ripple_raster(", "size_t ripple_cells("):
+        assert planes.count(fn) == 1 and host.count(fn) == 1, fn
+    assert "alloc_ripple_state(" not in host and "free_ripple_state(" not in host
+    assert planes.count("fill_ripple_raster(ctx, g, zero, a);") == 2 and host.count("ctx->rippleboundscurrent && !zero") == 1
+    assert planes.count("hipMemsetAsync(") == 1 and planes.count(", ctx->stream)") == 5
+    for word in ("hipMemset(", "hipMemcpy(", "hipDeviceSynchronize", ", 0)", "nullptr)"):
+        assert word not in planes, word
+    # the rectangles are ocean_ripple.h's, which the CPU walks (tests/test_ripple_emul.py); no kernel file names them
+    assert header.count("inline int ripple_window(") == 1 and host.count("ripple_window(ctx->rippleox, ctx->rippleoy, ctx->rippleR, rect)") == 1
+    for kernels in ("ocean_ripple.hip", "ocean_ripple_deep.hip", "ocean_ripple_foam.hip", "ocean_ripple_wall.hip", "ocean_ripple_bed.hip", "ocean_ripple_bounds.hip", "ocean_rippled.hip"):
+        assert "ripple_window(" not in read_csrc(kernels), kernels
+    assert "ripple_window(" in open(os.path.join(ROOT, "tests", "cpu", "ripple_emul.cpp"), encoding="utf-8").read()

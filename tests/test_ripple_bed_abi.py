@@ -160,7 +160,7 @@ def test_the_kernels_call_the_header():
     coupled = host.split("int run_step_bodies_coupled(")[1].split('extern "C"')[0]
     assert "bed" not in step.lower() and "bed" not in coupled.lower()
     assert host.count("raster_ripple_bed(ctx, ") == 4 and host.count("free_ripple_bed(ctx)") == 3
-    assert host.count("ctx->ripplebed ? std::sqrt(ctx->rippleg * (double)ctx->ripplebedparams.max_depth) : ctx->ripplec") == 1
+    assert host.count("ctx->ripplebed.get() ? std::sqrt(ctx->rippleg * (double)ctx->ripplebedparams.max_depth) : ctx->ripplec") == 1
     setter = host.split("int datum_ocean_set_ripple_dispersion(")[1].split("int datum_ocean_ripple_deep_weights(")[0]
     assert "mode == DATUM_OCEAN_RIPPLE_DEEP && ctx->ripplebed" in setter and "DATUM_OCEAN_ESTATE" in setter
 

@@ -38,6 +38,7 @@ def emul():
     lib.ripple_emul_splat.restype = ctypes.c_longlong
     lib.ripple_emul_sample.argtypes = [P, I, I, I, Fl, P, I, P]
     lib.ripple_emul_wake.argtypes = [P, P, I, P, I, P, P, Fl, P, I, I, I, Fl, P]
+    lib.ripple_emul_window.argtypes = [I, I, I, P]
     return lib
 
 
@@ -105,6 +106,29 @@ def test_addressing(emul):
     for B in (0, 1, 8, 64):
         k = ripple64.sponge_index(wx, wy, R, B)
         assert all(emul.ripple_emul_sponge(int(x), int(y), R, B) == k[y, x] for x in (0, 1, 7, 8, 31, 32, 56, 62, 63) for y in (0, 5, 8, 33, 63))
+
+
+@pytest.mark.parametrize("R", (64, 128))
+def test_window_rectangles(emul, R):
+    """ripple_window, by whose rectangles the host copies a plane out in window order: with both coordinates of the origin from the list,
+    the rectangles number at most four, none is empty, each lies within the rows it starts in, they are disjoint and cover R^2 cells, and
+    a plane of cell indices scattered through them is plane[(J mod R), (I mod R)] at the window's (I, J)"""
+    plane = np.arange(R * R).reshape(R, R)
+    wy, wx = np.mgrid[0:R, 0:R]
+    rects = np.zeros((4, 4), np.int32)
+    for ox in (-R // 2, 0, 1, R // 2, R - 1, -1, -R - 3, 5 * R + 17):
+        for oy in (-R // 2, 0, 1, R // 2, R - 1, -1, -R - 3, 5 * R + 17):
+            n = emul.ripple_emul_window(ox, oy, R, _p(rects))
+            assert 1 <= n <= 4, (ox, oy, n)
+            window = np.full((R, R), -1)
+            for src, dst, w, h in rects[:n].tolist():
+                assert w > 0 and h > 0, (ox, oy, w, h)
+                sy, sx, dy, dx = src // R, src % R, dst // R, dst % R
+                assert 0 <= src and sx + w <= R and sy + h <= R and 0 <= dst and dx + w <= R and dy + h <= R, (ox, oy, src, dst, w, h)
+                assert np.all(window[dy:dy + h, dx:dx + w] == -1), (ox, oy)          # disjoint
+                window[dy:dy + h, dx:dx + w] = plane[sy:sy + h, sx:sx + w]
+            assert sum(w * h for _, _, w, h in rects[:n].tolist()) == R * R
+            assert np.array_equal(window, plane[(oy + wy) % R, (ox + wx) % R]), (ox, oy)
 
 
 def _emul_splat(emul, lay, imp):

@@ -132,10 +132,17 @@ def test_the_kernels_call_the_header():
     # the host section: ahead of the ripple bounds', on the handle's stream, the layer's check shared
     section = host.split("/* -- wake foam: a coverage plane beside the ripple layer (ocean_ripple_foam.hip)")[1].split("/* -- bounds of the ripple layer")[0]
     assert section.count("check_ripples(ctx, ") == 2 and section.count("check_ripple_foam(ctx, ") == 5 and section.count("check_ripple_foam_points(ctx, ") == 2
-    assert section.count("hipMemsetAsync(") == 2 and section.count("read_staged(ctx, ") == 1 and section.count("(float)std::exp(-(double)ctx->ripplefoamdecay * (double)dt)") == 1
+    # (the section fills nothing itself: the guards' fill is GuardedPlane's, the plane's the one memset of clear_ripple_foam, which stands
+    # with the other two hooks ahead of the ripple layer's section)
+    hooks = host.split("/* -- the ripple layer's planes")[1].split("/* -- the ripple layer (ocean_ripple.hip)")[0]
+    assert section.count("hipMemsetAsync(") == 0 and hooks.count("hipMemsetAsync(") == 1 and section.count("ctx->ripplefoam.allocate(ripple_cells(ctx), ctx->stream)") == 1
+    assert "hipMemsetAsync(ctx->ripplefoam.get(), 0, ripple_cells(ctx) * sizeof(float), ctx->stream)" in hooks.split("int clear_ripple_foam(")[1].split("\n  }\n")[0]
+    assert section.count("read_staged(ctx, ") == 1 and section.count("(float)std::exp(-(double)ctx->ripplefoamdecay * (double)dt)") == 1
     for word in ("hipMemset(", "hipMemcpy(", "hipDeviceSynchronize", "rippleboundscurrent"):
         assert word not in section, word
-    for launch in re.findall(r"launch_ripple_foam\w*\([^;]*\)\);", section):
+    launches = re.findall(r"launch_ripple_foam\w*\([^;]*\)\);", section + hooks)
+    assert len(launches) == 3
+    for launch in launches:
         assert launch.endswith(", ctx->stream));"), launch
     # the three hooks are called from the ripple layer's section
     ripple = host.split("/* -- the ripple layer (ocean_ripple.hip)")[1].split("/* -- ray casts")[0]

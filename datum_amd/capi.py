@@ -194,6 +194,11 @@ SYMBOLS = {
     "datum_ocean_set_ripple_bed": (I, [P, P, P]),
     "datum_ocean_ripple_bed_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]),
     "datum_ocean_read_ripple_bed": (I, [P, P, P]),
+    # ripple swell: the FFT swell reflects off ripple walls and the beach
+    "datum_ocean_set_ripple_swell": (I, [P, I]),
+    "datum_ocean_refresh_ripple_swell": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I]),
+    "datum_ocean_ripple_swell_device": (I, [P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(I)]),
+    "datum_ocean_read_ripple_swell": (I, [P, P]),
 }
 
 
@@ -925,6 +930,30 @@ class Ocean:
         depth, surf = np.empty((R, R), np.float32), np.empty((R, R), np.uint8)
         self._check(self.lib.datum_ocean_read_ripple_bed(self.h, _ptr(depth), _ptr(surf)))
         return depth, surf
+
+    def set_ripple_swell(self, on=True):
+        """the FFT swell as a source of the layer at every solid face (walls, dry land): True allocates the forcing plane, zeroed and
+        not current; False frees it.  WAVE mode only.  The step reads the plane only while it is current (refresh_ripple_swell)."""
+        self._check(self.lib.datum_ocean_set_ripple_swell(self.h, int(on)))
+
+    def refresh_ripple_swell(self, cascades, oceanset, iterations=4):
+        """one launch writes the forcing plane whole from the summed surface of the listed cascades (sample_surface_blend's list, set
+        and iterations), the solid cells and the origin, and marks it current; call it after displace and center_ripples, before a step"""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_refresh_ripple_swell(self.h, arr, n, ctypes.byref(oceanset), iterations))
+
+    def ripple_swell_device(self):
+        """(pointer, bytes, current): the device plane in memory order, R * R floats; (None, 0, False) while swell is off"""
+        ptr, nbytes, current = P(), ctypes.c_size_t(), I()
+        self._check(self.lib.datum_ocean_ripple_swell_device(self.h, ctypes.byref(ptr), ctypes.byref(nbytes), ctypes.byref(current)))
+        return ptr.value, nbytes.value, bool(current.value)
+
+    def read_ripple_swell(self):
+        """the forcing plane in MEMORY order, (R, R) float32: [J mod R][I mod R] is world cell (I, J); blocking"""
+        R = int(round((self.ripples_device()[1] // 8) ** 0.5))
+        out = np.empty((R, R), np.float32)
+        self._check(self.lib.datum_ocean_read_ripple_swell(self.h, _ptr(out)))
+        return out
 
     def center_ripples(self, x, y):
         """Move the window so that the cell of (x, y) is its middle; the cells that entered are zeroed, none is copied."""

@@ -39,6 +39,7 @@
 #include "ocean_ripple_foam.hip"
 #include "ocean_ripple_wall.hip"
 #include "ocean_ripple_bed.hip"
+#include "ocean_ripple_swell.hip"
 
 using namespace ocean;
 
@@ -110,6 +111,35 @@ namespace
 
       return e;
     }
+  };
+
+  // ripple swell's forcing plane: a guarded plane of floats that starts as +0 everywhere, and the mark that says it is the function of
+  // the maps, the list and set, the solid cells and the origin that datum_ocean_refresh_ripple_swell last wrote.  A sub-step reads the
+  // plane only while the mark stands
+  struct RippleSwell : GuardedPlane<float>
+  {
+    bool current = false;
+
+    // the guards' fill, then the plane's zeroes, go on `stream`; after a failure the caller turns it off
+    hipError_t on(size_t cells, hipStream_t stream)
+    {
+      current = false;
+
+      hipError_t e = allocate(cells, stream);
+      if (e == hipSuccess)
+        e = hipMemsetAsync(plane, 0, cells * sizeof(float), stream);
+
+      return e;
+    }
+
+    hipError_t off()
+    {
+      current = false;
+
+      return release();
+    }
+
+    float const *fresh() const { return current ? plane : nullptr; }   // what a sub-step may read
   };
 }
 
@@ -238,6 +268,9 @@ struct datum_ocean_ctx
   GuardedPlane<unsigned char> ripplesurf;               // the surf plane: R x R bytes, 0 .. DATUM_OCEAN_RIPPLE_SURF_LEVELS
   float *ripplebedmap = nullptr;                        // the handle's copy of the map, on the device
   datum_ocean_ripple_bed ripplebedparams = {};
+
+  // ripple swell (datum_ocean_set_ripple_swell): nothing is allocated while rippleswell is null; freed with the layer
+  RippleSwell rippleswell;                              // the forcing plane: R x R floats on the layer's torus, and its CURRENT mark
 
   hipEvent_t complete = nullptr;      // "rendercomplete"
 
@@ -1234,6 +1267,7 @@ int datum_ocean_destroy(datum_ocean_t ctx)
   (void)ctx->ripplebed.release();
   (void)ctx->ripplesurf.release();
   (void)hipFree(ctx->ripplebedmap);
+  (void)ctx->rippleswell.off();
 
   for(Staging &st : ctx->staging)
     (void)hipFree(st.ptr);
@@ -3481,6 +3515,8 @@ namespace
     if (rcb != DATUM_OCEAN_OK)
       return rcb;
 
+    HIPCHECK(ctx, ctx->rippleswell.off());
+
     HIPCHECK(ctx, ctx->ripplestate[0].release());
     HIPCHECK(ctx, ctx->ripplestate[1].release());
     HIPCHECK(ctx, hipFree(ctx->ripplesrc));
@@ -3638,6 +3674,7 @@ namespace
     unsigned char const *surf;
     float gs2;
     float fsurf[RIPPLE_SURF_LEVELS + 1];
+    float const *swell;             // ripple swell's forcing plane, null while swell is off or its plane is not current
   };
 
   // what a sub-step of length h takes but its two state buffers: src, the grid, c2s2 and the sponge table, rounded once from double,
@@ -3650,6 +3687,7 @@ namespace
     r.wall = ctx->ripplewall.get();
     r.bed = ctx->ripplebed.get();
     r.surf = ctx->ripplesurf.get();
+    r.swell = ctx->rippleswell.fresh();
 
     if (r.bed)
     {
@@ -3680,9 +3718,11 @@ namespace
     return r;
   }
 
-  // the one place where the mode, the walls and the bed choose the kernel (the name is ocean::launch_ripple_step's: a call site reads
-  // the same in either mode, with walls or without, over a bed or not).  The bed's kernel runs whether walls are on or off: they are in
-  // its depths; the bed and the DEEP mode do not meet (both setters refuse)
+  // the one place where the mode, the walls, the bed and the swell choose the kernel (the name is ocean::launch_ripple_step's: a call
+  // site reads the same in either mode, with walls or without, over a bed or not).  The bed's kernel runs whether walls are on or off:
+  // they are in its depths; the bed and the DEEP mode do not meet (both setters refuse), nor do swell and the DEEP mode.  The swell's
+  // kernels run only while its plane is current (r.swell): a stale plane is never read, the parents' kernels run instead.  Swell
+  // without walls and without a bed has nothing solid and a plane of +0: the plain parent runs
   hipError_t launch_ripple_step(RippleStep &r, bool first, hipStream_t stream)
   {
     if (r.bed)
@@ -3694,7 +3734,21 @@ namespace
       b.gs2 = r.gs2;
       std::memcpy(b.fsurf, r.fsurf, sizeof b.fsurf);
 
+      if (r.swell)
+      {
+        RippleBedSwellStepArgs w = { b, r.swell };
+
+        return launch_ripple_bed_swell_step(w, first, stream);
+      }
+
       return launch_ripple_bed_step(b, first, stream);
+    }
+
+    if (r.swell && r.wall && !r.deep)
+    {
+      RippleWallSwellStepArgs w = { { r.a.s, r.wall }, r.swell };
+
+      return launch_ripple_step_walls_swell(w, first, stream);
     }
 
     if (r.wall && r.deep)
@@ -3821,6 +3875,9 @@ int datum_ocean_set_ripple_dispersion(datum_ocean_t ctx, int mode, float g)
   if (mode == DATUM_OCEAN_RIPPLE_DEEP && ctx->ripplebed.get())
     return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_ripple_dispersion: a ripple bed is set, and the bed and the DEEP mode do not combine (datum_ocean_set_ripple_bed)");
 
+  if (mode == DATUM_OCEAN_RIPPLE_DEEP && ctx->rippleswell.get())
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_ripple_dispersion: ripple swell is on, and swell and the DEEP mode do not combine (datum_ocean_set_ripple_swell)");
+
   ctx->rippledispersion = mode;
   ctx->rippleg = (double)g;
 
@@ -3867,6 +3924,7 @@ int datum_ocean_center_ripples(datum_ocean_t ctx, float x, float y)
   a.g = g;
 
   ctx->rippleboundscurrent = false;
+  ctx->rippleswell.current = false;
 
   HIPCHECK(ctx, launch_ripple_scroll(a, ctx->stream));
 
@@ -5349,6 +5407,8 @@ int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall cons
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
+  ctx->rippleswell.current = false;
+
   // (the wall byte enters the bed's depth: with or without walls now, a bed is rastered again)
   if (count == 0)
     return raster_ripple_bed(ctx, ripple_grid(ctx), false);
@@ -5463,6 +5523,8 @@ int datum_ocean_set_ripple_bed(datum_ocean_t ctx, datum_ocean_ripple_bed const *
   HIPCHECK(ctx, hipSetDevice(ctx->device));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
+  ctx->rippleswell.current = false;
+
   rc = free_ripple_bed(ctx);
   if (rc != DATUM_OCEAN_OK || !bed)
     return rc;
@@ -5524,6 +5586,126 @@ int datum_ocean_read_ripple_bed(datum_ocean_t ctx, float *depth, unsigned char *
   if (rc != DATUM_OCEAN_OK)
     return rc;
 
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  return DATUM_OCEAN_OK;
+}
+
+}
+
+/* -- ripple swell: a forcing plane beside the ripple layer (ocean_ripple_swell.hip) ------------------------------------------------------- */
+
+namespace
+{
+  // what every call that needs the plane refuses, the layer first; `name` goes into the error text
+  int check_ripple_swell(datum_ocean_ctx *ctx, char const *name)
+  {
+    int rc = check_ripples(ctx, name);
+    if (rc != DATUM_OCEAN_OK)
+      return rc;
+
+    if (!ctx->rippleswell.get())
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": ripple swell is off (datum_ocean_set_ripple_swell)");
+
+    return DATUM_OCEAN_OK;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_set_ripple_swell(datum_ocean_t ctx, int on)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_swell: null handle");
+
+  if (on != 0 && on != 1)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_set_ripple_swell: on must be 0 or 1");
+
+  int rc = check_ripples(ctx, "datum_ocean_set_ripple_swell");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (on && ctx->rippledispersion == DATUM_OCEAN_RIPPLE_DEEP)
+    return fail(ctx, DATUM_OCEAN_ESTATE, "datum_ocean_set_ripple_swell: the layer's mode is DATUM_OCEAN_RIPPLE_DEEP, and swell and the DEEP mode do not combine");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+  HIPCHECK(ctx, ctx->rippleswell.off());
+
+  if (!on)
+    return DATUM_OCEAN_OK;
+
+  hipError_t e = ctx->rippleswell.on(ripple_cells(ctx), ctx->stream);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(ctx->stream);
+
+  if (e != hipSuccess)
+  {
+    (void)ctx->rippleswell.off();
+    return fail(ctx, (int)e, "datum_ocean_set_ripple_swell: hipMalloc");
+  }
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_refresh_ripple_swell(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations)
+{
+  Query const q = { cascades, count, set, iterations };
+
+  // the layer and the plane first (a null handle EINVAL, either off ESTATE), then the blended sample's checks of the list, set and iterations
+  int rc = check_ripple_swell(ctx, "datum_ocean_refresh_ripple_swell");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_query(ctx, q, "datum_ocean_refresh_ripple_swell");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  RippleSwellRefreshArgs a;
+  a.swell = ctx->rippleswell.get();
+  a.wall = ctx->ripplewall.get();
+  a.depth = ctx->ripplebed.get();
+  a.g = ripple_grid(ctx);
+  a.s = (float)ctx->ripples;
+  a.q = query_args(ctx, q);
+
+  HIPCHECK(ctx, launch_ripple_swell_refresh(a, ctx->stream));
+
+  ctx->rippleswell.current = true;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_ripple_swell_device(datum_ocean_t ctx, void **plane, size_t *bytes, int *current)
+{
+  if (!ctx)
+    return fail(nullptr, DATUM_OCEAN_EINVAL, "datum_ocean_ripple_swell_device: null handle");
+
+  if (plane)
+    *plane = ctx->rippleswell.get();
+  if (bytes)
+    *bytes = ctx->rippleswell.get() ? ripple_cells(ctx) * sizeof(float) : 0;
+  if (current)
+    *current = ctx->rippleswell.current ? 1 : 0;
+
+  return DATUM_OCEAN_OK;
+}
+
+int datum_ocean_read_ripple_swell(datum_ocean_t ctx, float *plane)
+{
+  int rc = check_ripple_swell(ctx, "datum_ocean_read_ripple_swell");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  if (!plane)
+    return fail(ctx, DATUM_OCEAN_EINVAL, "datum_ocean_read_ripple_swell: null argument");
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  // (memory order: the plane as it lies on the torus, one copy)
+  HIPCHECK(ctx, hipMemcpyAsync(plane, ctx->rippleswell.get(), ripple_cells(ctx) * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
 
   return DATUM_OCEAN_OK;

@@ -468,6 +468,36 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_set_ocean_ripple_swell(void *c, int on)
+  {
+    try
+    {
+      set_ocean_ripple_swell(static_cast<HostContext*>(c)->context, on != 0);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_refresh_ocean_ripple_swell(void *c, void *p, int iterations)
+  {
+    try
+    {
+      refresh_ocean_ripple_swell(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
+  int datum_host_read_ocean_ripple_swell(void *c, float *plane)
+  {
+    try
+    {
+      read_ocean_ripple_swell(static_cast<HostContext*>(c)->context, plane);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_center_ocean_ripples(void *c, float x, float y)
   {
     try

@@ -1037,6 +1037,34 @@ void read_ocean_ripple_bed(OceanContext &context, float *depth, unsigned char *s
   check(context.hip, datum_ocean_read_ripple_bed(context.hip, depth, surf), "datum_ocean_read_ripple_bed");
 }
 
+void set_ocean_ripple_swell(OceanContext &context, bool on)
+{
+  if (!context.ready)
+    throw runtime_error("set_ocean_ripple_swell: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_set_ripple_swell(context.hip, on ? 1 : 0), "datum_ocean_set_ripple_swell");
+}
+
+void refresh_ocean_ripple_swell(OceanContext &context, OceanParams const &params, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("refresh_ocean_ripple_swell: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_refresh_ripple_swell(context.hip, &cascade, 1, &set, iterations), "datum_ocean_refresh_ripple_swell");
+}
+
+void read_ocean_ripple_swell(OceanContext &context, float *plane)
+{
+  if (!context.ready)
+    throw runtime_error("read_ocean_ripple_swell: the context is not prepared (prepare_ocean_context)");
+
+  check(context.hip, datum_ocean_read_ripple_swell(context.hip, plane), "datum_ocean_read_ripple_swell");
+}
+
 void center_ocean_ripples(OceanContext &context, Vec2 const &centre)
 {
   if (!context.ready)

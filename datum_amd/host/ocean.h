@@ -591,6 +591,15 @@ typedef datum_ocean_ripple_bed OceanRippleBed;
 void set_ocean_ripple_bed(OceanContext &context, OceanRippleBed const *bed, float const *depths);
 void read_ocean_ripple_bed(OceanContext &context, float *depth /* [R][R] */, unsigned char *surf /* [R][R] */);
 
+// ripple swell (include/datum_ocean_hip.h: "ripple swell", the definition there): the FFT swell reflects off the walls and the beach --
+// the layer carries the reflection, the shadow and the diffraction.  WAVE mode only.  Per frame, after the displacement and
+// center_ocean_ripples and before step_ocean_ripples or step_ocean_bodies_coupled, refresh_ocean_ripple_swell writes the forcing plane
+// from cascade 0's surface (one launch, enqueued); a step reads it only while it is current.  The read returns the plane in MEMORY
+// order.  All three throw before prepare_ocean_context and while the layer is off; the last two while swell is off
+void set_ocean_ripple_swell(OceanContext &context, bool on);
+void refresh_ocean_ripple_swell(OceanContext &context, OceanParams const &params, int iterations = 4);
+void read_ocean_ripple_swell(OceanContext &context, float *plane /* [R][R] */);
+
 // blocking read-backs for tools and tests
 void read_ocean_displacement(OceanContext &context, float *maps /* [2][N][N][4] */);
 void read_ocean_vertices(OceanContext &context, Ocean const *ocean, Mesh::Vertex *vertices);

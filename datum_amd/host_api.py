@@ -121,6 +121,9 @@ def load():
             "datum_host_read_ocean_ripple_walls": (I, [P, P]),
             "datum_host_set_ocean_ripple_bed": (I, [P, P, P]),
             "datum_host_read_ocean_ripple_bed": (I, [P, P, P]),
+            "datum_host_set_ocean_ripple_swell": (I, [P, I]),
+            "datum_host_refresh_ocean_ripple_swell": (I, [P, P, I]),
+            "datum_host_read_ocean_ripple_swell": (I, [P, P]),
             "datum_host_center_ocean_ripples": (I, [P, F, F]),
             "datum_host_deposit_ocean_ripples": (I, [P, P, ctypes.c_size_t]),
             "datum_host_deposit_ocean_body_ripples": (I, [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, P, I]),
@@ -451,6 +454,20 @@ class OceanContext:
         depth, surf = np.empty((R, R), np.float32), np.empty((R, R), np.uint8)
         self._check(self.lib.datum_host_read_ocean_ripple_bed(self.c, depth.ctypes.data_as(P), surf.ctypes.data_as(P)))
         return depth, surf
+
+    def set_ocean_ripple_swell(self, on=True):
+        """set_ocean_ripple_swell: the FFT swell reflects off the walls and the beach; WAVE mode only"""
+        self._check(self.lib.datum_host_set_ocean_ripple_swell(self.c, int(bool(on))))
+
+    def refresh_ocean_ripple_swell(self, params, iterations=4):
+        """refresh_ocean_ripple_swell: the forcing plane from cascade 0's surface, the solid cells and the origin; marks it current"""
+        self._check(self.lib.datum_host_refresh_ocean_ripple_swell(self.c, params.p, iterations))
+
+    def read_ocean_ripple_swell(self, R):
+        """read_ocean_ripple_swell: the (R, R) float32 forcing plane in MEMORY order"""
+        out = np.empty((R, R), np.float32)
+        self._check(self.lib.datum_host_read_ocean_ripple_swell(self.c, out.ctypes.data_as(P)))
+        return out
 
     def center_ocean_ripples(self, x, y):
         """center_ocean_ripples: the window's middle becomes the cell of (x, y); entered cells are zeroed"""

@@ -67,7 +67,8 @@ extern "C" {
  *      datum_ocean_set_ripple_dispersion and datum_ocean_ripple_deep_weights; then ripple walls, datum_ocean_set_ripple_walls,
  *      datum_ocean_ripple_walls_device and datum_ocean_read_ripple_walls; then the ripple bed, datum_ocean_set_ripple_bed,
  *      datum_ocean_ripple_bed_device and datum_ocean_read_ripple_bed; then the phase's store, datum_ocean_set_phase_store and
- *      datum_ocean_phase_store.
+ *      datum_ocean_phase_store; then ripple swell, datum_ocean_set_ripple_swell, datum_ocean_refresh_ripple_swell,
+ *      datum_ocean_ripple_swell_device and datum_ocean_read_ripple_swell.
  *      A consumer that needs them detects them by symbol (dlsym), not by the version */
 #define DATUM_OCEAN_ABI_VERSION 9
 int datum_ocean_abi_version(void);
@@ -1314,7 +1315,9 @@ int datum_ocean_read_ripple_walls(datum_ocean_t ctx, unsigned char *host);
  *                          either may be null; blocking.  DATUM_OCEAN_ESTATE while the bed is off.
  * LEFT OUT: the bed in DEEP, as tanh(k·d) weights; wetting and drying, run-up and non-linear steepening (the shoreline is fixed at
  * dry_depth); foam from the surf zone; bounds and wake foam treating solid cells as anything but water at rest; the FFT swell feeling the
- * bed; writing only the entered cells on a scroll; temporal blocking. */
+ * bed; writing only the entered cells on a scroll; temporal blocking.
+ * ("The FFT swell feeling the bed" is struck in part: the swell's source on a beach fades with the depth ("ripple swell", below); H
+ * itself still does not shoal.) */
 #define DATUM_OCEAN_RIPPLE_SURF_LEVELS 16
 #define DATUM_OCEAN_RIPPLE_BED_MAX_SIDE 4096
 typedef struct datum_ocean_ripple_bed
@@ -1331,6 +1334,70 @@ typedef struct datum_ocean_ripple_bed
 int datum_ocean_set_ripple_bed(datum_ocean_t ctx, datum_ocean_ripple_bed const *bed, float const *depths_host);
 int datum_ocean_ripple_bed_device(datum_ocean_t ctx, void **depth, void **surf, size_t *cells);
 int datum_ocean_read_ripple_bed(datum_ocean_t ctx, float *depth, unsigned char *surf);
+
+/* -- ripple swell (added at ABI 9; nothing in the reference) ------------------------------------------------------------------------------------
+ * The FFT swell reflects off ripple walls and the beach.  The renderer adds the summed surface H to the layer's η, and H passes through
+ * every pier as if it were not there.  With swell on, the layer carries the SCATTERED FIELD: the difference between the open-sea swell
+ * and the water that is really there.  No flux of the total H + η may pass through a solid face, so every solid face is a source for η
+ * of strength minus the incident flux through it: in front of a wall that radiates the reflection, behind it −H, which is the shadow,
+ * round its end the diffraction.  OPT-IN: while swell is off nothing is allocated, the parents' kernels are launched, and every call
+ * keeps its bits.  Every reader of the layer (mesh, query, ray cast, bounds, wake foam, coupled bodies) only reads the state, so swell
+ * in the step serves all of them; the renderer changes nothing.  SEEN IN FLOAT64 (tests/test_ripple_swell64.py), with a
+ * refresh before every sub-step and no damping: the mirrored wave before a straight wall to 8 % of the amplitude at 16 cells a
+ * wavelength, first order in the cell side; no flux of H + η through the wall's faces; rms(H + η) 0.59 of rms(H) close behind a
+ * breakwater four wavelengths wide.  Not seen: either under a refresh every few sub-steps, or under the layer's damping γ, which acts on
+ * η and not on H.
+ *
+ * THE FORCING PLANE.  F, R × R floats on the layer's torus, world cell (I, J) at the state's place (J mod R)·R + (I mod R).  A cell is
+ * SOLID by its wall byte while the bed is off (no walls: nothing is solid), by d == +0 while the bed is on (that holds the walls).  A
+ * neighbour n of world cell (I, J) COUNTS when it lies inside the window and is solid; a neighbour outside the window never counts, the
+ * flag of the torus-aliased cell is not consulted.  Every operator one fp32 operation as written, no contraction:
+ *     dX = (neighbour X counts) ? (Hc − Hn) : +0.0f                       X = L, R, D, U
+ *     F  = (dL + dR) + (dD + dU)        for a cell that is itself not solid
+ *     F  = +0.0f                        for a solid cell, and (the sum of four +0) for a cell none of whose neighbours count
+ * Hc and Hn are the height of the summed surface above the centres of the cell and of that neighbour, centres at
+ * x = ((float)I + 0.5f) · s, y = ((float)J + 0.5f) · s as the wall raster has them: FIELD 2 OF datum_ocean_sample_surface_blend's record at
+ * that point, bit for bit, for the call's cascade list, set and iterations.
+ *
+ * THE SUB-STEP WITH SWELL.  The WAVE mode.  F is the cell's own value, read once, no halo.  Everything else is the parent's sub-step.
+ *   - without a bed, the sub-step with walls as it stands (without walls nothing is solid, F is +0 and the plain sub-step runs), with
+ *         lap = (((eL + eR) + (eD + eU)) − 4.0f·e) + F
+ *     in place of the wave step's lap; a wall cell's new state is (+0.0f, +0.0f);
+ *   - over a bed, the bed's sub-step as it stands, with
+ *         div = ((tL + tR) + (tD + tU)) + dc·F
+ *     THE FACE AT A SOLID NEIGHBOUR CARRIES THE CELL'S OWN DEPTH, the rule the bed has for the window's edge: on a beach the source
+ *     fades with the depth.
+ * F IS FROZEN OVER THE SUB-STEPS OF A CALL; the swell moves between calls, when the caller refreshes.  No new stability refusal: F is a
+ * source term, the operator is the parent's.
+ *
+ * CURRENCY.  F is a function of the maps, the list and set, the solid cells and the origin.  datum_ocean_refresh_ripple_swell is its only
+ * writer and sets a CURRENT mark on the handle.  The mark is cleared by datum_ocean_center_ripples when the origin moves, by
+ * datum_ocean_set_ripple_walls, datum_ocean_set_ripple_bed, datum_ocean_set_ripples and datum_ocean_set_ripple_swell.  WHILE THE MARK IS
+ * CLEAR THE PARENTS' KERNELS ARE LAUNCHED: a stale F is never read.  The handle cannot see the maps change: a caller that displaces or
+ * scrolls every frame refreshes every frame, in the order displace -> center_ripples -> refresh_ripple_swell -> step_ripples or
+ * step_bodies_coupled.  datum_ocean_reset_ripples keeps the plane and the mark; datum_ocean_set_ripples drops both with the layer.
+ *
+ * DEEP.  Swell and the DEEP mode DO NOT COMBINE (iWave's obstruction is a mask, not a face flux): datum_ocean_set_ripple_swell(1) while
+ * the mode is DATUM_OCEAN_RIPPLE_DEEP, and datum_ocean_set_ripple_dispersion(DATUM_OCEAN_RIPPLE_DEEP, ...) while swell is on, return
+ * DATUM_OCEAN_ESTATE, as the bed's pair does.
+ *
+ *   set_ripple_swell       on = 1 allocates the plane, +0.0f everywhere, between two 256-byte guards of 0xCD, the mark clear (an `on`
+ *                          while swell is on starts again from that); on = 0 frees it.  Blocking.  DATUM_OCEAN_EINVAL: a null handle, `on`
+ *                          outside {0, 1}.  DATUM_OCEAN_ESTATE while the layer is off or its mode is DEEP (with on = 1).
+ *   refresh_ripple_swell   ONE launch on the handle's stream writes F WHOLE and sets the mark; nothing else is written.  The list, the set
+ *                          and `iterations` are datum_ocean_sample_surface_blend's and are checked as that call checks them.
+ *                          DATUM_OCEAN_ESTATE while the layer or swell is off.
+ *   ripple_swell_device    *plane = the device plane in memory order, *bytes = R·R·4, *current = the mark; null, 0 and 0 while swell is
+ *                          off.  Any of the three may be null.  Stable until the next set_ripple_swell or set_ripples.
+ *   read_ripple_swell      the plane to the HOST IN MEMORY ORDER, R·R floats, [(J mod R)][(I mod R)]; blocking, as
+ *                          datum_ocean_read_ripple_walls.  DATUM_OCEAN_ESTATE while the layer or swell is off.
+ * LEFT OUT: swell in DEEP; H itself shoaling or breaking over the bed (only the source at a solid face knows the depth); a swell that
+ * changes within a call's sub-steps; the layer's rate in datum_ocean_sample_velocity_blend; walls in the bilinear sample's patch (the
+ * mesh blends a wall cell's zero with the water beside it, so H + η does not vanish inside a wall). */
+int datum_ocean_set_ripple_swell(datum_ocean_t ctx, int on);
+int datum_ocean_refresh_ripple_swell(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations);
+int datum_ocean_ripple_swell_device(datum_ocean_t ctx, void **plane, size_t *bytes, int *current);
+int datum_ocean_read_ripple_swell(datum_ocean_t ctx, float *plane);
 
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what

@@ -243,7 +243,9 @@ struct datum_ocean_ctx
   GuardedPlane<float2> ripplestate[2];   // the two state buffers: R x R cells of (height, rate) on the layer's torus
   int ripplecurrent = 0;              // the state buffer the next sub-step reads
   int *ripplesrc = nullptr;           // pending deposits
-  double ripplec = 2.0, ripplegamma = 0.05, ripplespongegamma = 4.0;   // datum_ocean_set_ripple_params
+  // datum_ocean_set_ripple_params; the defaults are the fp32 values that call would store (0.05 is no float: as the double 0.05 the
+  // default sponge table was one no call could set again, an ulp off set_ripple_params(2, 0.05f, 8, 4)'s in some entries)
+  double ripplec = 2.0, ripplegamma = (double)0.05f, ripplespongegamma = 4.0;
   int ripplesponge = 8;
   int rippledispersion = DATUM_OCEAN_RIPPLE_WAVE;   // datum_ocean_set_ripple_dispersion: the step's mode, and g of the DEEP one (9.81 as a float)
   double rippleg = (double)9.81f;

@@ -817,7 +817,7 @@ int datum_ocean_step_bodies_host(datum_ocean_t ctx, int const *cascades, int cou
  * in double and rounded once; B = sponge_cells <= DATUM_OCEAN_RIPPLE_MAX_SPONGE, and with B = 0 there is no sponge and f[0] serves every cell.
  * dt = 0 is legal (the pending deposits become heights and nothing else moves); dt < 0 or not finite is DATUM_OCEAN_EINVAL: the damping would
  * grow.  After the first sub-step src is zero again.  The scheme is stable for c·h/s <= 1/√2; the call refuses c·h/s > 0.7 (that bound with a
- * margin) with DATUM_OCEAN_EINVAL, computed in double from c, s, dt and substeps.  Defaults: c = 2 m/s, γ = 0.05 1/s, B = 8, γe = 4 1/s.
+ * margin) with DATUM_OCEAN_EINVAL, computed in double from c, s, dt and substeps.  Defaults: c = 2 m/s, γ = 0.05 1/s (as a float, like every value datum_ocean_set_ripple_params stores), B = 8, γe = 4 1/s.
  *
  * DEPOSITS are integers, so that a plane repeats bit for bit whatever the order of the atomics.  For a volume V m³ at (x, y):
  *     Q   = rint((V · (invs·invs)) · 2^20) clamped to ±2^30        rint to nearest, ties to even; Q = 0 deposits nothing

@@ -166,6 +166,8 @@ SYMBOLS = {
     "datum_ocean_query_ripples": (I, [P, P, ctypes.c_size_t, P]),
     "datum_ocean_step_bodies_coupled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
     "datum_ocean_step_bodies_coupled_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P]),
+    "datum_ocean_step_bodies_contact": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, P]),
+    "datum_ocean_step_bodies_contact_host": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, P]),
     "datum_ocean_gen_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, I, P]),
     "datum_ocean_sample_surface_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
     "datum_ocean_read_surface_blend_rippled": (I, [P, ctypes.POINTER(I), I, ctypes.POINTER(OceanSet), I, P, ctypes.c_size_t, P]),
@@ -243,6 +245,16 @@ RIPPLE_MAX_SPONGE = 64
 
 # coupled stepping (datum_ocean_step_bodies_coupled, added at ABI 9): floats per body record
 COUPLED_RECORD_FLOATS = 12
+# body contact (datum_ocean_step_bodies_contact, added at ABI 9): floats per body record, the flags, the 32-byte parameters
+CONTACT_RECORD_FLOATS = 16
+CONTACT_BED, CONTACT_WALLS = 1, 2
+
+
+class BodyContact(ctypes.Structure):
+    _fields_ = [("stiffness", F), ("damping", F), ("friction", F), ("flags", ctypes.c_uint), ("reserved", F * 4)]
+
+
+assert ctypes.sizeof(BodyContact) == 32
 
 # body buoyancy (datum_ocean_reduce_bodies, added at ABI 9): floats per body record and per probe
 BODY_RECORD_FLOATS = 8
@@ -1032,6 +1044,24 @@ class Ocean:
         arr, n = self._list(cascades)
         args, out = _body_batch(bodies, motions, props, probes, COUPLED_RECORD_FLOATS, in_place=True)
         self._check(self.lib.datum_ocean_step_bodies_coupled_host(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, dt, substeps, _ptr(out)))
+        return out
+
+    # -- body contact (datum_ocean_step_bodies_contact): the coupled step with hulls that stop at ripple walls and ground on the bed -----
+
+    def step_bodies_contact(self, cascades, oceanset, bodies_ptr, motions_ptr, props_ptr, nbodies, probes_ptr, nprobes, dt, substeps, records_ptr, contact, iterations=4):
+        """step_bodies_coupled with penalty contact: `contact` a BodyContact (stiffness, damping, friction per unit probe weight, flags
+        CONTACT_BED | CONTACT_WALLS); records of 16 floats per body: the coupled record's twelve, the contact force of the last sub-step,
+        the deepest penetration of all sub-steps.  A flag needs its object set (set_ripple_bed, set_ripple_walls)."""
+        arr, n = self._list(cascades)
+        self._check(self.lib.datum_ocean_step_bodies_contact(self.h, arr, n, ctypes.byref(oceanset), iterations, _dev(bodies_ptr), _dev(motions_ptr), _dev(props_ptr),
+                                                             nbodies, _dev(probes_ptr), nprobes, dt, substeps, _dev(records_ptr), ctypes.cast(ctypes.byref(contact), P)))
+
+    def step_bodies_contact_host(self, cascades, oceanset, bodies, motions, props, probes, dt, contact, substeps=1, iterations=4):
+        """the same from host arrays, blocking: `bodies` and `motions` advanced IN PLACE; returns the (nbodies, 16) records"""
+        arr, n = self._list(cascades)
+        args, out = _body_batch(bodies, motions, props, probes, CONTACT_RECORD_FLOATS, in_place=True)
+        self._check(self.lib.datum_ocean_step_bodies_contact_host(self.h, arr, n, ctypes.byref(oceanset), iterations, *args, dt, substeps, _ptr(out),
+                                                                  ctypes.cast(ctypes.byref(contact), P)))
         return out
 
     # -- rippled reads (datum_ocean_gen_blend_rippled): the mesh, the query and the cast with the ripple layer's height and slopes on top -----

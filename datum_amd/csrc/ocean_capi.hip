@@ -34,6 +34,7 @@
 #include "ocean_ripple.hip"
 #include "ocean_ripple_deep.hip"
 #include "ocean_couple.hip"
+#include "ocean_contact.hip"
 #include "ocean_rippled.hip"
 #include "ocean_ripple_bounds.hip"
 #include "ocean_ripple_foam.hip"
@@ -3444,6 +3445,23 @@ namespace
     }
   }
 
+  // the bed as the arithmetic sees it (ocean_ripple_bed.h: RippleBed), for the raster and for body contact
+  RippleBed ripple_bed_terms(datum_ocean_ripple_bed const &p)
+  {
+    RippleBed b;
+    b.width = p.width;
+    b.height = p.height;
+    b.ox = p.origin[0];
+    b.oy = p.origin[1];
+    b.invt = (float)(1.0 / (double)p.texel);
+    b.outside = p.outside;
+    b.max_depth = p.max_depth;
+    b.dry_depth = p.dry_depth;
+    b.surf_depth = p.surf_depth;
+    b.invsurf = p.surf_depth > 0.0f ? (float)(1.0 / (double)p.surf_depth) : 0.0f;
+    return b;
+  }
+
   // both planes whole from the handle's map, its parameters and the wall plane at g's origin, on the handle's stream (behind the wall
   // raster, where there is one); with `zero` the solid cells' state in both buffers too
   int raster_ripple_bed(datum_ocean_ctx *ctx, RippleGrid const &g, bool zero)
@@ -3460,16 +3478,7 @@ namespace
     a.wall = ctx->ripplewall.get();
     fill_ripple_raster(ctx, g, zero, a);
 
-    a.b.width = p.width;
-    a.b.height = p.height;
-    a.b.ox = p.origin[0];
-    a.b.oy = p.origin[1];
-    a.b.invt = (float)(1.0 / (double)p.texel);
-    a.b.outside = p.outside;
-    a.b.max_depth = p.max_depth;
-    a.b.dry_depth = p.dry_depth;
-    a.b.surf_depth = p.surf_depth;
-    a.b.invsurf = p.surf_depth > 0.0f ? (float)(1.0 / (double)p.surf_depth) : 0.0f;
+    a.b = ripple_bed_terms(p);
 
     HIPCHECK(ctx, launch_ripple_bed_raster(a, ctx->stream));
 
@@ -4445,12 +4454,17 @@ namespace
     return check_ripple_stability(ctx, substep_length(dt, substeps), name, ": c * dt / (substeps * s) above 0.7, the ripple step's stability bound with a margin");
   }
 
-  // device arrays; `substeps` rounds of: the bodies' coupled sub-step (nbodies > 0), then the layer's sub-step in its first form
-  int run_step_bodies_coupled(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, int substeps)
+  // device arrays; `substeps` rounds of: the bodies' coupled sub-step (nbodies > 0), then the layer's sub-step in its first form.  With
+  // `scene` (body contact's share of the arguments, filled in by its caller) the bodies' sub-step is body contact's kernel, everything
+  // else the same
+  int run_step_bodies_coupled(datum_ocean_ctx *ctx, Query const &q, BodyBatch const &b, float dt, int substeps, ContactArgs *scene = nullptr)
   {
     float const h = substep_length(dt, substeps);
 
-    CoupleArgs a = {};
+    ContactArgs plain = {};
+    ContactArgs &ca = scene ? *scene : plain;
+
+    CoupleArgs &a = ca.c;
     fill_drag_args(ctx, q, b, a.d);
     a.bodies = const_cast<datum_ocean_body*>(a.d.b.bodies);             // (writable, as the step's)
     a.motions = const_cast<datum_ocean_body_motion*>(a.d.motions);
@@ -4470,7 +4484,7 @@ namespace
         a.state = ctx->ripplestate[ctx->ripplecurrent].get();
         a.first = i == 0;
 
-        HIPCHECK(ctx, launch_couple(a, ctx->stream));
+        HIPCHECK(ctx, scene ? launch_contact(ca, ctx->stream) : launch_couple(a, ctx->stream));
       }
 
       // datum_ocean_step_ripples(h, 1): the first form takes the deposits in, and no kernel clears src
@@ -4525,6 +4539,102 @@ int datum_ocean_step_bodies_coupled_host(datum_ocean_t ctx, int const *cascades,
     rc = run_step_bodies_coupled(ctx, q, dev, dt, substeps);
 
   return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_COUPLED_RECORD_FLOATS, true);
+}
+
+}   // extern "C"
+
+/* -- body contact (ocean_contact.hip): the coupled call's checks and loop, and the contact's own ---------------------------------------- */
+
+namespace
+{
+  // behind check_coupled_args: the parameters, then the objects the flags ask for
+  int check_contact_args(datum_ocean_ctx *ctx, datum_ocean_body_contact const *c, char const *name)
+  {
+    if (!c)
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": null contact");
+
+    for(float v : { c->stiffness, c->damping, c->friction })
+      if (!std::isfinite(v) || v < 0.0f)
+        return fail(ctx, DATUM_OCEAN_EINVAL, name, ": stiffness, damping and friction must be finite and not negative");
+
+    if (c->flags & ~CONTACT_FLAGS)
+      return fail(ctx, DATUM_OCEAN_EINVAL, name, ": unknown flag bits");
+
+    if ((c->flags & DATUM_OCEAN_CONTACT_BED) && !ctx->ripplebedmap)
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": DATUM_OCEAN_CONTACT_BED and no bed is set (datum_ocean_set_ripple_bed)");
+
+    if ((c->flags & DATUM_OCEAN_CONTACT_WALLS) && !ctx->ripplewalllist)
+      return fail(ctx, DATUM_OCEAN_ESTATE, name, ": DATUM_OCEAN_CONTACT_WALLS and no walls are set (datum_ocean_set_ripple_walls)");
+
+    return DATUM_OCEAN_OK;
+  }
+
+  // body contact's share of the kernel's arguments: the parameters, and the map and the list only where their flag is set
+  ContactArgs contact_scene(datum_ocean_ctx const *ctx, datum_ocean_body_contact const &c)
+  {
+    ContactArgs ca = {};
+    ca.s.k = c;
+
+    if (c.flags & DATUM_OCEAN_CONTACT_BED)
+    {
+      ca.s.bed = ripple_bed_terms(ctx->ripplebedparams);
+      ca.map = ctx->ripplebedmap;
+    }
+
+    if (c.flags & DATUM_OCEAN_CONTACT_WALLS)
+    {
+      ca.s.walls = ctx->ripplewalllist;
+      ca.s.nwalls = ctx->ripplewallcount;
+    }
+
+    return ca;
+  }
+}
+
+extern "C"
+{
+
+int datum_ocean_step_bodies_contact(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                    void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                    float dt, int substeps, void *records_device, datum_ocean_body_contact const *contact)
+{
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const b = { bodies_device, motions_device, props_device, nbodies, probes_device, nprobes, records_device };
+
+  int rc = check_coupled_args(ctx, q, b, dt, substeps, "datum_ocean_step_bodies_contact");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_contact_args(ctx, contact, "datum_ocean_step_bodies_contact");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+
+  ContactArgs scene = contact_scene(ctx, *contact);
+
+  return run_step_bodies_coupled(ctx, q, b, dt, substeps, &scene);
+}
+
+int datum_ocean_step_bodies_contact_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                         datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
+                                         float const *probes, size_t nprobes, float dt, int substeps, float *records, datum_ocean_body_contact const *contact)
+{
+  Query const q = { cascades, count, set, iterations };
+  BodyBatch const host = { bodies, motions, props, nbodies, probes, nprobes, records };
+  BodyBatch dev;
+
+  int rc = check_coupled_args(ctx, q, host, dt, substeps, "datum_ocean_step_bodies_contact_host");
+  if (rc == DATUM_OCEAN_OK)
+    rc = check_contact_args(ctx, contact, "datum_ocean_step_bodies_contact_host");
+  if (rc != DATUM_OCEAN_OK)
+    return rc;
+
+  ContactArgs scene = contact_scene(ctx, *contact);
+
+  rc = stage_batch(ctx, host, DATUM_OCEAN_CONTACT_RECORD_FLOATS, dev);
+  if (rc == DATUM_OCEAN_OK)
+    rc = run_step_bodies_coupled(ctx, q, dev, dt, substeps, &scene);
+
+  return rc != DATUM_OCEAN_OK ? rc : fetch_batch(ctx, host, dev, DATUM_OCEAN_CONTACT_RECORD_FLOATS, true);
 }
 
 }   // extern "C"
@@ -5419,8 +5529,18 @@ int datum_ocean_set_ripple_walls(datum_ocean_t ctx, datum_ocean_ripple_wall cons
   if (e == hipSuccess)
     e = hipMalloc(&ctx->ripplewalllist, (size_t)count * sizeof(datum_ocean_ripple_wall));
   // (the caller's array may go away behind the call: the copy is waited for)
+  // (the copy's `reserved` holds inv2 for body contact, ocean_contact.h; the raster does not read the field.  8 KiB at the most, on
+  // the stack: nothing here can throw)
+  datum_ocean_ripple_wall list[DATUM_OCEAN_RIPPLE_MAX_WALLS];
+
+  for(int k = 0; k < count; ++k)
+  {
+    list[k] = walls[k];
+    contact_wall_prepare(list[k]);
+  }
+
   if (e == hipSuccess)
-    e = hipMemcpyAsync(ctx->ripplewalllist, walls, (size_t)count * sizeof(datum_ocean_ripple_wall), hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpyAsync(ctx->ripplewalllist, list, (size_t)count * sizeof(datum_ocean_ripple_wall), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess)
     e = hipStreamSynchronize(ctx->stream);
 

@@ -29,15 +29,29 @@ namespace ocean
     float surf_depth, invsurf;
   };
 
-  // the raw depth at (x, y): `outside` off the map (a NaN coordinate is off the map), else the bilinear patch of the four texels round the
-  // point in ripple_sample's form, the lower index floor, clamped so that the upper one is a texel.  texel(index) returns map[index]
+  // the bilinear patch at (x, y): `outside` and no slope off the map (a NaN coordinate is off the map), else the patch of the four texels
+  // round the point in ripple_sample's form, the lower index floor, clamped so that the upper one is a texel, and its two slopes per
+  // metre, ripple_sample's again.  texel(index) returns map[index]
+  struct RippleBedPatch
+  {
+    float raw, gx, gy;
+    bool inside;
+  };
+
   template<class Texel>
-  OB_HD float ripple_bed_raw(RippleBed const &b, float x, float y, Texel &&texel)
+  OB_HD RippleBedPatch ripple_bed_patch(RippleBed const &b, float x, float y, Texel &&texel)
   {
     float const u = (x - b.ox) * b.invt, v = (y - b.oy) * b.invt;
 
+    RippleBedPatch p;
+
     if (!(u >= 0.0f && u <= (float)(b.width - 1) && v >= 0.0f && v <= (float)(b.height - 1)))
-      return b.outside;
+    {
+      p.raw = b.outside;
+      p.gx = p.gy = 0.0f;
+      p.inside = false;
+      return p;
+    }
 
     int const fi = (int)floorf(u), fj = (int)floorf(v);
     int const i = fi < b.width - 2 ? fi : b.width - 2, j = fj < b.height - 2 ? fj : b.height - 2;
@@ -50,7 +64,18 @@ namespace ocean
     float const a0 = c1 - c0, a1 = c3 - c2;
     float const e0 = c0 + wu * a0, e1 = c2 + wu * a1;
 
-    return e0 + wv * (e1 - e0);
+    p.raw = e0 + wv * (e1 - e0);
+    p.gx = (a0 + wv * (a1 - a0)) * b.invt;
+    p.gy = (e1 - e0) * b.invt;
+    p.inside = true;
+    return p;
+  }
+
+  // the raw depth at (x, y): the patch's value (the slopes are not formed where nothing reads them)
+  template<class Texel>
+  OB_HD float ripple_bed_raw(RippleBed const &b, float x, float y, Texel &&texel)
+  {
+    return ripple_bed_patch(b, x, y, texel).raw;
   }
 
   // the effective depth: the raw one clamped to [0, max_depth]; +0 -- solid -- below dry_depth and where a wall stands

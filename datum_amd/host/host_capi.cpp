@@ -558,6 +558,16 @@ extern "C"
     catch(std::exception const &e) { return caught(e); }
   }
 
+  int datum_host_step_ocean_bodies_contact(void *c, void *p, void *bodies, void *motions, void const *props, size_t nbodies, float const *probes, size_t nprobes, float dt, int substeps, float *records, void const *contact, int iterations)
+  {
+    try
+    {
+      step_ocean_bodies_contact(static_cast<HostContext*>(c)->context, *static_cast<OceanParams*>(p), static_cast<datum_ocean_body*>(bodies), static_cast<datum_ocean_body_motion*>(motions), static_cast<datum_ocean_body_props const*>(props), nbodies, reinterpret_cast<OceanBodyProbe const*>(probes), nprobes, dt, substeps, reinterpret_cast<OceanContactRecord*>(records), *static_cast<datum_ocean_body_contact const*>(contact), iterations);
+      return 0;
+    }
+    catch(std::exception const &e) { return caught(e); }
+  }
+
   int datum_host_cast_ocean_rays(void *c, void *p, float const *rays, size_t n, float *records, int iterations, int steps, int refine)
   {
     return cast_rays(cast_ocean_rays, c, p, rays, n, records, iterations, steps, refine);

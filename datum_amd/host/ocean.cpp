@@ -1124,6 +1124,20 @@ void step_ocean_bodies_coupled(OceanContext &context, OceanParams const &params,
 }
 
 
+///////////////////////// step_ocean_bodies_contact /////////////////////////
+void step_ocean_bodies_contact(OceanContext &context, OceanParams const &params, datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies, OceanBodyProbe const *probes, size_t nprobes, float dt, int substeps, OceanContactRecord *records, datum_ocean_body_contact const &contact, int iterations)
+{
+  if (!context.ready)
+    throw runtime_error("step_ocean_bodies_contact: the context is not prepared (prepare_ocean_context)");
+
+  datum_ocean_set set = make_oceanset(Camera(), params);
+
+  int const cascade = 0;
+
+  check(context.hip, datum_ocean_step_bodies_contact_host(context.hip, &cascade, 1, &set, iterations, bodies, motions, props, nbodies, reinterpret_cast<float const*>(probes), nprobes, dt, substeps, reinterpret_cast<float*>(records), &contact), "datum_ocean_step_bodies_contact_host");
+}
+
+
 ///////////////////////// cast_ocean_rays ///////////////////////////////////
 void cast_ocean_rays(OceanContext &context, OceanParams const &params, OceanRay const *rays, size_t n, OceanRayRecord *records, int iterations, int steps, int refine)
 {

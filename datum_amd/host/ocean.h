@@ -483,6 +483,20 @@ static_assert(sizeof(OceanCoupledRecord) == 48, "OceanCoupledRecord must be the 
 
 void step_ocean_bodies_coupled(OceanContext &context, OceanParams const &params, datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, float dt, int substeps, OceanCoupledRecord *records, int iterations = 4);
 
+// body contact (include/datum_ocean_hip.h: datum_ocean_step_bodies_contact_host, the definition there): step_ocean_bodies_coupled's
+// arguments and the contact parameters; hulls stop at the ripple walls and ground on the ripple bed by a penalty force per probe.  Throws
+// where step_ocean_bodies_coupled does, for parameters that are negative or not finite, and for a flag whose bed or walls are not set
+struct OceanContactRecord
+{
+  OceanCoupledRecord coupled;             // force and torque are the totals, the contact's share included
+  lml::Vec3 contact;                      // the contact force of the last sub-step
+  float deepest;                          // the deepest penetration over all sub-steps, metres
+};
+
+static_assert(sizeof(OceanContactRecord) == 64, "OceanContactRecord must be the C ABI's record of DATUM_OCEAN_CONTACT_RECORD_FLOATS floats");
+
+void step_ocean_bodies_contact(OceanContext &context, OceanParams const &params, datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, std::size_t nbodies, OceanBodyProbe const *probes, std::size_t nprobes, float dt, int substeps, OceanContactRecord *records, datum_ocean_body_contact const &contact, int iterations = 4);
+
 // ray casts (include/datum_ocean_hip.h: datum_ocean_read_rays, the definition there): per ray a fixed march of `steps` samples to the first
 // change of side, `refine` bisections of that bracket, and the surface sample at the bracket's far end.  One cascade, as
 // query_ocean_surface; the maps the context last displaced, swell and plane from `params`.  Host arrays, blocking.  Throws before

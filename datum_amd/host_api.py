@@ -130,6 +130,7 @@ def load():
             "datum_host_step_ocean_ripples": (I, [P, F, I]),
             "datum_host_query_ocean_ripples": (I, [P, P, ctypes.c_size_t, P]),
             "datum_host_step_ocean_bodies_coupled": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, I]),
+            "datum_host_step_ocean_bodies_contact": (I, [P, P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, F, I, P, P, I]),
             "datum_host_cast_ocean_rays": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
             "datum_host_query_ocean_surface_rippled": (I, [P, P, P, ctypes.c_size_t, P, I]),
             "datum_host_cast_ocean_rays_rippled": (I, [P, P, P, ctypes.c_size_t, P, I, I, I]),
@@ -514,6 +515,22 @@ class OceanContext:
         out = np.empty((bodies.shape[0], capi.COUPLED_RECORD_FLOATS), np.float32)
         self._check(self.lib.datum_host_step_ocean_bodies_coupled(self.c, params.p, bodies.ctypes.data_as(P), motions.ctypes.data_as(P), pp.ctypes.data_as(P), bodies.shape[0],
                                                                   pr.ctypes.data_as(P), pr.shape[0], dt, substeps, out.ctypes.data_as(P), iterations))
+        return out
+
+    def step_ocean_bodies_contact(self, params, bodies, motions, props, probes, dt, contact, substeps=1, iterations=4):
+        """step_ocean_bodies_contact: step_ocean_bodies_coupled's arguments and a capi.BodyContact; hulls stop at the ripple walls and
+        ground on the ripple bed; returns (nbodies, 16) float32 records (OceanContactRecord: the coupled record, the contact force of the
+        last sub-step, the deepest penetration)"""
+        assert isinstance(bodies, np.ndarray) and isinstance(motions, np.ndarray) and bodies.flags.c_contiguous and motions.flags.c_contiguous
+        assert bodies.flags.writeable and motions.flags.writeable
+        pp = np.ascontiguousarray(props)
+        assert bodies.dtype.itemsize == ctypes.sizeof(capi.Body) and motions.dtype.itemsize == ctypes.sizeof(capi.BodyMotion) and pp.dtype.itemsize == ctypes.sizeof(capi.BodyProps)
+        assert motions.shape[0] == bodies.shape[0] == pp.shape[0]
+        pr = np.ascontiguousarray(probes, np.float32).reshape(-1, capi.BODY_PROBE_FLOATS)
+        out = np.empty((bodies.shape[0], capi.CONTACT_RECORD_FLOATS), np.float32)
+        self._check(self.lib.datum_host_step_ocean_bodies_contact(self.c, params.p, bodies.ctypes.data_as(P), motions.ctypes.data_as(P), pp.ctypes.data_as(P), bodies.shape[0],
+                                                                  pr.ctypes.data_as(P), pr.shape[0], dt, substeps, out.ctypes.data_as(P), ctypes.cast(ctypes.byref(contact), P),
+                                                                  iterations))
         return out
 
     def cast_ocean_rays(self, params, rays, iterations=4, steps=32, refine=8):

@@ -1399,6 +1399,92 @@ int datum_ocean_refresh_ripple_swell(datum_ocean_t ctx, int const *cascades, int
 int datum_ocean_ripple_swell_device(datum_ocean_t ctx, void **plane, size_t *bytes, int *current);
 int datum_ocean_read_ripple_swell(datum_ocean_t ctx, float *plane);
 
+/* -- body contact (added at ABI 9; nothing in the reference) ------------------------------------------------------------------------------------
+ * Hulls stop at ripple walls and ground on the bed.  Every wave of the layer knows the walls and the bed; with this call the bodies of
+ * coupled stepping know them too.  datum_ocean_step_bodies_contact is datum_ocean_step_bodies_coupled -- its arguments, its checks, its
+ * host loop, its layer sub-step, its swell handling, its bad-body rules -- with PENALTY CONTACT added to every probe's terms.  OPT-IN per
+ * call: the coupled call and every other call keep their bits, and a contact call in which no probe touches anything gives the coupled
+ * call's poses, motions, record fields 0-11 and layer bit for bit.
+ *
+ * THE PARAMETERS.  datum_ocean_body_contact, 32 bytes, a HOST pointer given to each call (the handle keeps nothing): stiffness k >= 0
+ * (N/m per m² of probe weight), damping c >= 0 (N·s/m per m²), friction ct >= 0 (a VISCOUS tangential rate, N·s/m per m²; not Coulomb) and
+ * flags, DATUM_OCEAN_CONTACT_BED | DATUM_OCEAN_CONTACT_WALLS.  All three are per unit probe weight a, the a body buoyancy's terms take.
+ *
+ * Every operator below is one fp32 operation as written (no contraction), division and sqrt the correctly rounded ones.  w is the probe's
+ * world point, a its weight, T, v, ω the body's position and motion at the START of the sub-step.
+ *
+ * GROUND (flag BED; a bed must be set).  The handle's device copy of the depth map, the bed's invt = (float)(1.0 / texel):
+ *     u = (w.x − origin[0])·invt      v = (w.y − origin[1])·invt
+ *     off the map (u < 0 or u > width − 1 or v < 0 or v > height − 1, a NaN is off):   raw = outside,  n = (0, 0, 1)
+ *     else  i, j, wu, wv, c0..c3, a0, a1, e0, e1 and raw = e0 + wv·(e1 − e0) as the bed's raster rule has them (UNCLAMPED: negative on land)
+ *           gx = (a0 + wv·(a1 − a0))·invt      gy = (e1 − e0)·invt      l = sqrt((gx·gx + gy·gy) + 1·1)      n = (gx / l, gy / l, 1 / l)
+ *     zg = 0 − raw          the ground's elevation: the map is a depth, positive down
+ *     p  = zg − w.z         the penetration; the probe TOUCHES when p > 0
+ *
+ * WALLS (flag WALLS; walls must be set).  Walls are vertical prisms of unbounded height: contact is horizontal, n.z = 0.  For every record
+ * of the list IN LIST ORDER that covers (w.x, w.y) by the raster rule, with that rule's u, v:
+ *     BOX       px = half[0] − |u|      py = half[1] − |v|
+ *               px <= py:  q = px,  m = (u >= 0 ? 1 : −1, 0)          else  q = py,  m = (0, v >= 0 ? 1 : −1)
+ *     ELLIPSE   eu = u / half[0]      ev = v / half[1]      ρ = sqrt(eu·eu + ev·ev)      q = (1 − ρ)·fminf(half[0], half[1])
+ *               ρ == 0:  m = (1, 0)          else  lx = eu / half[0], ly = ev / half[1], l = sqrt(lx·lx + ly·ly), m = (lx / l, ly / l)
+ *     n  = (m.x·axis[0] − m.y·axis[1],  m.x·axis[1] + m.y·axis[0],  0)          the local normal turned by the axis AS GIVEN
+ *     p  = q·inv2          inv2 = (float)(1.0 / (axis[0]² + axis[1]²)), formed in double and rounded once by datum_ocean_set_ripple_walls
+ * The shape touches when p > 0.  THE LIBRARY STILL DOES NOT NORMALISE THE AXIS: with a unit axis n is a unit vector and p a distance; an
+ * axis of length L gives |n| = L and p = q / L², so that the spring term k·p·n is that of the scaled shape exactly while the damping and
+ * friction terms carry a factor L².  A ZERO AXIS, which datum_ocean_set_ripple_walls accepts, covers every point with inv2 = ∞ and n = 0:
+ * under flag WALLS its force is ∞·0, not a number, and EVERY body of the call ends as a bad body -- give walls an axis.  THE TEST IS THE ANALYTIC SHAPE, NOT THE BYTE PLANE: the plane stays what the waves see, and a shape
+ * thinner than a cell can stop a hull without reflecting a wave.
+ *
+ * THE FORCE OF ONE CONTACT that touches, with its p and n:
+ *     r  = w − T  per component                  u = v + ω × r  in body drag's form:  u.x = v.x + (ω.y·r.z − ω.z·r.y)  ...
+ *     vn = (u.x·n.x + u.y·n.y) + u.z·n.z         fn = fmaxf(a·(k·p − c·vn), 0)          the ground never pulls
+ *     g  = a·ct                                  F  = fn·n − g·(u − vn·n)  per component:  F.x = fn·n.x − g·(u.x − vn·n.x)  ...
+ *     τ  = r × F:  τ.x = r.y·F.z − r.z·F.y       τ.y = r.z·F.x − r.x·F.z       τ.z = r.x·F.y − r.y·F.x
+ * A probe's EIGHT contact terms start at +0 and take, one fp32 addition per field, first the ground's contact and then each touching
+ * shape's in list order: F (3), τ (3), the count of touching contacts (+1 each), and the deepest p (fmaxf).  They are summed beside the
+ * coupled call's fourteen in the body tree's order -- twenty-two fields, the tenth and the twenty-second maxima.
+ *
+ * THE INTEGRATOR is datum_ocean_step_bodies' steps 2-5, called and not restated.  A body whose count is 0 advances exactly as in the
+ * coupled call.  Otherwise F, τ are that call's step 2 for the sub-step; F_total = F + F_contact and τ_total = τ + τ_contact, one fp32
+ * addition per component; and steps 2-5 run once more with D = (F_total, τ_total), M = bx = by = 0 and buoyancy 0: step 2 then gives
+ * 0·0 + F_total.z and the like, F_total and τ_total again (a −0 becomes +0), and steps 3-5 advance the body under them.
+ *
+ * Each body gets a record of DATUM_OCEAN_CONTACT_RECORD_FLOATS = 16 floats (64 bytes):
+ *     0-11   the coupled record's fields, by its rules (0-5 are the totals the body advanced under: WITH the contact's share)
+ *     12-14  the contact force F_contact of the LAST sub-step          15   the deepest p over all sub-steps (fmaxf through the record)
+ * A bad body stores sixteen quiet NaNs; every rule of the coupled call's bad bodies holds.
+ *
+ * WHY A PENALTY.  The integrator is semi-implicit Euler, which is symplectic for a spring: a contact spring k·Σa under a mass m is stable
+ * for h·sqrt(k·Σa·invmass) < 2 and conserves a shadow energy below that.  THE BOUND IS NOT CHECKED -- the host never sees the bodies --
+ * and a body that blows up ends as a bad body.  Measured in float64 (tests/test_contact64.py): a box on flat land rests at
+ * p* = gravity / (k·Σa·invmass); with c > 0 its energy never rises; with c = 0 inside the bound it stays bounded.
+ *
+ *   step_bodies_contact        enqueue and return, as step_bodies_coupled.  records_device: nbodies × 64 bytes.
+ *   step_bodies_contact_host   the same from HOST arrays, blocking, through datum_ocean_step_bodies_host's staging.
+ * DATUM_OCEAN_ESTATE and DATUM_OCEAN_EINVAL wherever the coupled call returns them, in its order; then DATUM_OCEAN_EINVAL for a null
+ * contact struct, a rate that is not finite or is negative, and unknown flag bits; then DATUM_OCEAN_ESTATE for flag BED with no bed set
+ * and for flag WALLS with no walls set.  A refused call enqueues nothing and changes nothing.  flags = 0 is legal: the coupled call with
+ * a wider record.
+ * LEFT OUT: Coulomb friction (the tangential force is viscous); contact between bodies; wall tops (a wall has no height: a hull cannot
+ * ride over it); moving walls; contact outside the coupled step (datum_ocean_step_bodies has none); a check of the stability bound. */
+#define DATUM_OCEAN_CONTACT_RECORD_FLOATS 16
+#define DATUM_OCEAN_CONTACT_BED 1u
+#define DATUM_OCEAN_CONTACT_WALLS 2u
+typedef struct datum_ocean_body_contact
+{
+  float stiffness;         /*   0  k >= 0, per unit probe weight                                       */
+  float damping;           /*   4  c >= 0, along the normal                                            */
+  float friction;          /*   8  ct >= 0, viscous, along the tangent                                 */
+  unsigned int flags;      /*  12  DATUM_OCEAN_CONTACT_BED | DATUM_OCEAN_CONTACT_WALLS                 */
+  float reserved[4];       /*  16  not read                                                            */
+} datum_ocean_body_contact;
+int datum_ocean_step_bodies_contact(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                    void *bodies_device, void *motions_device, void const *props_device, size_t nbodies, void const *probes_device, size_t nprobes,
+                                    float dt, int substeps, void *records_device, datum_ocean_body_contact const *contact);
+int datum_ocean_step_bodies_contact_host(datum_ocean_t ctx, int const *cascades, int count, datum_ocean_set const *set, int iterations,
+                                         datum_ocean_body *bodies, datum_ocean_body_motion *motions, datum_ocean_body_props const *props, size_t nbodies,
+                                         float const *probes, size_t nprobes, float dt, int substeps, float *records, datum_ocean_body_contact const *contact);
+
 /* -- the tile farm: N processes, one GPU each, independent tiles / cascades, ONE all-gather per batch ------------------
  * (nothing in the reference, which has one device.)  The displacement step needs no exchange; what
  * north_star's "single RCCL all-gather over xGMI" reassembles is the displacement field of every rank's grids.  These

@@ -1532,11 +1532,12 @@ int datum_ocean_rebuild_height(datum_ocean_t ctx, int cascade, float wavescale, 
   ctx->cstate[cascade].new_height();
   HIPCHECK(ctx, hipGetLastError());
 
-  // a cascade without a state gets one with phase zero -- its foam accumulator is not reset (include/datum_ocean_hip.h).  (Nothing is
-  // retained while a cascade has no state, displace refuses: the flush says so where the phase is replaced.)
+  // a cascade without a state gets one with phase zero -- its foam accumulator is not reset (include/datum_ocean_hip.h).  The phase is
+  // replaced: like upload_state and resume_state the call brings it up to date first, so that the new state takes none of the updates
+  // queued before it (set_cascade above has done so only where the wave scale changed) and the other cascades keep them
   if (!ctx->cstate[cascade].uploaded)
   {
-    rc = flush_retained(ctx);
+    rc = flush_phase(ctx);
     if (rc != DATUM_OCEAN_OK)
       return rc;
 

@@ -27,22 +27,12 @@ import pytest
 
 import ref64
 from pointwise import EPS, pointwise as _pointwise, rms as _rms          # the error forms, shared with the literal mode's tests
+from pointwise import BORDER, FP16_DISP_RMSE, FP16_NORMAL_RMSE, K_BAND, K_EDGE, K_MAP, K_NORMAL, K_ROW, STRUCT   # the bars, and the check of
+from pointwise import check as _check                                    # one cascade: shared with tests/test_gpu_step_sequences.py
 
 pytestmark = pytest.mark.gpu
 
 DT = np.float32(1.0 / 60.0)
-
-# Bars: at least 3x the worst value measured on the MI355X over every case of this file (the measured worst beside each).
-K_MAP = 9.0             # random fields, every form, format and N, end to end (fp32) and column pass: measured 2.89 (512^2 fp32, e2e)
-K_EDGE = 30.0           # single-bin known answers (a pure tone: the twiddles' errors add coherently): measured 9.73 (4096^2)
-K_NORMAL = 6.0          # every case, the single bins included: measured 1.94 (4096^2)
-K_ROW = 24.0            # fp32 row pass: measured 7.63 (4096^2); grows faster than L because a row's small elements carry the sim's error
-K_BAND = 18.0           # fp16 formats, the band around a rounding midpoint: measured 5.59 (4096^2 fp16h0; 1e-4 .. 4e-3 of the halves are not the nearest)
-STRUCT = 7.5            # worst column / row RMS of the normalised error over the median one: measured 2.42 (4096^2 column pass, rows)
-BORDER = 4.0            # RMS of the error on the grid's border ring over the interior's: measured 1.22 (1024^2 column pass)
-FP16_DISP_RMSE = 3.5e-4  # fp16 formats, end to end: displacement RMSE / max |displacement|: measured 1.11e-4 (128^2 fp16h0)
-FP16_NORMAL_RMSE = 2e-3  # fp16 formats, end to end: normal RMSE (absolute): measured 6.17e-4 (4096^2 fp16)
-
 
 @pytest.fixture(scope="module")
 def capi():
@@ -56,123 +46,6 @@ def _state(oracle, N, rngseed, wavescale):
     p = oracle.EXAMPLE
     _, h0 = oracle.seed(N, rngseed, wavescale, p["waveamplitude"], p["windspeed"], p["winddirection"], sanitize=True)
     return h0
-
-
-def _structure(energy):
-    """(worst column / median column, worst row / median row, border ring / interior) of the RMS of the normalised error"""
-    cols = np.sqrt(energy.mean(axis=0))
-    rows = np.sqrt(energy.mean(axis=1))
-    ring = np.concatenate([energy[0], energy[-1], energy[1:-1, 0], energy[1:-1, -1]])
-    inner = float(np.sqrt(energy[1:-1, 1:-1].mean()))
-    return float(cols.max() / np.median(cols)), float(rows.max() / np.median(rows)), float(np.sqrt(ring.mean()) / inner)
-
-
-def _rowpass_fp32(got, want, N):
-    """worst |got - want| per element over eps * L * rms(row)"""
-    g = ref64.as_complex(got)
-    rows = np.sqrt(np.mean(np.abs(want) ** 2, axis=1, keepdims=True))
-    return float((np.abs(g - want) / (EPS * np.log2(N) * np.maximum(rows, 1e-37))).max())
-
-
-def _rowpass_fp16(got, want, N, e):
-    """(halves: every value times 2^e is one, K: the smallest band k * eps * L * rms(row) around the float64 value within which the
-    kernel's fp32 value must lie for its half to be what it is, share of values that are not the half nearest the float64 value).
-    A stored half h is RN(v) of the kernel's fp32 value v; |v - ref| <= band means RN(ref - band) <= h <= RN(ref + band): it is the
-    nearest half unless ref lies within the band of a rounding midpoint (of several, where the band spans more than a half's spacing,
-    as it does for the small values of a row).  Both components of each element are checked on their own."""
-    unit = EPS * np.log2(N) * np.sqrt(np.mean(np.abs(want) ** 2, axis=1, keepdims=True)) * np.ldexp(1.0, e)
-    halves = True
-    need = 0.0
-    off = 0
-    for g, w in ((got[..., 0], want.real), (got[..., 1], want.imag)):
-        g = g.astype(np.float64) * np.ldexp(1.0, e)                 # exact: a power of two
-        w = w * np.ldexp(1.0, e)
-        g16 = g.astype(np.float16)
-        halves = halves and bool(np.array_equal(g16.astype(np.float64), g))
-        rn = w.astype(np.float16)                                   # round to nearest even from float64
-        miss = g16 != rn
-        off += int(miss.sum())
-        if miss.any():
-            gm, wm = g16[miss], w[miss]
-            um = np.broadcast_to(unit, w.shape)[miss]
-            up = gm > rn[miss]
-            below = (gm.astype(np.float64) + np.nextafter(gm, np.float16(-np.inf)).astype(np.float64)) / 2   # midpoints next to the half
-            above = (gm.astype(np.float64) + np.nextafter(gm, np.float16(np.inf)).astype(np.float64)) / 2
-            k = np.where(up, below - wm, wm - above) / um
-            need = max(need, float(k.max()))
-    return halves, need, off / got.size
-
-
-def _check(capi, oracle, report, oc, c, h0, wavescale, chop, fmt, label, want_phase):
-    """the three comparisons (and the structure check from 1024^2 up) for cascade c of a handle that has just displaced"""
-    N = h0.shape[0]
-    scale = np.float32(1) / np.float32(wavescale)
-    maps = oc.read_maps(c)
-    phase = oc.read_state(c)
-    assert np.array_equal(phase, want_phase), label
-    assert np.all(maps[..., 3] == 0) and np.isfinite(maps).all(), label
-    got = ref64.channels(maps)
-    del maps
-    rp = oc.debug_rowpass(c)
-    again = oc.debug_rowpass(c)
-    same = all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(rp, again))
-    del again
-    checks = []                    # (what, measured, bar): measured <= bar
-    structure = N >= 1024
-    energies = []
-
-    # 1. end to end
-    ref, ln = ref64.displace64(h0, phase, scale, chop, return_len=True)
-    if fmt == "fp32":
-        kd, kn, en = _pointwise(got, ref, ln, N, structure)
-        checks += [("e2e disp K", kd, K_MAP), ("e2e normal K", kn, K_NORMAL)]
-        if structure:
-            energies.append(("e2e", en))
-    else:
-        big = float(np.abs(ref[:3]).max())
-        ed = _rms(got[:3] - ref[:3]) / big
-        en_ = _rms(got[3:] - ref[3:])
-        checks += [("e2e fp16 disp rmse/max", ed, FP16_DISP_RMSE), ("e2e fp16 normal rmse", en_, FP16_NORMAL_RMSE)]
-        assert ed > 1e-7, label                                     # really went through halves
-    del ref, ln
-
-    # 2. row pass
-    if fmt == "fp32":
-        c64, d64 = ref64.rowpass64(h0, phase, scale)
-        kr = max(_rowpass_fp32(rp[0], c64, N), _rowpass_fp32(rp[1], d64, N))
-        checks += [("row K", kr, K_ROW)]
-        off = None
-    else:
-        e, eh = ref64.fp16_scales(h0, N)
-        c64, d64 = ref64.rowpass64(ref64.h0_as_halves(h0, eh) if fmt == "fp16h0" else h0, phase, scale)
-        hc, kc, oc_ = _rowpass_fp16(rp[0], c64, N, e)
-        hd, kd_, od = _rowpass_fp16(rp[1], d64, N, e)
-        assert hc and hd, (label, "a row-pass value times 2^e is not a half")
-        checks += [("row midpoint band K", max(kc, kd_), K_BAND)]
-        off = (oc_ + od) / 2
-    del c64, d64
-
-    # 3. column pass from the GPU's own row-pass output
-    ref, ln = ref64.colpass64(rp[0], rp[1], scale, chop, return_len=True)
-    del rp
-    kd, kn, en = _pointwise(got, ref, ln, N, structure)
-    checks += [("col disp K", kd, K_MAP), ("col normal K", kn, K_NORMAL)]
-    if structure:
-        energies.append(("col", en))
-    del ref, ln, got
-
-    # 4. structure
-    for what, en in energies:
-        cr, rr, br = _structure(en)
-        checks += [(f"{what} worst col/median", cr, STRUCT), (f"{what} worst row/median", rr, STRUCT), (f"{what} border/interior", br, BORDER)]
-    del energies
-
-    text = "; ".join(f"{w} {m:.3g} (bar {b:g}, margin {b / m if m > 0 else float('inf'):.1f}x)" for w, m, b in checks)
-    extra = f"; halves not the nearest {off:.2e}" if off is not None else ""
-    report(f"pointwise {label}: {text}{extra}")
-    assert same, (label, "two debug_rowpass calls differ")
-    for w, m, b in checks:
-        assert m <= b, (label, w, m, b)
 
 
 # every map form x every spectrum format: (N, map store policy, whether that policy streams)
